@@ -11,7 +11,14 @@ One rank per GPU, one sample per rank, no collective on the data path ("scaling"
 torch.distributed is used only for the barrier and the max-over-ranks time.
 
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed inside the timed
-region) and, at N = 1, `cpu_baseline` (the oracle on a bounded sample of the same workload).
+region) and, at N = 1, `cpu_baseline` (the oracle on a bounded sample of the same workload).  The
+line holds the headline fields only (LINE_KEYS); the whole record, every secondary leg and note
+included, goes to `--details FILE` (default bench_details.json in the working directory).
+
+`--steps K` is the number of timed steps (`--min-seconds S` > 0 repeats the region of K steps until
+S seconds of timed work).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64): the count tables and a seeded sample of the per-read
+annotation; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +60,54 @@ ALGO_BYTES = {
     "k_trim": 2 * 50 + 16,           # sequence + quality bytes of a 50-cycle record in, new bounds out
     "k_scan_blocksums": 8,
 }
+
+# the keys of the printed line, in this order when present; the rest of the record goes to --details only (a 20 kB line of
+# secondary legs and prose outgrew what a driver keeps of stdout and went unparsed)
+LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+             "dtype", "data", "config", "timing", "barrier_backend", "barrier_backend_note", "rccl_ranks_seen",
+             "collapsed_reads_per_s_M", "stage_ms_per_step", "roofline", "kernels", "setup_s", "parity", "cpu_baseline",
+             "cpu_baseline_reference_error", "parity_on_cpu_sample", "details", "details_error", "outputs")
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_READ_ROWS = 1 << 20  # unique reads in the per-read sample (40 B each as written)
+DUMP_SEED = 20261015
+
+
+def step_outputs(cls, ex, iso, tally, counts, first, ann, rows=DUMP_READ_ROWS, seed=DUMP_SEED):
+    """What one step hands its caller, keyed by file name: the count tables whole, and the per-read annotation of the unique
+    reads in first-appearance order (the order of the raw reads, whatever order the collapse left them in) -- all of them, or
+    a seeded sample of `rows` positions of that order when there are more."""
+    order = np.argsort(first, kind="stable")
+    if order.shape[0] > rows:
+        order = order[np.sort(np.random.Generator(np.random.PCG64(seed)).choice(order.shape[0], rows, replace=False))]
+    ps, ref, off, mm = ann
+    out = {"class_counts": cls, "exact_mirna_counts": ex, "isomir_mirna_counts": iso,
+           "unique_reads": np.array([first.shape[0]], dtype=np.int64),
+           "read_first_index": first[order], "read_count": counts[order], "read_pass": ps[order], "read_ref": ref[order],
+           "read_offset": off[order], "read_mismatches": mm[order]}
+    if tally is not None:
+        out["variant_tally"] = tally
+    return out
+
+
+def write_outputs(path, arrays, limit=DUMP_MAX_BYTES):
+    """path/<name>.npy for every array: integers of up to 16 bits as float32, wider ones as float64 (exact below 2^53), floats
+    as they are; refuses to write more than `limit` bytes in all"""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind in "biu":
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        elif a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        conv[name] = a
+    total = sum(a.nbytes for a in conv.values())
+    if total > limit:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {limit}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def algo_bytes(name, per_pass=False):
@@ -164,7 +219,7 @@ def pmc_traffic(args, rec_name):
         # rocprofv3 is a python script: run it with this interpreter (no '#!/usr/bin/env' hop)
         cmd = [sys.executable, rocprof, "--pmc", ctr, "--output-format", "csv", "-d", d, "--", sys.executable,
                os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-baseline", "0", "--pmc", "0",
-               "--min-seconds", "0", "--spinup", "0", "--cli-path", "0", "--two-in-flight", "0", "--read-sets", "0",
+               "--min-seconds", "0", "--spinup", "0", "--cli-path", "0", "--two-in-flight", "0", "--read-sets", "0", "--details", "",
                "--reads", str(args.reads), "--scale", args.scale, "--workload", args.workload, "--pool", str(args.pool)]
         try:
             subprocess.run(cmd, timeout=900, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"),
@@ -866,8 +921,9 @@ def main():
     ap.add_argument("--pool", type=int, default=0,
                     help="draw the reads from this many templates with Zipf weights (SURVEY 8d 'realistic' U/N); 0 = independent draws")
     ap.add_argument("--cli-path", type=int, default=1, help="rank 0, N=1: also time the CLI's route from a FASTQ file on disk to all CSVs")
-    ap.add_argument("--min-seconds", dest="min_seconds", type=float, default=2.0,
-                    help="repeat the timed region of --steps steps until this much timed work has been seen (0 = one region)")
+    ap.add_argument("--min-seconds", dest="min_seconds", type=float, default=0.0,
+                    help="repeat the timed region of --steps steps until this much timed work has been seen (0, the default: one "
+                         "region, exactly --steps timed steps)")
     ap.add_argument("--spinup", type=float, default=0.3, help="seconds of untimed steps before the timed region (clock state)")
     ap.add_argument("--two-in-flight", dest="two_in_flight", type=int, default=1,
                     help="rank 0, N=1: also measure the step with TWO samples in flight on two contexts (never `value`)")
@@ -877,6 +933,10 @@ def main():
                     help="N > 1: also time the sharded CLI's whole route, FASTQ files -> all output files, tail included (never `value`)")
     ap.add_argument("--pmc", type=int, default=1,
                     help="rank 0, N=1: measure the dominant kernel's HBM traffic with two child rocprofv3 --pmc passes")
+    ap.add_argument("--details", default="bench_details.json",
+                    help="rank 0: write the whole record (secondary legs and notes included) to this JSON file ('' = none)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="rank 0: write what the last timed step computed as DIR/<name>.npy (float32/float64, at most 64 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -983,8 +1043,17 @@ def main():
         state["cls"] = cls
         if state.get("want_groups"):
             state["groups"] = uniq.group_counts()
+        if state.get("keep"):  # the last timed step under --dump-outputs: its read set and result stay open for the dump
+            state["kept"] = (uniq, res, cls, ex, iso, state.get("tally"))
+            return
         res.close()
         uniq.close()
+
+    def release_kept():
+        kept = state.pop("kept", None)
+        if kept is not None:
+            kept[1].close()
+            kept[0].close()
 
     def barrier():
         ctx.sync()
@@ -1042,9 +1111,11 @@ def main():
     ctx.profile_reset()
     region_s, step_ms = [], []
     while True:
+        release_kept()  # a region before this one kept its last step: not the last step after all
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for i in range(args.steps):
+            state["keep"] = bool(args.dump_outputs) and i == args.steps - 1
             ts = time.perf_counter()
             step()  # ends with the count tables on the host: synchronous
             step_ms.append((time.perf_counter() - ts) * 1e3)
@@ -1064,6 +1135,14 @@ def main():
     value = n_gpus * args.reads / (elapsed / timed_steps) / 1e6
     per_region_ms = sorted(r / args.steps * 1e3 for r in region_s)
     sm = np.sort(np.asarray(step_ms))
+    state["keep"] = False
+    dumped = None
+    if "kept" in state:
+        uniq_k, res_k, cls_k, ex_k, iso_k, tally_k = state["kept"]
+        if rank == 0:
+            counts_k, first_k = uniq_k.counts()
+            dumped = write_outputs(args.dump_outputs, step_outputs(cls_k, ex_k, iso_k, tally_k, counts_k, first_k, res_k.fetch()))
+        release_kept()
 
     # ---------------- per-kernel accounting
     # `kernels` (all launches bracketed) comes from the profiled warm-up steps; the dominant kernel's
@@ -1145,6 +1224,8 @@ def main():
                         "units_per_launch": round(v["units_per_launch"], 1)} for k, v in sorted(kernels.items())},
         "setup_s": round(t_setup, 1),
     }
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
     if whole_cascade and per_pass_units:
         a18 = algo_bytes(dom, per_pass=True) * per_pass_units / (kd["avg_ms"] * 1e-3) / 1e9
         out["roofline"]["per_pass_units"] = {
@@ -1511,7 +1592,14 @@ def main():
                     "note": "SQ_INSTS_VALU (own --pmc pass) x 4 issue cycles / (256 CUs x 4 SIMDs x 2.4 GHz peak shader clock x launch "
                             "time): the share of the chip's vector-issue cycles the kernel uses"}
     if rank == 0:
-        print(json.dumps(out))
+        if args.details:
+            out["details"] = args.details
+            try:
+                with open(args.details, "w") as fh:
+                    json.dump(out, fh)
+            except OSError as e:  # the headline line stands without its details
+                out["details"], out["details_error"] = None, repr(e)[:200]
+        print(json.dumps({k: out[k] for k in LINE_KEYS if k in out}))
     raw.close()
     casc.close()
     if dist is not None:

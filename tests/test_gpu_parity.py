@@ -827,11 +827,14 @@ def test_bench_two_ranks_share_the_gpu(tmp_path):
     env = dict(os.environ, MIRGE_BENCH_SHARE_GPU="1", MIRGE_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--reads", "300000", "--scale", "ci", "--cpu-baseline", "0", "--pmc", "0", "--min-seconds", "0.5"]
+           "--warmup", "1", "--reads", "300000", "--scale", "ci", "--cpu-baseline", "0", "--pmc", "0", "--min-seconds", "0.5",
+           "--details", str(tmp_path / "details.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
-    d = json.loads(line)
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    with open(tmp_path / "details.json") as fh:
+        d = json.load(fh)  # the whole record: the line's fields and the secondary legs (c4_end_to_end)
+    assert all(d[k] == v for k, v in line.items())
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert "cpu_baseline" not in d and d["roofline"]["frac"] > 0
     # under torch.distributed.run without --workload the line describes BASELINE configs[3], with the numbers actually run
@@ -868,7 +871,7 @@ def test_bench_barrier_over_rccl_with_one_rank(tmp_path):
     env = dict(os.environ, MIRGE_BENCH_FORCE_DIST="1", OMP_NUM_THREADS="8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "300000",
-           "--scale", "ci", "--cpu-baseline", "0", "--pmc", "0", "--min-seconds", "0", "--workload", "c3", "--cli-path", "0", "--read-sets", "0"]
+           "--scale", "ci", "--cpu-baseline", "0", "--pmc", "0", "--workload", "c3", "--cli-path", "0", "--read-sets", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -892,16 +895,30 @@ def test_bench_single_gpu_line(tmp_path):
     import subprocess
     import sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    details, dump = str(tmp_path / "details.json"), str(tmp_path / "outputs")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--reads", "400000", "--scale", "ci",
-           "--pmc", "0", "--min-seconds", "0.5"]
+           "--pmc", "0", "--min-seconds", "0.5", "--details", details, "--dump-outputs", dump]
     r = subprocess.run(cmd, env=dict(os.environ, OMP_NUM_THREADS="8"), capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    assert len(lines[0]) < 12_000  # a 20 kB line outgrew what a driver keeps of stdout and went unparsed
+    line = json.loads(lines[0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-              "dtype", "data", "config", "roofline", "cpu_baseline"):
-        assert k in d, k
+              "dtype", "data", "config", "roofline", "cpu_baseline", "kernels", "timing"):
+        assert k in line, k
+    # the whole record, secondary legs included, is the details file; the line is its headline
+    with open(details) as fh:
+        d = json.load(fh)
+    assert line["details"] == details and all(d[k] == v for k, v in line.items())
+    # --dump-outputs: the last timed step's count tables and per-read annotation (every unique read at this size)
+    o = {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+    assert line["outputs"]["bytes"] == sum(a.nbytes for a in o.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in o.values())
+    assert o["class_counts"].shape == (9, 1) and o["unique_reads"][0] == d["config"]["unique_reads_per_gpu"] == o["read_count"].shape[0]
+    assert np.all(np.diff(o["read_first_index"]) > 0) and o["read_count"].sum() == d["config"]["raw_reads_per_gpu"]
+    for p in range(9):
+        assert o["read_count"][o["read_pass"] == p].sum() == o["class_counts"][p, 0], p
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["vs_baseline"] is None and d["dtype"] == "u64"
     tm = d["timing"]
     assert tm["timed_seconds"] >= 0.5 and tm["timed_steps"] == 3 * tm["regions"] and d["barrier_backend"] is None

@@ -68,6 +68,42 @@ def test_bench_names_the_kernels_the_library_holds():
         assert frag in names, (rec, frag)
 
 
+def test_bench_dump_outputs_are_exact_and_fixed(tmp_path):
+    """bench.py --dump-outputs: the per-read arrays come in first-appearance order whatever order the collapse left the unique
+    reads in, a larger set is sampled at the same positions every time, every integer survives the float32/float64 files
+    exactly, and the 64 MB limit is enforced."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(os.path.dirname(__file__), "..", "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    U = 5000
+    first = rng.permutation(40_000)[:U].astype(np.int64)
+    counts = rng.integers(1, 1 << 31, size=(U, 1)).astype(np.uint32)
+    ann = (rng.integers(-1, 9, U).astype(np.int8), rng.integers(-1, 1 << 30, U).astype(np.int32),
+           rng.integers(-1, 1 << 30, U).astype(np.int32), rng.integers(-1, 3, U).astype(np.int8))
+    cls = rng.integers(0, 1 << 40, size=(9, 1))
+    ex = iso = rng.integers(0, 1 << 40, size=(7, 1))
+    a = bench.step_outputs(cls, ex, iso, None, counts, first, ann, rows=300)
+    perm = rng.permutation(U)  # the same unique reads in another order: the same sample
+    b = bench.step_outputs(cls, ex, iso, None, counts[perm], first[perm], tuple(x[perm] for x in ann), rows=300)
+    assert set(a) == set(b) and "variant_tally" not in a
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert a["read_first_index"].shape == (300,) and np.all(np.diff(a["read_first_index"]) > 0) and a["unique_reads"][0] == U
+    whole = bench.step_outputs(cls, ex, iso, cls, counts, first, ann)
+    assert np.array_equal(whole["read_first_index"], np.sort(first)) and np.array_equal(whole["variant_tally"], cls)
+    n = bench.write_outputs(str(tmp_path / "out"), whole)
+    assert n == sum(os.path.getsize(str(tmp_path / "out" / (k + ".npy"))) - 128 for k in whole)
+    for k, v in whole.items():
+        got = np.load(str(tmp_path / "out" / (k + ".npy")))
+        assert got.dtype == (np.float32 if v.dtype.itemsize == 1 else np.float64), k
+        assert np.array_equal(got.astype(np.int64), v.astype(np.int64)), k
+    with pytest.raises(ValueError, match="limit"):
+        bench.write_outputs(str(tmp_path / "big"), whole, limit=n - 1)
+    assert not os.path.exists(str(tmp_path / "big"))
+
+
 def test_policy_tables_agree_with_oracle():
     # the product's table and the oracle's are written independently from manifoldAlign.py:84-85
     for p, (col, key, args, kw) in enumerate(PASSES):
