@@ -1125,16 +1125,11 @@ __device__ __forceinline__ void spec_pick_one(const FusedSteps* __restrict__ ste
     res_ref[idx] = ref; res_off[idx] = off;
 }
 
-// `tickets` (one counter per round of 256 reads, zero between launches) = the pick in the same launch: the workgroup that finishes a
-// round's LAST step picks for that round's reads (its ticket is the count of steps before it) and puts the counter back to zero.
-// nullptr: the answers only, k_cascade_pick follows.  `stride` = the answers' row length (a multiple of 256: no two rounds share a line).
+// `stride` = the answers' row length (a multiple of 256: no two rounds share a line)
 template <int W, bool HASN, bool REP>
 __global__ void __launch_bounds__(MIRGE_BLOCK)
-k_cascade_spec(const FusedSteps* __restrict__ steps, ResolveTable tb, GroupView<W> g, unsigned long long* __restrict__ answers /*[nsteps][stride]*/,
-               uint32_t stride, uint32_t* __restrict__ tickets, int8_t* __restrict__ res_pass, uint32_t* __restrict__ res_pos,
-               int8_t* __restrict__ res_mm, int32_t* __restrict__ res_ref, int32_t* __restrict__ res_off, uint32_t* __restrict__ heavy_cnt,
-               uint32_t* __restrict__ heavy_list) {
-    __shared__ uint32_t s_last;
+k_cascade_spec(const FusedSteps* __restrict__ steps, GroupView<W> g, unsigned long long* __restrict__ answers /*[nsteps][stride]*/,
+               uint32_t stride) {
     const int si = blockIdx.y;
     const FusedStep& st = steps->s[si];
     const uint32_t idx = blockIdx.x * MIRGE_BLOCK + threadIdx.x;
@@ -1152,18 +1147,6 @@ k_cascade_spec(const FusedSteps* __restrict__ steps, ResolveTable tb, GroupView<
     psrc.g = st.plan; psrc.l = nullptr;
     align_hybrid<W, false, REP>(st.lib, st.pol, st.mi, psrc, r2, elig, best);
     if (valid) answers[(size_t)si * stride + idx] = elig ? best : MIRGE_NO_HIT;
-    if (!tickets) return;
-    __threadfence();  // this workgroup's answers are out (agent scope) before its ticket is drawn
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t t = __hip_atomic_fetch_add(&tickets[blockIdx.x], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == gridDim.y - 1 ? 1u : 0u;
-        if (s_last) __hip_atomic_store(&tickets[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();  // ... and the other steps' answers are read behind theirs
-    if (valid) spec_pick_one(steps, tb, stride, idx, answers, res_pass, res_pos, res_mm, res_ref, res_off, heavy_cnt, heavy_list);
 }
 
 template <int W>

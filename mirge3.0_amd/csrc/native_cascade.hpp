@@ -281,28 +281,17 @@ static int cascade_group_fused(mirge_ctx* c, const ReadGroup& rg, ResGroup& out,
         const uint32_t rounds = (n + MIRGE_BLOCK - 1) / MIRGE_BLOCK, stride = rounds * MIRGE_BLOCK;
         CHECK(dalloc(c, &answers, (size_t)nsteps * stride));
         const dim3 grid(rounds, (unsigned)nsteps);
-        // MIRGE_SPEC_TICKETS=1 (round 6 experiment, OFF by default): the pick in the same launch (the workgroup that ends a round's last
-        // step does it: `tickets`, k_cascade_spec) -- one kernel less in a chain of launches the step's end waits for on a sample with few
-        // unique reads.  Measured WORSE (profiles/r06_ab_spec_tickets.txt): 0.539 vs 0.408 ms on that sample, 1.259 vs 1.190 ms on the
-        // default draw -- the two agent-scope fences per workgroup write back and invalidate the XCD's L2 under the bulk kernel that runs
-        // beside it (its own launch time: 0.84 vs 0.78 ms); a kernel boundary is the cheaper fence here.
-        static const bool tickets_on = std::getenv("MIRGE_SPEC_TICKETS") && std::atoi(std::getenv("MIRGE_SPEC_TICKETS")) == 1;
-        uint32_t* tickets = nullptr;
-        if (tickets_on && c->spec_tickets && rounds <= MIRGE_SPEC_TICKET_ROUNDS)
-            for (int gi = 0; gi < MIRGE_NGROUPS; gi++)
-                if (std::strcmp(group_tag(gi), gtag) == 0) tickets = c->spec_tickets + (size_t)gi * MIRGE_SPEC_TICKET_ROUNDS;
+        // (the pick as a launch of its own: inside k_cascade_spec its fences were slower, profiles/r06_ab_spec_*.txt)
         {
             std::snprintf(name, sizeof(name), "k_cascade_spec%s", gtag);
             LaunchScope ls(c, name, n);
 #define MIRGE_LAUNCH_SPEC(HASN_, REP_)                                                                                                          \
-    hipLaunchKernelGGL((k_cascade_spec<W, HASN_, REP_>), grid, dim3(MIRGE_BLOCK), 0, c->cur, dsteps, rt, view_of<W>(rg), answers, stride, tickets, \
-                       out.pass, out.pos, out.mm, out.ref, out.off, hcnt, hlist)
+    hipLaunchKernelGGL((k_cascade_spec<W, HASN_, REP_>), grid, dim3(MIRGE_BLOCK), 0, c->cur, dsteps, view_of<W>(rg), answers, stride)
             if (rg.nmask) { if (c->casc_rep) MIRGE_LAUNCH_SPEC(true, true); else MIRGE_LAUNCH_SPEC(true, false); }
             else { if (c->casc_rep) MIRGE_LAUNCH_SPEC(false, true); else MIRGE_LAUNCH_SPEC(false, false); }
 #undef MIRGE_LAUNCH_SPEC
-            if (!tickets)
-                hipLaunchKernelGGL(k_cascade_pick<W>, dim3(rounds), dim3(MIRGE_BLOCK), 0, c->cur, dsteps, rt, n, stride,
-                                   (const unsigned long long*)answers, out.pass, out.pos, out.mm, out.ref, out.off, hcnt, hlist);
+            hipLaunchKernelGGL(k_cascade_pick<W>, dim3(rounds), dim3(MIRGE_BLOCK), 0, c->cur, dsteps, rt, n, stride,
+                               (const unsigned long long*)answers, out.pass, out.pos, out.mm, out.ref, out.off, hcnt, hlist);
         }
         if (hcnt) launch_heavy<W>(c, rg, out, dsteps, rt, gtag, hcnt, hlist, view_of<W>(rg), true);
         c->defer(hlist); c->defer(answers);
@@ -425,10 +414,6 @@ static int cascade_prepare(mirge_ctx* c, const mirge_lib* const* libs, const mir
         if (big_t_env && st.lib->max_bucket > big_t_env) c->casc_big_t = big_t_env;
     }
     if (!c->casc_rep) c->casc_big_t = 0;  // (only the repeat-aware build defers)
-    if (!c->spec_tickets) {  // (k_cascade_spec's per-round counters, one row per read group; zero between launches)
-        HIPOK(hipMalloc((void**)&c->spec_tickets, (size_t)MIRGE_NGROUPS * MIRGE_SPEC_TICKET_ROUNDS * 4));
-        HIPOK(hipMemset(c->spec_tickets, 0, (size_t)MIRGE_NGROUPS * MIRGE_SPEC_TICKET_ROUNDS * 4));
-    }
     if (c->casc_big_t && !c->heavy_cnt) {
         HIPOK(hipMalloc((void**)&c->heavy_cnt, 2 * MIRGE_NGROUPS * 4));
         HIPOK(hipMemset(c->heavy_cnt, 0, 2 * MIRGE_NGROUPS * 4));
@@ -590,15 +575,12 @@ static int cascade_launch_groups(mirge_ctx* c, const mirge_reads* R, mirge_resul
     // the largest small group first: it gets extra stream 0, the one the main stream waits for directly (stream_join)
     std::stable_sort(order, order + no, [&](int a, int b) { return R->g[a].n > R->g[b].n; });
     order[no++] = big;
-    // every small group's one-launch cascade on a stream of its own, behind whatever `aux` still holds for them
-    static const bool xaux_on = !(std::getenv("MIRGE_XAUX") && std::atoi(std::getenv("MIRGE_XAUX")) == 0);
-    int n_small = 0;
-    for (int k = 0; k < MIRGE_NGROUPS; k++)
-        if (order[k] != skip && order[k] != big && R->g[order[k]].n && R->g[order[k]].n <= fused_max) n_small++;
-    const bool spread = xaux_on && n_small > 1;
-    if (spread && !c->xaux_forked) CHECK(xaux_fork(c));
-    // (the same assignment as small_group_slots, native_collapse.hpp; with `xaux_forked` the caller's own: small_slot)
-    int slot = 0;
+    // every small group's one-launch cascade on an extra stream, behind whatever `aux` still holds for them (with `xaux_forked`:
+    // behind its own scatter kernel, which collapse_impl put on the slot this computes again from the same counts)
+    uint32_t n[MIRGE_NGROUPS];
+    int slot[MIRGE_NGROUPS];
+    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) n[gi] = R->g[gi].n;
+    if (small_group_slots(n, big, skip, slot) && !c->xaux_forked) CHECK(xaux_fork(c));
     for (int k = 0; k < MIRGE_NGROUPS && rc == 0; k++) {
         const int gi = order[k];
         if (gi == skip) continue;
@@ -608,8 +590,7 @@ static int cascade_launch_groups(mirge_ctx* c, const mirge_reads* R, mirge_resul
             continue;
         }
         if (gi != big && R->g[gi].n <= fused_max) {
-            if (c->xaux_forked) { if (c->small_slot[gi] >= 0) c->cur = c->xaux[c->small_slot[gi]]; }  // behind its own scatter kernel
-            else if (spread && R->g[gi].n) c->cur = c->xaux[xaux_slot_of(slot++)];
+            if (slot[gi] >= 0) c->cur = c->xaux[slot[gi]];
             MIRGE_BY_WIDTH(gi, rc, cascade_group_fused<W>(c, R->g[gi], res->g[gi], dsteps, rt, group_tag(gi)));
             continue;
         }
@@ -620,7 +601,7 @@ static int cascade_launch_groups(mirge_ctx* c, const mirge_reads* R, mirge_resul
     c->x0_gathered = false;
     if (rc == 0 && c->xaux_forked && c->xaux_used) {
         hipError_t e = hipSuccess;
-        for (int k = 1; k < xaux_slots() && e == hipSuccess; k++) {  // (the streams small_slot names)
+        for (int k = 1; k < MIRGE_N_SLOTS && e == hipSuccess; k++) {
             e = hipEventRecord(c->ev_xjoin[k], c->xaux[k]);
             if (e == hipSuccess) e = hipStreamWaitEvent(c->xaux[0], c->ev_xjoin[k], 0);
         }
@@ -715,15 +696,14 @@ extern "C" int mirge_cascade_walks(mirge_ctx* c, int32_t* walks) {
 // memory: k_pass / k_resolve `n_dev`), so the GPU does not idle while the host wakes up, finishes the small groups'
 // collapse and enqueues the cascade (~0.1 ms of a 2 ms step).  Same results as mirge_collapse followed by
 // mirge_cascade_run, which is also what runs when the bulk group is not on the partitioned key path or its
-// partition overflowed (MIRGE_NO_PRESYNC=1 forces that, for A/B).
+// partition overflowed.
 extern "C" int mirge_collapse_cascade(mirge_ctx* c, const mirge_reads* raw, const mirge_lib* const* libs, const mirge_policy* pol,
                                       int32_t n_pass, mirge_reads** uniq, int64_t* n_uniq, mirge_result** out) {
     if (!c || !raw || !libs || !pol || !uniq || !out || n_pass < 1 || n_pass > MIRGE_MAX_PASSES)
         return fail(-1, "mirge_collapse_cascade: bad argument");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
-    static const bool presync_off = std::getenv("MIRGE_NO_PRESYNC") != nullptr;
     mirge_reads* U = nullptr;
-    if (presync_off || !raw->hist_valid || raw->n == 0) {
+    if (!raw->hist_valid || raw->n == 0) {
         CHECK(mirge_collapse(c, raw, nullptr, 1, &U, n_uniq));
         const int rc = mirge_cascade_run(c, U, libs, pol, n_pass, out);
         if (rc) { mirge_reads_destroy(U); return rc; }

@@ -395,37 +395,29 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
                          int64_t* n_uniq, CollapseHook* hook, const uint32_t* weights = nullptr, int32_t* dsample_in = nullptr,
                          uint32_t* dweight_in = nullptr);
 
-// How many of the extra streams the small groups are dealt over (MIRGE_XAUX_SLOTS, default 2).  The runtime maps this context's streams
-// onto four hardware queues: a third extra stream shares a queue with the second, and two streams taking turns on one queue pay a
-// dependency packet per turn (~12 us, profiles/r06_timeline_zipf.txt).  Two: 0.382 vs 0.409 ms on the sample with few unique reads,
-// 1.197 vs 1.195 ms on the default draw (profiles/r06_ab_xaux_slots.txt; largest group alone on a stream, the others chained: the same).
-static int xaux_slots() {
-    static const int v = std::getenv("MIRGE_XAUX_SLOTS") ? std::max(1, std::min(MIRGE_N_XAUX, std::atoi(std::getenv("MIRGE_XAUX_SLOTS")))) : 2;
-    return v;
-}
-static int xaux_slot_of(int k) { return k % xaux_slots(); }  // the k-th small group by size, 0 = the largest
 static uint32_t small_fused_max() {  // (cascade_launch_groups: the largest group that takes the one-launch cascade)
     static const uint32_t v = std::getenv("MIRGE_FUSED_MAX") ? (uint32_t)std::strtoul(std::getenv("MIRGE_FUSED_MAX"), nullptr, 10) : (1u << 19);
     return v;
 }
-// Which extra stream the one-launch cascade of every small read group takes (cascade_launch_groups assigns them this way): the groups
-// other than `big` by size, largest first; one slot each for those that take the one-launch route, when there is more than one; -1:
-// the second stream.  n[gi] = reads of group gi.
-static void small_group_slots(const uint32_t* n, int big, int* slot) {
+// Which extra stream the one-launch cascade of every small read group takes (collapse_impl puts its scatter kernel there too): the
+// groups other than `big` and `skip` by size, largest first, dealt over the extra streams in turn for those that take the one-launch
+// route; -1: the second stream.  n[gi] = reads of group gi.  Returns whether the small groups are spread (more than one, the long
+// class counted); otherwise every slot is -1.
+static bool small_group_slots(const uint32_t* n, int big, int skip, int* slot) {
     const uint32_t fused_max = small_fused_max();
-    static const bool xaux_on = !(std::getenv("MIRGE_XAUX") && std::atoi(std::getenv("MIRGE_XAUX")) == 0);
     int order[MIRGE_NGROUPS], no = 0;
-    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) { slot[gi] = -1; if (gi != big) order[no++] = gi; }
+    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) { slot[gi] = -1; if (gi != big && gi != skip) order[no++] = gi; }
     std::stable_sort(order, order + no, [&](int a, int b) { return n[a] > n[b]; });
     int n_small = 0;
     for (int k = 0; k < no; k++) if (n[order[k]] && n[order[k]] <= fused_max) n_small++;
-    if (!xaux_on || n_small <= 1) return;
+    if (n_small <= 1) return false;
     int next = 0;
     for (int k = 0; k < no; k++) {
         const int gi = order[k];
         if (is_long_group(gi) || !n[gi] || n[gi] > fused_max) continue;
-        slot[gi] = xaux_slot_of(next++);
+        slot[gi] = next++ % MIRGE_N_SLOTS;  // 0: the largest, the stream stream_join waits for directly
     }
+    return true;
 }
 
 extern "C" int mirge_collapse(mirge_ctx* c, const mirge_reads* raw, const int32_t* sample_ids, int32_t S,
@@ -477,44 +469,15 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
         // the CUs with it, then the bulk group's wide kernels.  Small groups entirely first left the GPU idle for
         // the ~0.2 ms their enqueue takes; entirely last, each of their kernels waits behind 2048-8192-workgroup
         // launches for CUs to drain and the join at the end waits for them (5.3 vs 3.8 ms).
-        // MIRGE_SPREAD_SMALL=1 (round 5 experiment, OFF by default): the small groups' chains SIDE BY SIDE -- the largest on
-        // `aux`, the others on extra streams of their own -- instead of one after the other on `aux`.  Measured worse: 1.29 vs
-        // 1.21 ms per C3 step (profiles/r05_ab_spread_small.txt): more kernels in flight beside k_part_split / k_part_dedup slow
-        // those, and the small groups' cascades end when the bulk kernel's workgroups retire whenever they start.
-        static const bool spread_on = std::getenv("MIRGE_SPREAD_SMALL") && std::atoi(std::getenv("MIRGE_SPREAD_SMALL")) == 1;
-        int small_stream[MIRGE_NGROUPS];  // -1: aux, k: xaux[k]
-        int n_spread = 0;
-        {
-            int largest = -1;
-            for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
-                small_stream[gi] = -1;
-                if (gi != big && raw->g[gi].n && (largest < 0 || raw->g[gi].n > raw->g[largest].n)) largest = gi;
-            }
-            if (spread_on && !c->overlap_mode && rc == 0)
-                for (int gi = 0; gi < MIRGE_NGROUPS; gi++)
-                    if (gi != big && gi != largest && raw->g[gi].n) small_stream[gi] = n_spread++ % MIRGE_N_XAUX;
-            if (n_spread && rc == 0) rc = xaux_fork(c);
-        }
-        // MIRGE_DEDUP_FIRST=1 (round 6 experiment): the bulk group's k_part_dedup enqueued with its first two kernels, ahead of the small
-        // groups' launches, instead of behind them
-        static const bool dedup_first = std::getenv("MIRGE_DEDUP_FIRST") && std::atoi(std::getenv("MIRGE_DEDUP_FIRST")) == 1;
+        // The small groups' chains one after the other on `aux`: side by side on extra streams was slower (profiles/r05_ab_spread_small.txt).
         for (int k = -1; k <= MIRGE_NGROUPS && rc == 0; k++) {
             const int gi = (k < 0 || k == MIRGE_NGROUPS) ? big : k;
             if (k >= 0 && k < MIRGE_NGROUPS && gi == big) continue;
-            if (dedup_first && k == MIRGE_NGROUPS) continue;
-            const int stage = k < 0 ? (dedup_first ? 0 : 1) : (k == MIRGE_NGROUPS ? 2 : 0);
-            c->cur = gi == big ? c->stream : (small_stream[gi] >= 0 ? c->xaux[small_stream[gi]] : c->aux);
+            const int stage = k < 0 ? 1 : (k == MIRGE_NGROUPS ? 2 : 0);
+            c->cur = gi == big ? c->stream : c->aux;
             if (is_long_group(gi)) rc = collapse_phase_a_long(c, gi, raw->g[gi], tmp[gi], dsample, S, dmeta, stage, dweight);
             else MIRGE_BY_WIDTH(gi, rc, collapse_phase_a<W>(c, gi, raw->g[gi], R->g[gi], tmp[gi], dsample, S, dmeta, attempt, stage, dweight));
             if (k < 0) hc.lap("first kernel of the bulk group enqueued");
-        }
-        if (n_spread && rc == 0) {  // `aux` behind the extra streams' chains: the counts it copies next are theirs too
-            hipError_t e = hipSuccess;
-            for (int k = 0; k < std::min(n_spread, MIRGE_N_XAUX) && e == hipSuccess; k++) {
-                e = hipEventRecord(c->ev_xjoin[k], c->xaux[k]);
-                if (e == hipSuccess) e = hipStreamWaitEvent(c->aux, c->ev_xjoin[k], 0);
-            }
-            if (e != hipSuccess) rc = fail(-2, std::string("mirge_collapse: ") + hipGetErrorString(e));
         }
         // (no join here: the second stream waits for the main one below and carries the read-back of the counts)
         c->cur = c->stream;
@@ -522,7 +485,6 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
         if (rc == -3 && attempt < 2) {
             // the partitioned attempts take up to 2 KiB of HBM per read (attempt 1); the global-atomic tables ~20 B.  A device
             // that cannot give the former (a second context in flight, a fragmented pool) is no reason to fail the call.
-            for (int k = 0; k < MIRGE_N_XAUX; k++) (void)hipStreamSynchronize(c->xaux[k]);
             (void)hipStreamSynchronize(c->aux); (void)hipStreamSynchronize(c->stream);
             for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
                 collapse_tmp_release(c, tmp[gi]);
@@ -543,8 +505,7 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
         // then the bulk group's count.  Measured NEUTRAL on the 10 M-read step (1.235 vs 1.238 ms, profiles/README.md round 5):
         // beside k_part_agg / k_part_split the small groups' own kernels end when k_part_dedup does, and their cascades end when
         // the bulk kernel's workgroups retire, whenever they start.  Kept: it cannot lose, and the host returns no later.
-        static const bool early_on = !(std::getenv("MIRGE_EARLY_SMALL") && std::atoi(std::getenv("MIRGE_EARLY_SMALL")) == 0);
-        if (rc == 0 && early_on && hook && hook->small_ready && attempt == 0 && tmp[big].partitioned && !c->overlap_mode) {
+        if (rc == 0 && hook && hook->small_ready && attempt == 0 && tmp[big].partitioned && !c->overlap_mode) {
             uint32_t* const small = c->pinned + 512;  // (the page-locked block holds 1024 words; the full copy takes the first 272)
             hipError_t e = hipMemcpyAsync(small, dmeta, MIRGE_NGROUPS * 4, hipMemcpyDeviceToHost, c->aux);
             if (e == hipSuccess) e = hipEventRecord(c->ev_meta_small, c->aux);
@@ -553,27 +514,25 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
                 rc = hook->pre_sync(R.get(), tmp, dmeta, big);
                 hooked = rc == 0;
             }
-            static const bool scatter_x = !(std::getenv("MIRGE_SCATTER_ON_XAUX") && std::atoi(std::getenv("MIRGE_SCATTER_ON_XAUX")) == 0);
             if (e == hipSuccess && hooked) e = hipEventSynchronize(c->ev_meta_small);
             if (e == hipSuccess && hooked) {
                 // (round 6) a small group's scatter kernel goes on the extra stream its one-launch cascade will take (small_ready ->
                 // cascade_launch_groups): the three scatters ran one after the other on the second stream (74 us on a sample with few
                 // unique reads) and every cascade then started a cross-stream hop (~22 us) behind the LAST of them -- now each group's
-                // scatter and cascade are neighbours on one stream and the groups run side by side.  MIRGE_SCATTER_ON_XAUX=0: as before.
+                // scatter and cascade are neighbours on one stream and the groups run side by side (profiles/r06_ab_scatter_stream_*.txt).
                 int xslot[MIRGE_NGROUPS];
                 uint32_t n_small_u[MIRGE_NGROUPS];
                 for (int gi = 0; gi < MIRGE_NGROUPS; gi++) n_small_u[gi] = gi == big ? 0u : small[gi];
-                small_group_slots(n_small_u, big, xslot);
+                small_group_slots(n_small_u, big, big, xslot);
                 bool forked = false;
-                for (int gi = 0; gi < MIRGE_NGROUPS; gi++) forked |= scatter_x && xslot[gi] >= 0;
+                for (int gi = 0; gi < MIRGE_NGROUPS; gi++) forked |= xslot[gi] >= 0;
                 // Not when a small group is large enough for the staged cascade (beyond MIRGE_FUSED_MAX unique reads: a 20 M-read sample's
                 // 32-64-nt group): its k_cascade_bulk<2> is a grid of resident workgroups like the bulk group's own, and whichever of the
                 // two is resident first keeps the other's remaining workgroups waiting until it retires.  With the scatter kernels one
                 // after the other on `aux` the bulk group's kernel has ~55 us of head start and is resident first in 83 of 87 steps; with
                 // them side by side in 55 of 79, and a step that loses the race takes 2.85 instead of 2.33 ms (20 M reads: 2.65 vs 2.26 ms
-                // per step on average, profiles/r06_ab_c4_shape.txt).  MIRGE_SCATTER_ON_XAUX=2: side by side regardless.
-                static const bool scatter_always = std::getenv("MIRGE_SCATTER_ON_XAUX") && std::atoi(std::getenv("MIRGE_SCATTER_ON_XAUX")) == 2;
-                for (int gi = 0; gi < MIRGE_NGROUPS && !scatter_always; gi++)
+                // per step on average, profiles/r06_ab_c4_shape.txt).
+                for (int gi = 0; gi < MIRGE_NGROUPS; gi++)
                     if (gi != big && !is_long_group(gi) && small[gi] > small_fused_max()) forked = false;
                 // The extra streams take over from `aux` here, once, for the scatter kernels AND the cascades (cascade_launch_groups skips
                 // its own fork: four runtime calls less in front of the cascades).  Queued BEFORE the host's wait instead -- the calls off
@@ -588,9 +547,7 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
                     else MIRGE_BY_WIDTH(gi, rc, collapse_phase_b<W>(c, gi, raw->g[gi], R->g[gi], tmp[gi], S, small[gi], 0u, dmeta));
                 }
                 c->cur = c->stream;
-                c->xaux_forked = forked;  // (cascade_launch_groups: the extra streams already stand behind `aux`, and where each group went)
-                static_assert(MIRGE_NGROUPS <= 16, "mirge_ctx::small_slot");
-                for (int gi = 0; gi < MIRGE_NGROUPS; gi++) c->small_slot[gi] = forked ? xslot[gi] : -1;
+                c->xaux_forked = forked;  // (cascade_launch_groups: the same slots again from the groups' unique counts, no second fork)
                 if (rc == 0) { rc = hook->small_ready(R.get(), big); small_done = rc == 0; }
                 c->xaux_forked = false;
             }

@@ -46,9 +46,12 @@ struct mirge_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_meta = nullptr, ev_meta_small = nullptr, ev_bulk_counted = nullptr;
     // the small read groups' one-launch cascades each on a stream of their own (round 3): with the bulk group's passes in one
     // launch they only get the chip when its workgroups retire, and on ONE stream three of them then ran one after the other
-    // (56 + 69 + 49 us behind the bulk kernel, with the join waiting); side by side they take what the longest takes
+    // (56 + 69 + 49 us behind the bulk kernel, with the join waiting); side by side they take what the longest takes.  They are dealt
+    // over the first MIRGE_N_SLOTS in turn by size (small_group_slots): a third shares a hardware queue with the second
+    // (profiles/r06_ab_xaux_slots.txt).  The third is still created and joined although it gets no work: without it the default
+    // workload's A/B came out 0.5 % slower, beyond the same build's own spread (0.46 %)
+#define MIRGE_N_SLOTS 2
 #define MIRGE_N_XAUX 3
-#define MIRGE_SPEC_TICKET_ROUNDS 8192  // groups of up to 2 M reads pick inside k_cascade_spec
     hipStream_t xaux[MIRGE_N_XAUX] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_xfork = nullptr, ev_xjoin[MIRGE_N_XAUX] = {nullptr, nullptr, nullptr};
     bool xaux_used = false;
@@ -88,9 +91,7 @@ struct mirge_ctx {
     // (x0_gathered), and the host has since waited for the last thing queued on `aux` (aux_drained): the main stream then waits for
     // extra stream 0 alone -- one dependency packet and four runtime calls instead of two and eight in the step's tail
     bool x0_gathered = false, aux_drained = false;
-    bool xaux_forked = false;  // collapse_impl -> cascade_launch_groups: the extra streams were put behind `aux` for the scatter kernels,
-    int small_slot[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // ... group gi's on extra stream small_slot[gi] (-1: on `aux`): its cascade goes there too
-    uint32_t* spec_tickets = nullptr;  // [MIRGE_NGROUPS][MIRGE_SPEC_TICKET_ROUNDS], see k_cascade_spec
+    bool xaux_forked = false;  // collapse_impl -> cascade_launch_groups: the extra streams already stand behind `aux` (no second fork)
     uint32_t casc_big_t = 0;
     bool casc_rep = false;  // the configuration's libraries repeat themselves: the cascade kernels' repeat-aware build (align_hybrid<.., REP>)
     uint32_t* wg_pinned = nullptr;
@@ -222,8 +223,7 @@ static int stream_join(mirge_ctx* c) {
     c->cur = c->stream;
     hipError_t e = hipSuccess;
     const bool x = c->xaux_used;
-    static const bool short_join = !(std::getenv("MIRGE_SHORT_JOIN") && std::atoi(std::getenv("MIRGE_SHORT_JOIN")) == 0);  // A/B
-    const bool only_x0 = short_join && x && c->x0_gathered && c->aux_drained;
+    const bool only_x0 = x && c->x0_gathered && c->aux_drained;
     c->x0_gathered = c->aux_drained = false;
     if (only_x0) {
         c->xaux_used = false;
@@ -289,16 +289,14 @@ extern "C" int mirge_ctx_create(int device, void* hip_stream, mirge_ctx** out) {
     hipDeviceProp_t prop;
     HIPOK(hipGetDeviceProperties(&prop, device));
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // MIRGE_STREAM_PRIORITY=1 (round 6 experiment): the main stream at the device's highest stream priority, the side streams at its lowest
-    static const bool prio = std::getenv("MIRGE_STREAM_PRIORITY") && std::atoi(std::getenv("MIRGE_STREAM_PRIORITY")) == 1;
-    int p_low = 0, p_high = 0;
-    if (prio) HIPOK(hipDeviceGetStreamPriorityRange(&p_low, &p_high));
+    // (every stream at normal priority: the main one high and the side ones low made the 20 M-read shape 27 % slower,
+    // profiles/r06_ab_stream_priority.txt)
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; }
-    else { HIPOK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, p_high)); c->own_stream = true; }
+    else { HIPOK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
     c->cur = c->stream;
-    HIPOK(hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, p_low));
+    HIPOK(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
     for (int k = 0; k < MIRGE_N_XAUX; k++) {
-        HIPOK(hipStreamCreateWithPriority(&c->xaux[k], hipStreamNonBlocking, p_low));
+        HIPOK(hipStreamCreateWithFlags(&c->xaux[k], hipStreamNonBlocking));
         HIPOK(hipEventCreateWithFlags(&c->ev_xjoin[k], hipEventDisableTiming));
     }
     HIPOK(hipEventCreateWithFlags(&c->ev_xfork, hipEventDisableTiming));
@@ -333,7 +331,6 @@ extern "C" void mirge_ctx_destroy(mirge_ctx* c) {
     if (c->csv_pinned) (void)hipHostFree(c->csv_pinned);
     if (c->wg_pinned) (void)hipHostFree(c->wg_pinned);
     if (c->heavy_cnt) (void)hipFree(c->heavy_cnt);
-    if (c->spec_tickets) (void)hipFree(c->spec_tickets);
     if (c->join_dev) (void)hipFree(c->join_dev);
     for (auto& e : c->plans) (void)hipFree(e.dplan);
     for (auto& e : c->fused) (void)hipFree(e.dev);
