@@ -360,6 +360,27 @@ int mirge_gff_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
                            const int64_t* parent_off, int64_t n_parents, const int64_t* order, const char* path, const char* head,
                            const char* source, int64_t* n_lines_out);
 
+/* ---- the A-to-I report's genome filter: replaces the two whole-genome runs
+ * `bowtie <org>_genome -n 1 -f -a -3 2 SeqToMap.fasta` (mirge2_tRF_a2i.py:1056-1096) and `-n 0 ... SeqToJudge.fasta` (:1297-1316).
+ * mirge_genome_create         the genome from ASCII references (<org>_genome.fa): anything but A/C/G/T is ambiguous.
+ * mirge_genome_create_packed  the same from bowtie's own reference files, uploaded as they are: packed[n_packed] = .4.ebwt (2 bits
+ *                             per base, base i at bits 2*(i & 3) of byte i >> 2), rec_off / rec_len / rec_first[n_rec] = the
+ *                             .3.ebwt records (off ambiguous characters, then len bases; first: a new reference).  64-bit positions.
+ * mirge_genome_destroy        (before its context)
+ * mirge_genome_align_counts   out[n][3] = alignments of each query with 0, 1, 2 mismatches (saturating at UINT32_MAX) on both strands,
+ *                             every valid alignment (-a): trim5 / trim3 bases cut (-5 / -3), at most n_mm mismatches in the first
+ *                             min(seedlen, L) bases of the read's 5' end and maxtotal in all (-n; -e 70 with FASTA qualities: 2); an N in
+ *                             a query mismatches everything, a window with an ambiguous base or across two references is invalid; a
+ *                             query with L < 1 or L <= n_mm has none.  0 <= n_mm <= 2, maxtotal <= 2, L <= 64.  Restated from bowtie's
+ *                             documented -n policy (parity unpinned).                                                     */
+typedef struct mirge_genome mirge_genome;
+int mirge_genome_create(mirge_ctx* ctx, const char* ascii, const int64_t* offsets, int64_t n_refs, mirge_genome** out);
+int mirge_genome_create_packed(mirge_ctx* ctx, const uint8_t* packed, int64_t n_packed, const uint64_t* rec_off,
+                               const uint64_t* rec_len, const uint8_t* rec_first, int64_t n_rec, mirge_genome** out);
+void mirge_genome_destroy(mirge_genome* genome);
+int mirge_genome_align_counts(mirge_ctx* ctx, const mirge_genome* genome, const char* queries, const int64_t* offsets, int64_t n,
+                              int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, uint32_t* out);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

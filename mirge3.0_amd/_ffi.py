@@ -28,6 +28,7 @@ EXPORTS = [
     "mirge_count_join", "mirge_count_join_host", "mirge_annotation_csv", "mirge_annotation_csv_device", "mirge_variant_tally", "mirge_isomir_type", "mirge_gff_write", "mirge_gff_write_device", "mirge_ctx_timer_start", "mirge_ctx_timer_stop", "mirge_ctx_profile_enable",
     "mirge_reads_range_sample", "mirge_reads_range_split", "mirge_annotation_csv_device_sizes", "mirge_annotation_csv_device_at",
     "mirge_cascade_prepare", "mirge_cascade_walks", "mirge_cascade_wg_times", "mirge_ctx_profile_only", "mirge_ctx_profile_units", "mirge_ctx_profile_reset", "mirge_ctx_profile_count", "mirge_ctx_profile_get",
+    "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
 ]
 
 
@@ -107,7 +108,7 @@ def load() -> C.CDLL:
     lib.mirge_last_error.restype = C.c_char_p
     for name in ("mirge_lib_n_refs", "mirge_lib_device_bytes", "mirge_reads_count", "mirge_reads_total_bases"):
         getattr(lib, name).restype = C.c_int64
-    for name in ("mirge_lib_destroy", "mirge_reads_destroy", "mirge_result_destroy", "mirge_ctx_destroy"):
+    for name in ("mirge_lib_destroy", "mirge_reads_destroy", "mirge_result_destroy", "mirge_ctx_destroy", "mirge_genome_destroy"):
         getattr(lib, name).restype = None
     _lib = lib
     return lib
@@ -124,7 +125,7 @@ def _shutdown():
     then libraries, then contexts (a handle freed after its context is gone would crash at exit)."""
     objs = [r() for r in _live]
     objs = [o for o in objs if o is not None]
-    for kind in (CascadeResult, DeviceReads, DeviceLibrary, Context):
+    for kind in (CascadeResult, DeviceReads, DeviceLibrary, DeviceGenome, Context):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -280,7 +281,7 @@ class Context:
             # context's pool, and a handle destroyed after its context (a reference kept by a traceback, a cycle the collector
             # reaches late) would free into released memory
             objs = [o for o in (r() for r in _live) if o is not None and getattr(o, "ctx", None) is self]
-            for kind in (CascadeResult, DeviceReads, DeviceLibrary):
+            for kind in (CascadeResult, DeviceReads, DeviceLibrary, DeviceGenome):
                 for o in objs:
                     if isinstance(o, kind):
                         o.close()
@@ -378,6 +379,48 @@ class DeviceLibrary:
     def close(self):
         if self._h:
             load().mirge_lib_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceGenome:
+    """The genome of the A-to-I report's filter in HBM (``mirge_genome``): from ASCII references (``seqs``) or from bowtie's own
+    reference files as they are (``packed`` = the bytes of ``.4.ebwt``, ``records`` = the ``(off, len, first)`` arrays of
+    ``.3.ebwt``, ``ebwt.read_records``)."""
+
+    def __init__(self, ctx: Context, seqs: Optional[FlatSeqs] = None, packed: Optional[np.ndarray] = None, records=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        if seqs is not None:
+            data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
+            off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
+            _check(load().mirge_genome_create(ctx._h, _p(data), _p(off), C.c_int64(len(seqs)), C.byref(self._h)), "mirge_genome_create")
+        else:
+            pk = np.ascontiguousarray(packed, dtype=np.uint8)
+            ro, rl, rf = (np.ascontiguousarray(a, dtype=t) for a, t in zip(records, (np.uint64, np.uint64, np.uint8)))
+            _check(load().mirge_genome_create_packed(ctx._h, _p(pk), C.c_int64(pk.shape[0]), _p(ro), _p(rl), _p(rf),
+                                                     C.c_int64(ro.shape[0]), C.byref(self._h)), "mirge_genome_create_packed")
+        _track(self)
+
+    def align_counts(self, seqs: FlatSeqs, n_mm: int, seedlen: int = 28, maxtotal: int = 2, trim5: int = 0, trim3: int = 2) -> np.ndarray:
+        """``mirge_genome_align_counts`` -> uint32 [n, 3]: every query's alignments with 0, 1, 2 mismatches"""
+        n = len(seqs)
+        out = np.zeros((max(n, 1), 3), dtype=np.uint32)
+        data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
+        off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
+        _check(load().mirge_genome_align_counts(self.ctx._h, self._h, _p(data) if data.size else C.c_void_p(0), _p(off), C.c_int64(n),
+                                                C.c_int32(n_mm), C.c_int32(seedlen), C.c_int32(maxtotal), C.c_int32(trim5),
+                                                C.c_int32(trim3), _p(out)), "mirge_genome_align_counts")
+        return out[:n]
+
+    def close(self):
+        if self._h:
+            load().mirge_genome_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

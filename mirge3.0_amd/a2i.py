@@ -13,8 +13,10 @@ binomial p-value (:405-413), Benjamini-Hochberg (:1175-1183) -- and the files: `
 writing it (:1333-1350); it is kept here.
 
 The genome filter stays a predicate: the reference shells out to ``bowtie`` against ``<org>_genome``
-twice (:1056-1096, :1297-1316); ``BowtieGenome`` does exactly that through ``args.bowtie_path`` / PATH, ``ListedGenome``
-answers from two files of sequences, and any object with ``unique_best(seqs)`` / ``aligned(seqs)`` can be passed in.
+twice (:1056-1096, :1297-1316).  ``GpuGenome`` answers both runs with one streamed pass of the genome on the device
+(``mirge_genome_align_counts``; the genome is loaded once per process, ``load_genome``); ``BowtieGenome`` runs ``bowtie``
+through ``args.bowtie_path`` / PATH, ``ListedGenome`` answers from two files of sequences, and any object with
+``unique_best(seqs)`` / ``aligned(seqs)`` can be passed in.  ``genome_route`` picks one (``--genome-filter``).
 
 Parity: pinned against the reference's own functions and files (``tests/golden/case4_gff_a2i``) except for the
 aligner itself, which is Biopython's (absent here; restated, see ``tests/golden/stubs/Bio/pairwise2.py``).
@@ -24,7 +26,9 @@ from __future__ import annotations
 import math
 import os
 import shlex
+import shutil
 import subprocess
+import time
 from pathlib import Path
 from typing import Dict, Iterable, List, Optional, Sequence
 
@@ -108,6 +112,105 @@ class ListedGenome:
 
     def aligned(self, seqs):
         return {s for s in seqs if s in self._al}
+
+
+class GpuGenome:
+    """The same two answers from the genome on the device (``_ffi.DeviceGenome``): per distinct sequence the counts of its
+    alignments with 0, 1, 2 mismatches under the two runs' policies (``-n 1`` / ``-n 0``, ``-f -a -3 2``, both strands)."""
+    SEEDLEN, MAXTOTAL, TRIM3 = 28, 2, 2  # bowtie's -l default; -e 70 over FASTA's Q40 calls; -3 2
+
+    def __init__(self, ctx, genome):
+        self.ctx, self.genome = ctx, genome
+
+    def counts(self, seqs: Sequence[str], n_mm: int):
+        """-> (distinct sequences in first-seen order, uint32 [n, 3] counts, multiplicity of each in ``seqs``)"""
+        mult: Dict[str, int] = {}
+        for q in seqs:
+            mult[q] = mult.get(q, 0) + 1
+        distinct = list(mult)
+        c = self.genome.align_counts(FlatSeqs.from_list(distinct), n_mm, self.SEEDLEN, self.MAXTOTAL, 0, self.TRIM3)
+        return distinct, c, np.array([mult[q] for q in distinct], dtype=np.int64)
+
+    def unique_best(self, seqs: Sequence[str]) -> set:
+        # a sequence given k times has every alignment k times (the reference's dictionary merges its records by name): one
+        # alignment with the fewest mismatches only when k == 1 and that count is 1
+        distinct, c, k = self.counts(seqs, 1)
+        out = set()
+        for q, row, kq in zip(distinct, c.astype(np.int64), k):
+            nz = row[row > 0]
+            if nz.size and kq == 1 and nz[0] == 1:
+                out.add(q)
+        return out
+
+    def aligned(self, seqs: Sequence[str]) -> set:
+        distinct, c, _ = self.counts(seqs, 0)
+        return {q for q, row in zip(distinct, c) if row.any()}
+
+
+_GENOMES: Dict[tuple, object] = {}  # (context, index base) -> DeviceGenome: loaded on the first -ai sample, kept for the process
+
+
+def load_genome(ctx, base: str, timings: Optional[dict] = None):
+    """``<base>`` = ``<lib>/<org>/index.Libs/<org>_genome``: ``<base>.fa`` through ``seqio.load_index``, else bowtie's
+    ``.3`` / ``.4.ebwt[l]`` uploaded as they are (``ebwt.read_records``: no base is decoded on the host).  Once per process."""
+    key = (id(ctx), str(base))
+    g = _GENOMES.get(key)
+    if g is None or g.ctx is not ctx or not g._h:
+        from . import ebwt
+        from .seqio import load_index
+        t = time.perf_counter()
+        if os.path.exists(str(base) + ".fa"):
+            g = _ffi.DeviceGenome(ctx, seqs=load_index(str(base), use_cache=False).seqs)
+        elif ebwt.has_index(str(base)):
+            packed, off, ln, first = ebwt.read_records(str(base))
+            g = _ffi.DeviceGenome(ctx, packed=packed, records=(off, ln, first))
+        else:
+            raise FileNotFoundError(f"-ai: no genome at {base} (.fa or .1/.3/.4.ebwt[l])")
+        _GENOMES[key] = g
+        if timings is not None:
+            timings["genome_load_s"] = time.perf_counter() - t
+    elif timings is not None:
+        timings["genome_load_s"] = 0.0
+    return g
+
+
+def genome_base(args) -> Path:
+    return Path(args.libraries_path) / args.organism_name / "index.Libs" / (str(args.organism_name) + "_genome")
+
+
+def genome_route(args) -> str:
+    """``--genome-filter``: 'predicate' (a caller's object), 'listed' (--genome-retained), 'bowtie' or 'gpu'.  auto: the lists
+    when given, bowtie when -pbwt names one or PATH has one, else the device."""
+    if getattr(args, "genome_predicate", None) is not None:
+        return "predicate"
+    mode = getattr(args, "genome_filter", None) or "auto"
+    if mode == "gpu":
+        return "gpu"
+    if getattr(args, "genome_retained", None):
+        return "listed"
+    if mode == "bowtie" or getattr(args, "bowtie_path", None) or shutil.which("bowtie"):
+        return "bowtie"
+    return "gpu"
+
+
+class TimedGenome:
+    """a predicate with the seconds its two answers took (``genome_filter_s``)"""
+
+    def __init__(self, inner):
+        self.inner, self.seconds = inner, 0.0
+
+    def _timed(self, f, seqs):
+        t = time.perf_counter()
+        try:
+            return f(seqs)
+        finally:
+            self.seconds += time.perf_counter() - t
+
+    def unique_best(self, seqs):
+        return self._timed(self.inner.unique_best, seqs)
+
+    def aligned(self, seqs):
+        return self._timed(self.inner.aligned, seqs)
 
 
 # ---------------------------------------------------------------------------------------------------------------

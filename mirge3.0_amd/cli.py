@@ -73,8 +73,12 @@ def parse_args(argv=None):
     ap.add_argument("-gff", "--gff-out", dest="gff_out", action="store_true",
                     help="write sample_miRge3.gff (miRTop GFF3 of the miRNA reads, isomiR variant types from the GPU)")
     ap.add_argument("-ai", "--AtoI", dest="AtoI", action="store_true",
-                    help="A-to-I editing report (a2IEditing.report.csv, .newform.csv, .detail.txt); the genome filter runs "
-                         "`bowtie` against <org>_genome as the reference does (-pbwt / PATH), or reads --genome-retained")
+                    help="A-to-I editing report (a2IEditing.report.csv, .newform.csv, .detail.txt); its genome filter (the "
+                         "reference's two `bowtie <org>_genome` runs) takes the route --genome-filter picks")
+    ap.add_argument("--genome-filter", dest="genome_filter", choices=("auto", "bowtie", "gpu"), default="auto",
+                    help="-ai's genome filter.  gpu: one pass of <org>_genome (.fa or .ebwt) on the device.  bowtie: `bowtie` "
+                         "from -pbwt / PATH, or the lists of --genome-retained.  auto (default): the lists when given, bowtie when "
+                         "-pbwt names one or PATH has one, else gpu")
     ap.add_argument("-pbwt", "--bowtie-path", dest="bowtie_path", default=None,
                     help="directory of the bowtie binary used by -ai for the two whole-genome runs")
     ap.add_argument("--genome-retained", dest="genome_retained", default=None,
@@ -125,6 +129,8 @@ def parse_args(argv=None):
     args.bowtieVersion = "True"
     if (args.AtoI or args.gff_out) and (args.save_pkl or args.resume):
         ap.error("-ai / -gff run on the device-resident route: not together with -spl / -rr")
+    if args.genome_filter == "gpu" and args.genome_retained:
+        ap.error("--genome-filter gpu computes what --genome-retained lists: give one of them")
     if args.backend == "bowtie" and (args.AtoI or args.gff_out or args.isoform_entropy):
         ap.error("--backend bowtie writes the count tables and mapped.csv / unmapped.csv; -ai / -gff / -ie take per-read data of the GPU cascade")
     return args

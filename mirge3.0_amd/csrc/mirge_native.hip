@@ -46,3 +46,4 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_join.hpp"
 #include "native_csv.hpp"
 #include "native_iso.hpp"
+#include "native_genome.hpp"

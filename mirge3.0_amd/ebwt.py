@@ -129,8 +129,9 @@ def _name_lines(tail: bytes) -> List[bytes]:
     return body.split(b"\n")
 
 
-def read_sequences(base: str) -> Tuple[FlatSeqs, List[int]]:
-    """-> (sequences, records per sequence) decoded from ``.3.ebwt`` (records) + ``.4.ebwt`` (2-bit bases)."""
+def read_records(base: str):
+    """-> (packed, off, len, first): the bytes of ``.4.ebwt`` as they are (uint8) and the ``.3.ebwt`` records (int64, int64, bool)
+    -- the genome filter uploads these without decoding a base (a2i.load_genome)."""
     ext, osz = _suffix(base)
     p3, p4 = base + ".3" + ext, base + ".4" + ext
     if not (os.path.exists(p3) and os.path.exists(p4)):
@@ -159,6 +160,13 @@ def read_sequences(base: str) -> Tuple[FlatSeqs, List[int]]:
     total = int(ln.sum())
     if packed.size * 4 < total:
         raise ValueError(f"{p4}: {total} bases announced by {p3}, {packed.size * 4} present")
+    return packed, off, ln, first
+
+
+def read_sequences(base: str) -> Tuple[FlatSeqs, List[int]]:
+    """-> (sequences, records per sequence) decoded from ``.3.ebwt`` (records) + ``.4.ebwt`` (2-bit bases)."""
+    packed, off, ln, first = read_records(base)
+    nrec, total = off.shape[0], int(ln.sum())
     # unpack the 2-bit stream four bases at a time (one table look-up per packed byte), then lay the stretches out with their
     # runs of N in front: the output is [off_0 x N][ln_0 bases][off_1 x N][ln_1 bases]... in record order, so one boolean mask
     # of the output's length places every base -- no per-base index arrays (a 130 Mb index took 22 s with them, 1 s without)

@@ -281,14 +281,25 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
         tm["gff_s"] = time.perf_counter() - t
         tm["gff_stages_s"] = out["gff"].get("timing", {})
     if getattr(args, "AtoI", False):  # -ai (summary.py:1034-1057)
-        from .a2i import ListedGenome, a2i_report
+        from .a2i import BowtieGenome, GpuGenome, ListedGenome, TimedGenome, a2i_report, genome_base, genome_route, load_genome
         t = time.perf_counter()
-        genome = getattr(args, "genome_predicate", None)
-        if genome is None and getattr(args, "genome_retained", None):
+        route = genome_route(args)
+        if route == "predicate":
+            genome = args.genome_predicate
+        elif route == "listed":
             genome = ListedGenome.from_files(args.genome_retained, getattr(args, "genome_aligned", None))
+        elif route == "bowtie":
+            genome = BowtieGenome(args, workDir)
+        else:
+            genome = GpuGenome(ctx, load_genome(ctx, str(genome_base(args)), tm))
+        genome = TimedGenome(genome)
         out["a2i"] = a2i_report(args, workDir, ref_db, base_names, casc, uniq, res, seqs, ps, ref, counts, order, out, merges,
                                 genome=genome)
+        tm["genome_filter_s"] = genome.seconds
         tm["a2i_report_s"] = time.perf_counter() - t
+        with open(workDir / "run.log", "a+") as fh:
+            fh.write(f"A-to-I genome filter: {route}" + (f" ({genome_base(args)}, loaded in {tm.get('genome_load_s', 0.0):.3f} s)"
+                                                        if route == "gpu" else "") + f", {genome.seconds:.3f} s\n")
     if getattr(args, "isoform_entropy", False):  # -ie reads the miRNA rows of the mapped frame: build just those
         from .countjoin import isomir_entropy_tables
         isomir_entropy_tables(mirna_frame(seqs, ps, ref, counts, order, casc, base_names), base_names, out["filtered"], workDir)
