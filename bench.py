@@ -10,10 +10,16 @@ against human-sized libraries.  `--workload c2` is configs[1] (pa
 One rank per GPU, one sample per rank, no collective on the data path ("scaling": "weak");
 torch.distributed is used only for the barrier and the max-over-ranks time.
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the
+line.  `--full` adds every secondary leg after the timed region: the CPU baseline with its parity
+check, the other read sets, the FASTQ / host-buffer / CLI routes, two samples in flight, the GFF
+typing, the PMC passes of the dominant kernel (child runs of their own) and, at N > 1, the sharded
+CLI end to end; `--cpu-baseline 0`, `--pmc 0` and the like leave single legs out of a full run.
+
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed inside the timed
-region) and, at N = 1, `cpu_baseline` (the oracle on a bounded sample of the same workload).  The
-line holds the headline fields only (LINE_KEYS); the whole record, every secondary leg and note
-included, goes to `--details FILE` (default bench_details.json in the working directory).
+region) and, with `--full` at N = 1, `cpu_baseline` (the oracle on a bounded sample of the same
+workload).  The line holds the headline fields only (LINE_KEYS); the whole record, every secondary
+leg and note included, goes to `--details FILE` (default bench_details.json in the working directory).
 
 `--steps K` is the number of timed steps (`--min-seconds S` > 0 repeats the region of K steps until
 S seconds of timed work).  `--dump-outputs DIR` writes what the last timed step computed as
@@ -200,7 +206,8 @@ def pmc_traffic(args, rec_name):
     """HBM bytes per launch of one kernel from the PMC counters, as MI355X_MICROARCH.md prescribes:
     FETCH_SIZE and WRITE_SIZE in SEPARATE --pmc passes (no trace domains), kB units, and the gfx950
     correction (FETCH_SIZE counts 128-B requests as 64 B -> x2); a third pass counts SQ_INSTS_VALU (wave-level vector
-    instructions) for the secondary, VALU-issue bound of SURVEY 8(d).  Child processes; None on any failure."""
+    instructions) for the secondary, VALU-issue bound of SURVEY 8(d).  Plain child runs (no --full: no legs, no nested
+    passes); None on any failure."""
     import csv
     import glob
     import shutil
@@ -218,8 +225,7 @@ def pmc_traffic(args, rec_name):
         d = tempfile.mkdtemp(prefix="mirge_pmc_", dir="/tmp")
         # rocprofv3 is a python script: run it with this interpreter (no '#!/usr/bin/env' hop)
         cmd = [sys.executable, rocprof, "--pmc", ctr, "--output-format", "csv", "-d", d, "--", sys.executable,
-               os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-baseline", "0", "--pmc", "0",
-               "--min-seconds", "0", "--spinup", "0", "--cli-path", "0", "--two-in-flight", "0", "--read-sets", "0", "--details", "",
+               os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--min-seconds", "0", "--spinup", "0", "--details", "",
                "--reads", str(args.reads), "--scale", args.scale, "--workload", args.workload, "--pool", str(args.pool)]
         try:
             subprocess.run(cmd, timeout=900, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"),
@@ -914,25 +920,29 @@ def main():
     ap.add_argument("--reads", type=int, default=None, help="raw reads per sample (default 10 M; 20 M for c4)")
     ap.add_argument("--scale", default="full", choices=["ci", "small", "full"])
     ap.add_argument("--two-calls", type=int, default=0, help="1: mirge_collapse then mirge_cascade_run instead of the one-call path")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every secondary leg (the flags below leave single legs out); a plain run "
+                         "does setup, warm-up, the timed steps, --dump-outputs and the line")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full, rank 0, N=1: the CPU baseline on a bounded sample of the workload and its parity check")
     ap.add_argument("--cpu-sample", type=int, default=10_000_000)
     ap.add_argument("--long-frac", dest="long_frac", type=float, default=None,
                     help="share of the sample drawn as 32-50-nt reads (synth default 0.05); a side measurement, labelled in config.workload")
     ap.add_argument("--pool", type=int, default=0,
                     help="draw the reads from this many templates with Zipf weights (SURVEY 8d 'realistic' U/N); 0 = independent draws")
-    ap.add_argument("--cli-path", type=int, default=1, help="rank 0, N=1: also time the CLI's route from a FASTQ file on disk to all CSVs")
+    ap.add_argument("--cli-path", type=int, default=1, help="with --full, rank 0, N=1: time the CLI's route from a FASTQ file on disk to all CSVs")
     ap.add_argument("--min-seconds", dest="min_seconds", type=float, default=0.0,
                     help="repeat the timed region of --steps steps until this much timed work has been seen (0, the default: one "
                          "region, exactly --steps timed steps)")
     ap.add_argument("--spinup", type=float, default=0.3, help="seconds of untimed steps before the timed region (clock state)")
     ap.add_argument("--two-in-flight", dest="two_in_flight", type=int, default=1,
-                    help="rank 0, N=1: also measure the step with TWO samples in flight on two contexts (never `value`)")
+                    help="with --full, rank 0, N=1: measure the step with TWO samples in flight on two contexts (never `value`)")
     ap.add_argument("--read-sets", dest="read_sets", type=int, default=1,
-                    help="rank 0, N=1, c3: also step SURVEY 8(d)'s Zipf-pool (U/N ~ 5 %%) and all-distinct (U = N) read sets (never `value`)")
+                    help="with --full, rank 0, N=1, c3: step SURVEY 8(d)'s Zipf-pool (U/N ~ 5 %%) and all-distinct (U = N) read sets (never `value`)")
     ap.add_argument("--c4-end-to-end", dest="c4_e2e", type=int, default=1,
-                    help="N > 1: also time the sharded CLI's whole route, FASTQ files -> all output files, tail included (never `value`)")
+                    help="with --full, N > 1: time the sharded CLI's whole route, FASTQ files -> all output files, tail included (never `value`)")
     ap.add_argument("--pmc", type=int, default=1,
-                    help="rank 0, N=1: measure the dominant kernel's HBM traffic with two child rocprofv3 --pmc passes")
+                    help="with --full, rank 0, N=1: measure the dominant kernel's HBM traffic with child rocprofv3 --pmc passes")
     ap.add_argument("--details", default="bench_details.json",
                     help="rank 0: write the whole record (secondary legs and notes included) to this JSON file ('' = none)")
     ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
@@ -1251,13 +1261,13 @@ def main():
     # ---------------- SURVEY 8(d)'s two read sets beside the default draw (never `value`): Zipf duplication over a template pool
     # (U/N of a few percent, the "realistic" set) and all-distinct reads (U = N, "stress").  The default sample -- every read
     # drawn independently, U/N = 0.42 -- is neither; `value` swings 2 x between the two, so the line carries all three.
-    if rank == 0 and n_gpus == 1 and args.read_sets and args.workload == "c3" and not args.pool:
+    if args.full and rank == 0 and n_gpus == 1 and args.read_sets and args.workload == "c3" and not args.pool:
         try:
             out["read_sets"] = secondary_read_sets(args, sl, ctx, casc, _ffi, synth, n_mirna, EXACT_PASS, ISO_PASS, out)
         except Exception as e:  # noqa: BLE001
             out["read_sets"] = {"error": repr(e)[:300]}
 
-    if rank == 0 and n_gpus == 1 and args.read_sets and args.workload == "c3" and not args.pool:
+    if args.full and rank == 0 and n_gpus == 1 and args.read_sets and args.workload == "c3" and not args.pool:
         try:
             out.setdefault("read_sets", {})["repeat_rich"] = repeat_rich_leg(args, ctx, _ffi, synth, Cascade, PASSES, n_mirna, EXACT_PASS, ISO_PASS,
                                                                               out["ms_per_step"])
@@ -1266,7 +1276,7 @@ def main():
 
     # ---------------- the same from the FILE's text (never `value`): FASTQ bytes in host memory -> records parsed,
     # filtered, packed on the GPU -> collapse -> cascade -> count tables on the host
-    if rank == 0 and n_gpus == 1 and len(reads) <= 20_000_000:  # the text is built with numpy: ~0.5 KB of host memory per read
+    if args.full and rank == 0 and n_gpus == 1 and len(reads) <= 20_000_000:  # the text is built with numpy: ~0.5 KB of host memory per read
         text = fastq_text(reads)
         best_dt = None
         for _ in range(3):
@@ -1350,7 +1360,7 @@ def main():
         del text
 
     # ---------------- BASELINE configs[3] end to end (never `value`): all ranks, N > 1 -- the product's route with its tail
-    if dist is not None and world > 1 and args.c4_e2e and args.workload in ("c3", "c4") and not args.pool:
+    if args.full and dist is not None and world > 1 and args.c4_e2e and args.workload in ("c3", "c4") and not args.pool:
         try:
             e2e = c4_end_to_end(args, dist, rank, world, sl, casc, reads, n_pass)
             if rank == 0 and e2e is not None:
@@ -1362,7 +1372,7 @@ def main():
     # ---------------- two samples in flight (never `value`): what a batch of samples per GPU runs at -- a second context (its own
     # streams, its own copy of the libraries) steps a second sample from a second host thread; the collapse of one sample (LDS-
     # and write-bound) overlaps the cascade of the other (bound by L1 misses in flight)
-    if rank == 0 and n_gpus == 1 and args.two_in_flight and args.workload in ("c3", "c4") and not args.pool:
+    if args.full and rank == 0 and n_gpus == 1 and args.two_in_flight and args.workload in ("c3", "c4") and not args.pool:
         try:
             import threading
             ctx2 = _ffi.Context(dev_index)
@@ -1401,7 +1411,7 @@ def main():
     # ---------------- SURVEY 8(d)'s "collapsed reads/s" to the letter (never `value`): U device-resident packed unique reads ->
     # cascade -> count join -> per-read annotation (pass, reference, offset, mismatches: 10 B per read) AND the count tables back
     # on the host.  `collapsed_reads_per_s_M` above divides U by the whole step (collapse included, no per-read fetch).
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             u_c = raw.collapse()
             best_dt = None
@@ -1427,7 +1437,7 @@ def main():
     # ---------------- SURVEY 8(f) row N2 (never `value`): the isomiR typing of the miRTop GFF3 on the sample's miRNA reads --
     # every read of the exact-miRNA and isomiR passes through k_isotype (the reference's per-read difflib diff + list rewriting,
     # summary.py:204-470), records back on the host; the kernel's own time from its HIP-event bracket
-    if rank == 0 and n_gpus == 1 and args.workload in ("c3", "c5") and n_pass > ISO_PASS and hasattr(sl, "mir_hairpin"):
+    if args.full and rank == 0 and n_gpus == 1 and args.workload in ("c3", "c5") and n_pass > ISO_PASS and hasattr(sl, "mir_hairpin"):
         try:
             from mirge3_amd import gff
             mir, hp = sl.libs["mirna"], sl.libs["hairpin"]
@@ -1487,7 +1497,7 @@ def main():
             out["gff_typing"] = {"error": repr(e)[:300]}
 
     # ---------------- PCIe-inclusive rate (never `value`): host ASCII reads in, per-read annotation + counts out
-    if rank == 0:
+    if args.full and rank == 0:
         best_dt = None
         for _ in range(3):  # best of three: the first pass also pays for new buffer-pool blocks
             t = time.perf_counter()
@@ -1510,13 +1520,13 @@ def main():
                      "bwtAlign/summarize wrote around that oracle; the bowtie predicate itself is UNPINNED (no bowtie 1.x "
                      "in the image or on the pool): 'bit-exact vs ref' in `metric` is BASELINE.json's wording, not a claim")
     bowtie_dir = reference_bowtie_dir()
-    if rank == 0 and n_gpus == 1 and args.cpu_baseline and bowtie_dir:
+    if args.full and rank == 0 and n_gpus == 1 and args.cpu_baseline and bowtie_dir:
         try:
             out["cpu_baseline"] = reference_bowtie_baseline(bowtie_dir, sl, libs, reads, n_pass, ctx, casc, args)
             out["parity"] = out["cpu_baseline"].pop("parity")
         except Exception as e:  # a broken bowtie install must not take the bench line down
             out["cpu_baseline_reference_error"] = repr(e)[:300]
-    if rank == 0 and n_gpus == 1 and args.cpu_baseline and "cpu_baseline" not in out:
+    if args.full and rank == 0 and n_gpus == 1 and args.cpu_baseline and "cpu_baseline" not in out:
         import oracle
         cores = os.cpu_count() or 1
         threads = min(cores, 64)
@@ -1552,7 +1562,7 @@ def main():
         out["parity_on_cpu_sample"] = bool(np.array_equal(cls_g[:, 0], cls_o)) and len(u_g) == len(u2)
         res.close(); u_g.close(); r2.close()
 
-    if rank == 0 and n_gpus == 1 and args.pmc:
+    if args.full and rank == 0 and n_gpus == 1 and args.pmc:
         t = pmc_traffic(args, dom)
         if t is not None:
             algo_launch = algo_bytes(dom) * kd["units_per_launch"]

@@ -827,7 +827,7 @@ def test_bench_two_ranks_share_the_gpu(tmp_path):
     env = dict(os.environ, MIRGE_BENCH_SHARE_GPU="1", MIRGE_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--reads", "300000", "--scale", "ci", "--cpu-baseline", "0", "--pmc", "0", "--min-seconds", "0.5",
+           "--warmup", "1", "--reads", "300000", "--scale", "ci", "--full", "--cpu-baseline", "0", "--pmc", "0", "--min-seconds", "0.5",
            "--details", str(tmp_path / "details.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -889,7 +889,7 @@ def test_bench_barrier_over_rccl_with_one_rank(tmp_path):
 
 
 def test_bench_single_gpu_line(tmp_path):
-    """bench.py at N = 1 on a small configuration: the ONE JSON line with the contract's fields, the oracle-checked
+    """bench.py --full at N = 1 on a small configuration: the ONE JSON line with the contract's fields, the oracle-checked
     sample, the roofline object of the dominant kernel and the two host-inclusive paths."""
     import json
     import subprocess
@@ -897,7 +897,7 @@ def test_bench_single_gpu_line(tmp_path):
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     details, dump = str(tmp_path / "details.json"), str(tmp_path / "outputs")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--reads", "400000", "--scale", "ci",
-           "--pmc", "0", "--min-seconds", "0.5", "--details", details, "--dump-outputs", dump]
+           "--full", "--pmc", "0", "--min-seconds", "0.5", "--details", details, "--dump-outputs", dump]
     r = subprocess.run(cmd, env=dict(os.environ, OMP_NUM_THREADS="8"), capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -958,6 +958,44 @@ def test_bench_single_gpu_line(tmp_path):
     assert rs["default_draw"]["ms_per_step"] == d["ms_per_step"] and rs["distinct"]["U_over_N"] == 1.0
     assert rs["zipf_pool"]["U_over_N"] < rs["default_draw"]["U_over_N"] < 1.0 and rs["zipf_pool"]["raw_reads"] == N
     assert d["cascade_walks"]["passes"] == 7 and d["cascade_walks"]["walks"] in (5, 7) and d["cascade_walks"]["exact_lookup_passes"] in (0, 2)
+
+
+def test_bench_plain_run(tmp_path):
+    """bench.py without --full: setup, warm-up, exactly --steps timed steps, the dump and the line with the same headline
+    fields as a full run -- and none of the secondary legs (CPU baseline, read sets, host and CLI routes, GFF typing, PMC)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    details, dump = str(tmp_path / "details.json"), str(tmp_path / "outputs")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--reads", "400000", "--scale", "ci",
+           "--details", details, "--dump-outputs", dump]
+    r = subprocess.run(cmd, env=dict(os.environ, OMP_NUM_THREADS="8"), capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline",
+              "kernels", "timing"):
+        assert k in line, k
+    assert line["unit"] == "M reads/s" and line["higher_is_better"] is True and line["dtype"] == "u64" and line["value"] > 0
+    tm = line["timing"]
+    assert line["steps"] == 3 and tm["timed_steps"] == 3 and tm["regions"] == 1
+    assert abs(line["ms_per_step"] - tm["timed_seconds"] / 3 * 1e3) <= 0.05 / 3 + 1e-4  # timed_seconds is rounded to 0.1 ms
+    assert abs(line["value"] - 0.4 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    with open(details) as fh:
+        d = json.load(fh)
+    assert all(d[k] == v for k, v in line.items())
+    moved = {"cpu_baseline", "parity_on_cpu_sample", "read_sets", "raw_reads_per_s_fastq_in_M", "fastq_text_path", "fastq_trim_path",
+             "cli_path", "two_samples_in_flight", "collapsed_reads_annotation_on_host", "gff_typing", "host_buffer_path"}
+    assert not moved & set(d), moved & set(d)
+    assert d["roofline"]["traffic"] is None and "traffic_detail" not in d["roofline"]
+    o = {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+    assert line["outputs"]["bytes"] == sum(a.nbytes for a in o.values())
+    assert o["unique_reads"][0] == d["config"]["unique_reads_per_gpu"] == o["read_count"].shape[0]
+    assert o["read_count"].sum() == 400000
+    for p in range(9):
+        assert o["read_count"][o["read_pass"] == p].sum() == o["class_counts"][p, 0], p
 
 
 def test_variant_tally_vs_oracle(ctx):
