@@ -381,6 +381,31 @@ void mirge_genome_destroy(mirge_genome* genome);
 int mirge_genome_align_counts(mirge_ctx* ctx, const mirge_genome* genome, const char* queries, const int64_t* offsets, int64_t n,
                               int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, uint32_t* out);
 
+/* ---- genome alignments with positions, and their clusters (the front half of -nmir, novel_mir.py:41-150,340-362)
+ * mirge_genome_align_loci  every alignment mirge_genome_align_counts counts, as a record: the same predicate (one verify routine), plus
+ *                          max_loci (bowtie -m: a query with more than max_loci valid alignments reports none; 0 = no cap) and norc
+ *                          (forward strand only).  totals[n] = every query's valid alignments, capped or not.  The records
+ *                          (mirge_loci_count / _fetch) are sorted by (reference, offset, query, strand with '+' = 0 first); offset is
+ *                          0-based inside the reference, ambiguous stretches included (SAM POS - 1).  Queries are scanned in batches
+ *                          of 2^20 against the one resident genome.
+ * mirge_loci_cluster       records sorted by (reference, offset) -> cluster[n] (-1: dropped) and the cluster table (caller's arrays
+ *                          of n entries; *n_clusters filled) in (reference, strand, start) order.  Inside one (reference, strand) a
+ *                          record joins iff offset + max(threshold, 1) <= the largest offset + qlen before it; ref_skip[r] != 0
+ *                          drops reference r; minus_first_only != 0 keeps only the first minus-strand cluster of a reference, as
+ *                          the reference does.  c_start 0-based, c_end exclusive, c_reads = sum of qcount.            */
+typedef struct mirge_loci mirge_loci;
+int mirge_genome_align_loci(mirge_ctx* ctx, const mirge_genome* genome, const char* queries, const int64_t* offsets, int64_t n,
+                            int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, int64_t max_loci,
+                            int32_t norc, uint64_t* totals, mirge_loci** out);
+int64_t mirge_loci_count(const mirge_loci* loci);
+int mirge_loci_fetch(const mirge_loci* loci, uint32_t* query, uint32_t* ref, uint64_t* off, uint8_t* strand, uint8_t* mm);
+void mirge_loci_destroy(mirge_loci* loci);
+int mirge_loci_cluster(mirge_ctx* ctx, int64_t n, const uint32_t* ref, const uint64_t* off, const uint8_t* strand,
+                       const uint32_t* query, int64_t n_queries, const int32_t* qlen, const int64_t* qcount, int64_t n_refs,
+                       const uint8_t* ref_skip, int32_t threshold, int32_t minus_first_only, int32_t* cluster,
+                       int64_t* n_clusters, uint32_t* c_ref, uint8_t* c_strand, uint64_t* c_start, uint64_t* c_end,
+                       int64_t* c_reads, uint32_t* c_members);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

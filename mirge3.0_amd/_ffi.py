@@ -29,6 +29,7 @@ EXPORTS = [
     "mirge_reads_range_sample", "mirge_reads_range_split", "mirge_annotation_csv_device_sizes", "mirge_annotation_csv_device_at",
     "mirge_cascade_prepare", "mirge_cascade_walks", "mirge_cascade_wg_times", "mirge_ctx_profile_only", "mirge_ctx_profile_units", "mirge_ctx_profile_reset", "mirge_ctx_profile_count", "mirge_ctx_profile_get",
     "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
+    "mirge_genome_align_loci", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
 ]
 
 
@@ -110,6 +111,9 @@ def load() -> C.CDLL:
         getattr(lib, name).restype = C.c_int64
     for name in ("mirge_lib_destroy", "mirge_reads_destroy", "mirge_result_destroy", "mirge_ctx_destroy", "mirge_genome_destroy"):
         getattr(lib, name).restype = None
+    if hasattr(lib, "mirge_loci_count"):  # absent from an older A/B build (MIRGE_NATIVE_SO)
+        lib.mirge_loci_count.restype = C.c_int64
+        lib.mirge_loci_destroy.restype = None
     _lib = lib
     return lib
 
@@ -417,6 +421,32 @@ class DeviceGenome:
                                                 C.c_int32(n_mm), C.c_int32(seedlen), C.c_int32(maxtotal), C.c_int32(trim5),
                                                 C.c_int32(trim3), _p(out)), "mirge_genome_align_counts")
         return out[:n]
+
+    def align_loci(self, seqs: FlatSeqs, n_mm: int, seedlen: int = 28, maxtotal: int = 2, trim5: int = 0, trim3: int = 0,
+                   max_loci: int = 0, norc: bool = False) -> dict:
+        """``mirge_genome_align_loci`` -> ``query`` (uint32), ``ref`` (uint32), ``off`` (uint64, 0-based in the reference),
+        ``strand`` (uint8, 1 = '-'), ``mm`` (uint8) per reported alignment in (ref, off, query, strand) order, and ``totals``
+        (uint64 per query: its valid alignments, reported or capped by ``max_loci``)"""
+        lib = load()
+        n = len(seqs)
+        totals = np.zeros(max(n, 1), dtype=np.uint64)
+        data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
+        off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
+        h = C.c_void_p()
+        _check(lib.mirge_genome_align_loci(self.ctx._h, self._h, _p(data) if data.size else C.c_void_p(0), _p(off), C.c_int64(n),
+                                           C.c_int32(n_mm), C.c_int32(seedlen), C.c_int32(maxtotal), C.c_int32(trim5), C.c_int32(trim3),
+                                           C.c_int64(max_loci), C.c_int32(1 if norc else 0), _p(totals), C.byref(h)),
+               "mirge_genome_align_loci")
+        try:
+            m = int(lib.mirge_loci_count(h))
+            out = dict(query=np.zeros(m, np.uint32), ref=np.zeros(m, np.uint32), off=np.zeros(m, np.uint64),
+                       strand=np.zeros(m, np.uint8), mm=np.zeros(m, np.uint8))
+            if m:
+                _check(lib.mirge_loci_fetch(h, *(_p(out[k]) for k in ("query", "ref", "off", "strand", "mm"))), "mirge_loci_fetch")
+        finally:
+            lib.mirge_loci_destroy(h)
+        out["totals"] = totals[:n]
+        return out
 
     def close(self):
         if self._h:
@@ -836,3 +866,26 @@ def annotation_csv_device(ctx: "Context", uniq: "DeviceReads", res: "CascadeResu
         return False
     _check(rc, "mirge_annotation_csv_device")
     return True
+
+
+def loci_cluster(ctx: Context, ref, off, strand, query, qlen, qcount, ref_skip, threshold: int, minus_first_only: bool = True) -> dict:
+    """``mirge_loci_cluster``: records sorted by (ref, off) -> ``cluster`` (int32 per record, -1 = dropped) and the cluster table
+    ``ref``, ``strand``, ``start`` (0-based), ``end`` (exclusive), ``reads``, ``members`` in (ref, strand, start) order"""
+    ref, query = (np.ascontiguousarray(a, dtype=np.uint32) for a in (ref, query))
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    strand, ref_skip = (np.ascontiguousarray(a, dtype=np.uint8) for a in (strand, ref_skip))
+    qlen = np.ascontiguousarray(qlen, dtype=np.int32)
+    qcount = np.ascontiguousarray(qcount, dtype=np.int64)
+    n = ref.shape[0]
+    m = max(n, 1)
+    cluster = np.full(m, -1, dtype=np.int32)
+    tab = dict(ref=np.zeros(m, np.uint32), strand=np.zeros(m, np.uint8), start=np.zeros(m, np.uint64), end=np.zeros(m, np.uint64),
+               reads=np.zeros(m, np.int64), members=np.zeros(m, np.uint32))
+    nc = C.c_int64(0)
+    _check(load().mirge_loci_cluster(ctx._h, C.c_int64(n), _p(ref), _p(off), _p(strand), _p(query), C.c_int64(qlen.shape[0]), _p(qlen),
+                                     _p(qcount), C.c_int64(ref_skip.shape[0]), _p(ref_skip), C.c_int32(threshold),
+                                     C.c_int32(1 if minus_first_only else 0), _p(cluster), C.byref(nc),
+                                     *(_p(tab[k]) for k in ("ref", "strand", "start", "end", "reads", "members"))), "mirge_loci_cluster")
+    out = {k: v[:nc.value] for k, v in tab.items()}
+    out["cluster"] = cluster[:n]
+    return out

@@ -146,6 +146,17 @@ class GpuGenome:
         distinct, c, _ = self.counts(seqs, 0)
         return {q for q, row in zip(distinct, c) if row.any()}
 
+    def loci(self, queries, n_mm: int = 0, seedlen: int = SEEDLEN, maxtotal: int = MAXTOTAL, trim5: int = 0, trim3: int = 0,
+             max_loci: int = 0, norc: bool = False) -> dict:
+        """Where the queries align (``mirge_genome_align_loci``): numpy arrays ``query``, ``ref``, ``off`` (0-based inside the
+        reference = SAM POS - 1), ``strand`` (1 = '-'), ``mm`` per reported alignment, sorted by (ref, off, query, strand), and
+        ``totals`` per query (above ``max_loci``: capped, nothing reported).  ``queries``: strings or a ``FlatSeqs``.  The
+        predicate is ``counts``' own; ``ref_names`` comes along when the genome was loaded by ``load_genome``."""
+        seqs = queries if isinstance(queries, FlatSeqs) else FlatSeqs.from_list(list(queries))
+        out = self.genome.align_loci(seqs, n_mm, seedlen, maxtotal, trim5, trim3, max_loci, norc)
+        out["ref_names"] = getattr(self.genome, "ref_names", None)
+        return out
+
 
 _GENOMES: Dict[tuple, object] = {}  # (context, index base) -> DeviceGenome: loaded on the first -ai sample, kept for the process
 
@@ -160,10 +171,15 @@ def load_genome(ctx, base: str, timings: Optional[dict] = None):
         from .seqio import load_index
         t = time.perf_counter()
         if os.path.exists(str(base) + ".fa"):
-            g = _ffi.DeviceGenome(ctx, seqs=load_index(str(base), use_cache=False).seqs)
+            lib = load_index(str(base), use_cache=False)
+            g = _ffi.DeviceGenome(ctx, seqs=lib.seqs)
+            g.ref_names, g.ref_lens = list(lib.names), [int(x) for x in lib.seqs.lengths]
         elif ebwt.has_index(str(base)):
             packed, off, ln, first = ebwt.read_records(str(base))
             g = _ffi.DeviceGenome(ctx, packed=packed, records=(off, ln, first))
+            g.ref_names = [(h.split() or [""])[0] for h in ebwt.read_names(str(base))]
+            # what the index knows of a reference's length: ambiguous characters at its end are not recorded
+            g.ref_lens = np.bincount(np.cumsum(first.astype(np.int64)) - 1, weights=(off + ln).astype(np.float64)).astype(np.int64).tolist()
         else:
             raise FileNotFoundError(f"-ai: no genome at {base} (.fa or .1/.3/.4.ebwt[l])")
         _GENOMES[key] = g

@@ -85,6 +85,10 @@ def parse_args(argv=None):
                     help="-ai without bowtie: file of the miRNA reads with a unique best genome alignment (one per line)")
     ap.add_argument("--genome-aligned", dest="genome_aligned", default=None,
                     help="-ai without bowtie: file of the edited canonical sequences that align to the genome")
+    ap.add_argument("--unmapped-clusters", dest="unmapped_clusters", action="store_true",
+                    help="map the reads of unmapped.csv to <org>_genome on the device and cluster them by coordinate: "
+                         "unmapped_tmp/*.fa, unmapped_mirna_<sample>_vs_genome_sorted.sam, <sample>_clusters.tsv (the front half of "
+                         "the reference's -nmir).  With it -minl -maxl -c -mloc -sl -olc are read (defaults 16 25 2 3 25 14)")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -129,6 +133,13 @@ def parse_args(argv=None):
     args.bowtieVersion = "True"
     if (args.AtoI or args.gff_out) and (args.save_pkl or args.resume):
         ap.error("-ai / -gff run on the device-resident route: not together with -spl / -rr")
+    if args.unmapped_clusters and (args.save_pkl or args.resume or args.backend == "bowtie"):
+        ap.error("--unmapped-clusters runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+    if args.unmapped_clusters:
+        for k in ("minl", "maxl", "c", "mloc", "sl", "olc"):
+            v = getattr(args, "ignored_" + k)
+            if v is not None and not str(v).lstrip("-").isdigit():
+                ap.error(f"-{k} takes an integer")
     if args.genome_filter == "gpu" and args.genome_retained:
         ap.error("--genome-filter gpu computes what --genome-retained lists: give one of them")
     if args.backend == "bowtie" and (args.AtoI or args.gff_out or args.isoform_entropy):

@@ -28,6 +28,7 @@ struct GenomeQueryArgs {
     const int64_t* off;
     uint32_t n;
     int32_t n_mm, seedlen, trim5, trim3, kmax;
+    int32_t norc;  // forward strand only: the '-' entries stay empty (len 0, no key)
 };
 
 #define MIRGE_GENOME_NOKEY 0xFFFFFFFFFFFFFFFFull
@@ -63,7 +64,7 @@ __global__ void k_genome_queries(GenomeQueryArgs a, GenomeQS* __restrict__ qs, u
             keys[(size_t)slot * P + j] = MIRGE_GENOME_NOKEY;
             vals[(size_t)slot * P + j] = slot * 4u + j;
         }
-        if (L >= 1 && L > a.n_mm && L <= MIRGE_GENOME_MAXLEN) {
+        if (L >= 1 && L > a.n_mm && L <= MIRGE_GENOME_MAXLEN && !(s == 1 && a.norc)) {
             for (int t = 0; t < L; t++) {
                 const char ch = a.ascii[b + a.trim5 + (s == 0 ? t : L - 1 - t)];
                 int c = -1;
@@ -129,7 +130,17 @@ struct GenomeScanArgs {
     int32_t tab_k[MIRGE_GENOME_MAXK];
     uint64_t tab_bm[MIRGE_GENOME_MAXK];
     uint32_t tab_b[MIRGE_GENOME_MAXK], tab_e[MIRGE_GENOME_MAXK];
+    // the fill pass (k_genome_scan<true>, mirge_genome_align_loci): query q's records go to [range[q], range[q + 1]) -- empty for
+    // a query that reports nothing -- at the place its cursor hands out
+    const uint64_t* range;       // [n queries + 1]
+    uint32_t* cursor;            // [n queries], zeroed
+    uint64_t* rec_pos;           // stream position of the window's first base
+    uint32_t* rec_meta;          // (query_base + query) << 3 | strand << 2 | mismatches
+    uint32_t* overflow;          // set when a cursor leaves its range (the two passes disagree: a bug, reported by the host)
+    uint32_t query_base;
 };
+
+#define MIRGE_GENOME_STASH 4  // hits a lane keeps per trip for the wave's merged flush (more go out one atomic each)
 
 __device__ __forceinline__ void genome_window(const uint64_t* __restrict__ text, uint64_t ws, uint64_t& w0, uint64_t& w1) {
     const uint64_t i = ws >> 5;
@@ -146,7 +157,13 @@ __device__ __forceinline__ void genome_window(const uint64_t* __restrict__ text,
 // set bit is looked up in the sorted keys, and every (query, strand, piece) under it is verified in full.  An alignment is
 // counted by its OWNER only -- the first piece of its (query, strand) that is exact in the window -- so that it is counted
 // once however many of its pieces are exact.
+// FILL: the same scan writes every alignment it would count as a record.  A lane keeps its trip's hits in LDS; at the end of the
+// trip the wave hands them out query by query: one atomic on the query's cursor per distinct query of the wave, every lane
+// taking its rank under it (a query planted 10^5 times costs one atomic per wave and trip, as in the count pass).
+template <bool FILL>
 __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
+    __shared__ uint64_t st_pos[FILL ? 256 * MIRGE_GENOME_STASH : 1];
+    __shared__ uint32_t st_meta[FILL ? 256 * MIRGE_GENOME_STASH : 1];
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t n_strips = (a.n_bases + MIRGE_GENOME_STRIP - 1) / MIRGE_GENOME_STRIP;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -155,6 +172,7 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
         const uint64_t strip = w0s + lane;
         uint32_t acc_key = 0xFFFFFFFFu;
         unsigned long long acc_n = 0;
+        int n_st = 0;
         if (strip < n_strips) {
             const uint64_t wa = a.text[strip], wb = a.text[strip + 1];
             for (int i = 0; i < MIRGE_GENOME_STRIP; i++) {
@@ -204,6 +222,21 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
                             if (!((d0 & genome_range_mask(plo, phi)) | (d1 & genome_range_mask(plo - 32, phi - 32)))) owner = q;
                         }
                         if (owner != (int)piece) continue;
+                        if constexpr (FILL) {
+                            const uint64_t rs = a.range[g.query], len = a.range[g.query + 1] - rs;
+                            if (!len) continue;  // capped by max_loci
+                            const uint32_t meta = ((a.query_base + g.query) << 3) | (((v >> 2) & 1u) << 2) | (uint32_t)tot;
+                            if (n_st < MIRGE_GENOME_STASH) {
+                                st_pos[n_st * 256 + threadIdx.x] = ws;
+                                st_meta[n_st * 256 + threadIdx.x] = meta;
+                                n_st++;
+                            } else {
+                                const uint32_t idx = atomicAdd(&a.cursor[g.query], 1u);
+                                if (idx < len) { a.rec_pos[rs + idx] = ws; a.rec_meta[rs + idx] = meta; }
+                                else atomicOr(a.overflow, 1u);
+                            }
+                            continue;
+                        }
                         const uint32_t hk = g.query * 3u + (uint32_t)tot;
                         if (acc_n && hk != acc_key) atomicAdd(&a.counts[acc_key], acc_n);
                         if (hk != acc_key) { acc_key = hk; acc_n = 0; }
@@ -211,6 +244,34 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
                     }
                 }
             }
+        }
+        if constexpr (FILL) {
+            for (int e = 0; e < MIRGE_GENOME_STASH; e++) {
+                bool pending = e < n_st;
+                unsigned long long m = __ballot(pending);
+                if (!m) break;
+                const uint64_t pos = pending ? st_pos[e * 256 + threadIdx.x] : 0ull;
+                const uint32_t meta = pending ? st_meta[e * 256 + threadIdx.x] : 0u;
+                const uint32_t ql = (meta >> 3) - a.query_base;
+                while (m) {
+                    const int leader = __ffsll((long long)m) - 1;
+                    const uint32_t lq = (uint32_t)__shfl((int)ql, leader, 64);
+                    const bool same = pending && ql == lq;
+                    const unsigned long long sm = __ballot(same);
+                    uint32_t base = 0;
+                    if ((int)lane == leader) base = atomicAdd(&a.cursor[lq], (uint32_t)__popcll(sm));
+                    base = (uint32_t)__shfl((int)base, leader, 64);
+                    if (same) {
+                        const uint32_t idx = base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
+                        const uint64_t rs = a.range[lq], len = a.range[lq + 1] - rs;
+                        if (idx < len) { a.rec_pos[rs + idx] = pos; a.rec_meta[rs + idx] = meta; }
+                        else atomicOr(a.overflow, 1u);
+                        pending = false;
+                    }
+                    m = __ballot(pending);
+                }
+            }
+            continue;
         }
         // wave-level merge of the lanes' pending counts: one atomic per distinct (query, mismatches) of the wave
         bool pending = acc_n != 0;
@@ -230,4 +291,120 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
             m = __ballot(pending);
         }
     }
+}
+
+// ---- loci: a record's stream position -> (reference, offset inside it as bowtie counts it, ambiguous stretches included)
+__global__ void k_genome_loci_finish(uint32_t n, const uint64_t* __restrict__ pos, const uint32_t* __restrict__ meta,
+                                     const uint64_t* __restrict__ s_start, uint32_t n_str, const uint32_t* __restrict__ str_ref,
+                                     const uint64_t* __restrict__ str_off, uint32_t* __restrict__ query, uint32_t* __restrict__ ref,
+                                     uint64_t* __restrict__ off, uint8_t* __restrict__ strand, uint8_t* __restrict__ mm) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t p = pos[i];
+    uint32_t l = 0, h = n_str;  // largest s with s_start[s] <= p
+    while (h - l > 1) {
+        const uint32_t m = (l + h) >> 1;
+        if (s_start[m] <= p) l = m; else h = m;
+    }
+    const uint32_t v = meta[i];
+    query[i] = v >> 3;
+    ref[i] = str_ref[l];
+    off[i] = str_off[l] + (p - s_start[l]);
+    strand[i] = (uint8_t)((v >> 2) & 1u);
+    mm[i] = (uint8_t)(v & 3u);
+}
+
+// ---- clustering of coordinate-sorted records (novel_mir.py:98-132 as a segmented running maximum)
+struct ClusterItem {  // the scan's element over the records in (reference, strand, input order)
+    uint64_t seg;     // reference << 1 | strand
+    int64_t maxend;   // max over the segment so far of offset + length (0-based exclusive = the reference's 1-based endPos)
+    uint32_t first;   // where the segment starts
+    uint32_t pad;
+};
+
+struct ClusterScanOp {
+    __host__ __device__ ClusterItem operator()(const ClusterItem& a, const ClusterItem& b) const {
+        if (a.seg != b.seg) return b;
+        ClusterItem r = b;
+        r.maxend = a.maxend > b.maxend ? a.maxend : b.maxend;
+        r.first = a.first;
+        return r;
+    }
+};
+
+__global__ void k_cluster_keys(uint32_t n, const uint32_t* __restrict__ ref, const uint8_t* __restrict__ strand,
+                               uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = ((uint64_t)ref[i] << 1) | (strand[i] & 1u);
+    vals[i] = i;
+}
+
+__global__ void k_cluster_items(uint32_t n, const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ perm,
+                                const uint64_t* __restrict__ off, const uint32_t* __restrict__ query, const int32_t* __restrict__ qlen,
+                                ClusterItem* __restrict__ items) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = perm[j];
+    ClusterItem it;
+    it.seg = skeys[j];
+    it.maxend = (int64_t)off[i] + qlen[query[i]];
+    it.first = j;
+    it.pad = 0;
+    items[j] = it;
+}
+
+// flag[j] = 1: record j (sorted order) does not join what is before it in its segment.  It joins iff
+// startPos <= E and E - startPos + 1 >= threshold with E the running maximum of endPos, i.e. offset + max(threshold, 1) <= E.
+__global__ void k_cluster_flags(uint32_t n, const ClusterItem* __restrict__ scanned, const uint32_t* __restrict__ perm,
+                                const uint64_t* __restrict__ off, int32_t threshold, uint32_t* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    uint32_t f = 1;
+    if (scanned[j].first != j) {
+        const int64_t need = (int64_t)off[perm[j]] + (threshold > 1 ? threshold : 1);
+        f = need <= scanned[j - 1].maxend ? 0u : 1u;
+    }
+    flag[j] = f;
+}
+
+// kept[j] = 1: record j starts a cluster that is written.  first_only (the reference's minus strand): a segment on
+// the minus strand keeps its first cluster only; a record after that cluster's end is dropped.  skip[ref]: the reference's name
+// holds no 'chr'.
+__global__ void k_cluster_kept(uint32_t n, const ClusterItem* __restrict__ scanned, const uint32_t* __restrict__ flag,
+                               const uint32_t* __restrict__ fsum, const uint8_t* __restrict__ skip, int32_t minus_first_only,
+                               uint32_t* __restrict__ kept, uint8_t* __restrict__ dropped) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const ClusterItem it = scanned[j];
+    const bool minus = it.seg & 1u;
+    const uint32_t ordinal = fsum[j] - fsum[it.first];  // clusters opened in the segment before this record's
+    const bool drop = skip[it.seg >> 1] || (minus && minus_first_only && ordinal > 0);
+    dropped[j] = drop ? 1 : 0;
+    kept[j] = (!drop && flag[j]) ? 1u : 0u;
+}
+
+struct ClusterTable {
+    uint32_t* ref; uint8_t* strand; uint64_t* start; unsigned long long* end; unsigned long long* reads; uint32_t* members;
+};
+
+__global__ void k_cluster_assign(uint32_t n, const ClusterItem* __restrict__ scanned, const uint32_t* __restrict__ perm,
+                                 const uint32_t* __restrict__ kept, const uint32_t* __restrict__ ksum, const uint8_t* __restrict__ dropped,
+                                 const uint64_t* __restrict__ off, const uint32_t* __restrict__ query, const int32_t* __restrict__ qlen,
+                                 const int64_t* __restrict__ qcount, int32_t* __restrict__ cluster, ClusterTable t) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = perm[j];
+    if (dropped[j]) { cluster[i] = -1; return; }
+    const uint32_t c = ksum[j] - 1;
+    cluster[i] = (int32_t)c;
+    const uint32_t q = query[i];
+    if (kept[j]) {
+        t.ref[c] = (uint32_t)(scanned[j].seg >> 1);
+        t.strand[c] = (uint8_t)(scanned[j].seg & 1u);
+        t.start[c] = off[i];
+    }
+    atomicMax(&t.end[c], (unsigned long long)(off[i] + (uint64_t)qlen[q]));
+    atomicAdd(&t.reads[c], (unsigned long long)qcount[q]);
+    atomicAdd(&t.members[c], 1u);
 }

@@ -300,6 +300,13 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
         with open(workDir / "run.log", "a+") as fh:
             fh.write(f"A-to-I genome filter: {route}" + (f" ({genome_base(args)}, loaded in {tm.get('genome_load_s', 0.0):.3f} s)"
                                                         if route == "gpu" else "") + f", {genome.seconds:.3f} s\n")
+    if getattr(args, "unmapped_clusters", False):  # the front half of -nmir (novel_mir.py:41-150,340-362) from unmapped.csv
+        from . import unmapped as _unmapped
+        from .a2i import GpuGenome, genome_base, load_genome
+        tm_g = {}
+        g = GpuGenome(ctx, load_genome(ctx, str(genome_base(args)), tm_g))  # the genome -ai loaded, when it ran on the device
+        tm.setdefault("genome_load_s", tm_g.get("genome_load_s", 0.0))
+        out["unmapped_clusters"] = _unmapped.run(args, ctx, workDir, base_names, g, tm)
     if getattr(args, "isoform_entropy", False):  # -ie reads the miRNA rows of the mapped frame: build just those
         from .countjoin import isomir_entropy_tables
         isomir_entropy_tables(mirna_frame(seqs, ps, ref, counts, order, casc, base_names), base_names, out["filtered"], workDir)
@@ -381,7 +388,7 @@ def parallel_tail_eligible(args, n_samples: int, world: int, casc) -> bool:
         return False
     if world < 2 or n_samples < 2 or getattr(args, "host_csv", False):
         return False
-    if any(getattr(args, k, False) for k in ("gff_out", "AtoI", "isoform_entropy")):
+    if any(getattr(args, k, False) for k in ("gff_out", "AtoI", "isoform_entropy", "unmapped_clusters")):
         return False
     return not names_need_quoting(casc)
 
