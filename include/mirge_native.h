@@ -388,6 +388,11 @@ int mirge_genome_align_counts(mirge_ctx* ctx, const mirge_genome* genome, const 
  *                          (mirge_loci_count / _fetch) are sorted by (reference, offset, query, strand with '+' = 0 first); offset is
  *                          0-based inside the reference, ambiguous stretches included (SAM POS - 1).  Queries are scanned in batches
  *                          of 2^20 against the one resident genome.
+ * mirge_genome_align_loci_strata  the same with strata != 0: only the alignments of each query's best stratum (bowtie --best --strata
+ *                          -a).  A stratum is the number of mismatches in the SEED (bowtie manual, -n mode), not in the whole read;
+ *                          max_loci then counts the best stratum only (-m with --strata), totals[] stays every valid alignment and a
+ *                          record's mm stays its total mismatch count.  strata = 0 is mirge_genome_align_loci.  Restated from the
+ *                          manual, unpinned like the predicate.
  * mirge_loci_cluster       records sorted by (reference, offset) -> cluster[n] (-1: dropped) and the cluster table (caller's arrays
  *                          of n entries; *n_clusters filled) in (reference, strand, start) order.  Inside one (reference, strand) a
  *                          record joins iff offset + max(threshold, 1) <= the largest offset + qlen before it; ref_skip[r] != 0
@@ -397,6 +402,9 @@ typedef struct mirge_loci mirge_loci;
 int mirge_genome_align_loci(mirge_ctx* ctx, const mirge_genome* genome, const char* queries, const int64_t* offsets, int64_t n,
                             int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, int64_t max_loci,
                             int32_t norc, uint64_t* totals, mirge_loci** out);
+int mirge_genome_align_loci_strata(mirge_ctx* ctx, const mirge_genome* genome, const char* queries, const int64_t* offsets, int64_t n,
+                                   int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, int64_t max_loci,
+                                   int32_t norc, int32_t strata, uint64_t* totals, mirge_loci** out);
 int64_t mirge_loci_count(const mirge_loci* loci);
 int mirge_loci_fetch(const mirge_loci* loci, uint32_t* query, uint32_t* ref, uint64_t* off, uint8_t* strand, uint8_t* mm);
 void mirge_loci_destroy(mirge_loci* loci);

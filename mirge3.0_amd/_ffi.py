@@ -29,7 +29,7 @@ EXPORTS = [
     "mirge_reads_range_sample", "mirge_reads_range_split", "mirge_annotation_csv_device_sizes", "mirge_annotation_csv_device_at",
     "mirge_cascade_prepare", "mirge_cascade_walks", "mirge_cascade_wg_times", "mirge_ctx_profile_only", "mirge_ctx_profile_units", "mirge_ctx_profile_reset", "mirge_ctx_profile_count", "mirge_ctx_profile_get",
     "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
-    "mirge_genome_align_loci", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
+    "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
 ]
 
 
@@ -423,20 +423,24 @@ class DeviceGenome:
         return out[:n]
 
     def align_loci(self, seqs: FlatSeqs, n_mm: int, seedlen: int = 28, maxtotal: int = 2, trim5: int = 0, trim3: int = 0,
-                   max_loci: int = 0, norc: bool = False) -> dict:
+                   max_loci: int = 0, norc: bool = False, strata: bool = False) -> dict:
         """``mirge_genome_align_loci`` -> ``query`` (uint32), ``ref`` (uint32), ``off`` (uint64, 0-based in the reference),
         ``strand`` (uint8, 1 = '-'), ``mm`` (uint8) per reported alignment in (ref, off, query, strand) order, and ``totals``
-        (uint64 per query: its valid alignments, reported or capped by ``max_loci``)"""
+        (uint64 per query: its valid alignments, reported or capped by ``max_loci``).  ``strata``
+        (``mirge_genome_align_loci_strata``): only each query's best stratum -- fewest seed mismatches -- is reported, and
+        ``max_loci`` counts that stratum"""
         lib = load()
         n = len(seqs)
         totals = np.zeros(max(n, 1), dtype=np.uint64)
         data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
         off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
         h = C.c_void_p()
-        _check(lib.mirge_genome_align_loci(self.ctx._h, self._h, _p(data) if data.size else C.c_void_p(0), _p(off), C.c_int64(n),
-                                           C.c_int32(n_mm), C.c_int32(seedlen), C.c_int32(maxtotal), C.c_int32(trim5), C.c_int32(trim3),
-                                           C.c_int64(max_loci), C.c_int32(1 if norc else 0), _p(totals), C.byref(h)),
-               "mirge_genome_align_loci")
+        head = (self.ctx._h, self._h, _p(data) if data.size else C.c_void_p(0), _p(off), C.c_int64(n), C.c_int32(n_mm), C.c_int32(seedlen),
+                C.c_int32(maxtotal), C.c_int32(trim5), C.c_int32(trim3), C.c_int64(max_loci), C.c_int32(1 if norc else 0))
+        if strata:
+            _check(lib.mirge_genome_align_loci_strata(*head, C.c_int32(1), _p(totals), C.byref(h)), "mirge_genome_align_loci_strata")
+        else:
+            _check(lib.mirge_genome_align_loci(*head, _p(totals), C.byref(h)), "mirge_genome_align_loci")
         try:
             m = int(lib.mirge_loci_count(h))
             out = dict(query=np.zeros(m, np.uint32), ref=np.zeros(m, np.uint32), off=np.zeros(m, np.uint64),

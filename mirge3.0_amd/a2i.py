@@ -147,13 +147,14 @@ class GpuGenome:
         return {q for q, row in zip(distinct, c) if row.any()}
 
     def loci(self, queries, n_mm: int = 0, seedlen: int = SEEDLEN, maxtotal: int = MAXTOTAL, trim5: int = 0, trim3: int = 0,
-             max_loci: int = 0, norc: bool = False) -> dict:
+             max_loci: int = 0, norc: bool = False, strata: bool = False) -> dict:
         """Where the queries align (``mirge_genome_align_loci``): numpy arrays ``query``, ``ref``, ``off`` (0-based inside the
         reference = SAM POS - 1), ``strand`` (1 = '-'), ``mm`` per reported alignment, sorted by (ref, off, query, strand), and
-        ``totals`` per query (above ``max_loci``: capped, nothing reported).  ``queries``: strings or a ``FlatSeqs``.  The
-        predicate is ``counts``' own; ``ref_names`` comes along when the genome was loaded by ``load_genome``."""
+        ``totals`` per query (above ``max_loci``: capped, nothing reported).  ``strata``: bowtie's ``--best --strata``, only the
+        alignments with the query's fewest seed mismatches, which is also what ``max_loci`` then counts.  ``queries``: strings or
+        a ``FlatSeqs``.  The predicate is ``counts``' own; ``ref_names`` comes along when the genome was loaded by ``load_genome``."""
         seqs = queries if isinstance(queries, FlatSeqs) else FlatSeqs.from_list(list(queries))
-        out = self.genome.align_loci(seqs, n_mm, seedlen, maxtotal, trim5, trim3, max_loci, norc)
+        out = self.genome.align_loci(seqs, n_mm, seedlen, maxtotal, trim5, trim3, max_loci, norc, strata)
         out["ref_names"] = getattr(self.genome, "ref_names", None)
         return out
 

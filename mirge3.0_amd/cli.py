@@ -7,7 +7,9 @@ Same flag names as the reference (``mirge/libs/parse.py``) for what is implement
 scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignored.  Writes the reference's files:
 ``run.log``, ``mapped.csv``, ``unmapped.csv``, ``miR.Counts.csv``, ``miR.RPM.csv``, ``annotation.report.csv/html``
 (+ ``isomirs.csv`` / ``isomirs.samples.csv`` with ``-ie``, ``sample_miRge3.gff`` with ``-gff``, the three
-``a2IEditing.*`` files with ``-ai``, ``<sample>_umiCounts.csv`` with ``-udd``).
+``a2IEditing.*`` files with ``-ai``, ``<sample>_umiCounts.csv`` with ``-udd``, ``unmapped_tmp/`` with ``--unmapped-clusters``
+(FASTA files, the genome SAM and ``<sample>_clusters.tsv``) and ``--unmapped-align`` (the cluster filter's two files, the
+cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences)).
 
 One process: all samples on one GPU, byte-compatible outputs.  Under ``torch.distributed.run`` with N
 ranks: samples are sharded one per GPU (multigpu.py); rank 0 gathers each sample's count columns and its
@@ -89,6 +91,11 @@ def parse_args(argv=None):
                     help="map the reads of unmapped.csv to <org>_genome on the device and cluster them by coordinate: "
                          "unmapped_tmp/*.fa, unmapped_mirna_<sample>_vs_genome_sorted.sam, <sample>_clusters.tsv (the front half of "
                          "the reference's -nmir).  With it -minl -maxl -c -mloc -sl -olc are read (defaults 16 25 2 3 25 14)")
+    ap.add_argument("--unmapped-align", dest="unmapped_align", action="store_true",
+                    help="implies --unmapped-clusters, then filters each sample's clusters (length <= -clc, default 30; poly-A / poly-T "
+                         "ends; <org>_genome_repeats.pckl) and aligns its unmapped reads to the kept cluster sequences on the device: "
+                         "unmapped_tmp/<sample>clusters_trimmed.tsv, _clusters_trimmed_orig.fa, _tmp1.sam, _imperfectMath2Cluster.fa, "
+                         "_tmp2.sam, .sam, _modified.sam, _RepSeq_modified.sam, _selected*.tsv, _modified_selected*_sorted.tsv")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -133,10 +140,12 @@ def parse_args(argv=None):
     args.bowtieVersion = "True"
     if (args.AtoI or args.gff_out) and (args.save_pkl or args.resume):
         ap.error("-ai / -gff run on the device-resident route: not together with -spl / -rr")
+    if args.unmapped_align:
+        args.unmapped_clusters = True
     if args.unmapped_clusters and (args.save_pkl or args.resume or args.backend == "bowtie"):
-        ap.error("--unmapped-clusters runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+        ap.error("--unmapped-clusters / --unmapped-align run on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.unmapped_clusters:
-        for k in ("minl", "maxl", "c", "mloc", "sl", "olc"):
+        for k in ("minl", "maxl", "c", "mloc", "sl", "olc") + (("clc",) if args.unmapped_align else ()):
             v = getattr(args, "ignored_" + k)
             if v is not None and not str(v).lstrip("-").isdigit():
                 ap.error(f"-{k} takes an integer")

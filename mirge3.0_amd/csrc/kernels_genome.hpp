@@ -124,7 +124,7 @@ struct GenomeScanArgs {
     const uint64_t* skeys;
     const uint32_t* svals;
     const GenomeQS* qs;
-    unsigned long long* counts;  // [n queries][3]: alignments with 0, 1, 2 mismatches
+    unsigned long long* counts;  // [n queries][3]: alignments with 0, 1, 2 mismatches -- in the seed when strata, else in all
     int32_t n_mm, maxtotal;
     int32_t ntab;                // tables present (key length tab_k[t], words at tab_bm[t], sorted slice [tab_b, tab_e))
     int32_t tab_k[MIRGE_GENOME_MAXK];
@@ -138,6 +138,11 @@ struct GenomeScanArgs {
     uint32_t* rec_meta;          // (query_base + query) << 3 | strand << 2 | mismatches
     uint32_t* overflow;          // set when a cursor leaves its range (the two passes disagree: a bug, reported by the host)
     uint32_t query_base;
+    // --best --strata (mirge_genome_align_loci_strata): a query's stratum is its fewest SEED mismatches.  The count pass then
+    // counts by seed mismatches, so that the host reads the best stratum and its size from the same [n][3]; the fill pass drops
+    // every candidate whose seed mismatches are not best[query]
+    int32_t strata;
+    const uint8_t* best;         // [n queries], fill pass under strata
 };
 
 #define MIRGE_GENOME_STASH 4  // hits a lane keeps per trip for the wave's merged flush (more go out one atomic each)
@@ -215,7 +220,8 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
                         const uint64_t d1 = (((x1 | (x1 >> 1)) & 0x5555555555555555ull) | g.nm[1]) & lm1;
                         const int tot = __popcll(d0) + __popcll(d1);
                         if (tot > a.maxtotal) continue;
-                        if (__popcll(d0 & g.seed[0]) + __popcll(d1 & g.seed[1]) > a.n_mm) continue;
+                        const int sd = __popcll(d0 & g.seed[0]) + __popcll(d1 & g.seed[1]);
+                        if (sd > a.n_mm) continue;
                         int owner = -1;
                         for (int q = 0; q < g.npieces && owner < 0; q++) {
                             const int plo = g.poff[q], phi = plo + g.plen[q];
@@ -225,6 +231,7 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
                         if constexpr (FILL) {
                             const uint64_t rs = a.range[g.query], len = a.range[g.query + 1] - rs;
                             if (!len) continue;  // capped by max_loci
+                            if (a.strata && sd != (int)a.best[g.query]) continue;  // a worse stratum takes no slot
                             const uint32_t meta = ((a.query_base + g.query) << 3) | (((v >> 2) & 1u) << 2) | (uint32_t)tot;
                             if (n_st < MIRGE_GENOME_STASH) {
                                 st_pos[n_st * 256 + threadIdx.x] = ws;
@@ -237,7 +244,7 @@ __global__ void __launch_bounds__(256) k_genome_scan(GenomeScanArgs a) {
                             }
                             continue;
                         }
-                        const uint32_t hk = g.query * 3u + (uint32_t)tot;
+                        const uint32_t hk = g.query * 3u + (uint32_t)(a.strata ? sd : tot);
                         if (acc_n && hk != acc_key) atomicAdd(&a.counts[acc_key], acc_n);
                         if (hk != acc_key) { acc_key = hk; acc_n = 0; }
                         acc_n++;

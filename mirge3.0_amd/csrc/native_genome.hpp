@@ -1,6 +1,7 @@
 // native_genome.hpp -- part of mirge_native.hip (one translation unit): the genome of the A-to-I report's filter on the device
 // (mirge_genome_create / _create_packed / _destroy), the two bowtie runs it replaces (mirge_genome_align_counts;
-// mirge2_tRF_a2i.py:1056-1096,1297-1316), the same alignments with their positions (mirge_genome_align_loci) and the clustering
+// mirge2_tRF_a2i.py:1056-1096,1297-1316), the same alignments with their positions (mirge_genome_align_loci, and
+// mirge_genome_align_loci_strata: the best stratum only, bowtie's --best --strata) and the clustering
 // of such records (mirge_loci_cluster; novel_mir.py:81-150).  Kernels: kernels_genome.hpp.
 #pragma once
 
@@ -242,7 +243,9 @@ extern "C" int mirge_genome_align_counts(mirge_ctx* c, const mirge_genome* g, co
     return rc;
 }
 
-// ---- alignments with positions (mirge_genome_align_loci): the count pass, then the same scan as a fill pass, then two stable sorts
+// ---- alignments with positions (mirge_genome_align_loci[_strata]): the count pass, then the same scan as a fill pass, then two
+// stable sorts.  strata: the count pass counts by SEED mismatches; a query's best stratum is the first of its three counts that is
+// not zero, and only that stratum is sized, capped by max_loci and filled
 struct mirge_loci {  // on the host: the records in (reference, offset, query, strand) order
     std::vector<uint32_t> query, ref;
     std::vector<uint64_t> off;
@@ -266,9 +269,9 @@ extern "C" int mirge_loci_fetch(const mirge_loci* l, uint32_t* query, uint32_t* 
     return 0;
 }
 
-extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t n,
-                                       int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, int64_t max_loci,
-                                       int32_t norc, uint64_t* totals, mirge_loci** out) {
+extern "C" int mirge_genome_align_loci_strata(mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t n,
+                                              int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3,
+                                              int64_t max_loci, int32_t norc, int32_t strata, uint64_t* totals, mirge_loci** out) {
     if (!out || max_loci < 0 || (n > 0 && !totals)) return fail(-1, "mirge_genome_align_loci: bad argument");
     CHECK(genome_check_args("mirge_genome_align_loci", c, g, queries, offsets, n, n_mm, seedlen, maxtotal, trim5, trim3));
     if (n > (int64_t)(0xFFFFFFFFu >> 3)) return fail(-1, "mirge_genome_align_loci: too many queries for one call");
@@ -281,19 +284,28 @@ extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, cons
     GenomeTables t;
     uint64_t *d_range = nullptr, *d_pos = nullptr, *d_pos2 = nullptr, *d_roff = nullptr;
     uint32_t *d_cursor = nullptr, *d_meta = nullptr, *d_meta2 = nullptr, *d_flag = nullptr, *d_rq = nullptr, *d_rref = nullptr;
-    uint8_t *d_rs = nullptr, *d_rmm = nullptr; void* d_tmp = nullptr;
+    uint8_t *d_rs = nullptr, *d_rmm = nullptr, *d_best = nullptr; void* d_tmp = nullptr;
     auto run = [&]() -> int {
         // ---- pass 1: every query's total; what it reports (all of them, or none when -m caps it) -> its range of the records
         std::vector<uint64_t> range((size_t)n + 1, 0);
         std::vector<unsigned long long> h;
+        std::vector<uint8_t> best(strata ? (size_t)n : 0, 0);
         for (int64_t b = 0; b < n_batches; b++) {
             const int64_t q0 = b * batch, nq = std::min(batch, n - q0);
             CHECK(genome_tables_build(c, g, queries, offsets, q0, nq, n_mm, seedlen, maxtotal, trim5, trim3, norc ? 1 : 0, t));
+            t.sa.strata = strata ? 1 : 0;
             CHECK(genome_count_pass(c, g, t, h));
             for (int64_t i = 0; i < nq; i++) {
-                const uint64_t tot = h[(size_t)i * 3] + h[(size_t)i * 3 + 1] + h[(size_t)i * 3 + 2];
+                const unsigned long long* hc = &h[(size_t)i * 3];
+                const uint64_t tot = hc[0] + hc[1] + hc[2];
                 totals[q0 + i] = tot;
-                range[(size_t)(q0 + i) + 1] = (max_loci && tot > (uint64_t)max_loci) ? 0 : tot;
+                uint64_t rep = tot;  // what the query reports: everything, or its best stratum
+                if (strata) {
+                    const int b = hc[0] ? 0 : (hc[1] ? 1 : 2);
+                    best[(size_t)(q0 + i)] = (uint8_t)b;
+                    rep = hc[b];
+                }
+                range[(size_t)(q0 + i) + 1] = (max_loci && rep > (uint64_t)max_loci) ? 0 : rep;
             }
             if (n_batches > 1) genome_tables_release(c, t);  // one batch: its tables serve the fill pass as they are
         }
@@ -307,6 +319,10 @@ extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, cons
         HIPOK(hipMemcpyAsync(d_range, range.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
         HIPOK(hipMemsetAsync(d_cursor, 0, (size_t)n * 4, c->stream));
         HIPOK(hipMemsetAsync(d_flag, 0, 4, c->stream));
+        if (strata) {
+            CHECK(dalloc(c, &d_best, (size_t)n));
+            HIPOK(hipMemcpyAsync(d_best, best.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+        }
         // ---- pass 2: the same scan writes the records
         for (int64_t b = 0; b < n_batches; b++) {
             const int64_t q0 = b * batch, nq = std::min(batch, n - q0);
@@ -314,6 +330,7 @@ extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, cons
             if (n_batches > 1) CHECK(genome_tables_build(c, g, queries, offsets, q0, nq, n_mm, seedlen, maxtotal, trim5, trim3, norc ? 1 : 0, t));
             t.sa.range = d_range + q0; t.sa.cursor = d_cursor + q0; t.sa.rec_pos = d_pos; t.sa.rec_meta = d_meta; t.sa.overflow = d_flag;
             t.sa.query_base = (uint32_t)q0;
+            t.sa.strata = strata ? 1 : 0; t.sa.best = strata ? d_best + q0 : nullptr;
             if (t.sa.ntab && g->n_bases) {
                 const uint64_t strips = (g->n_bases + MIRGE_GENOME_STRIP - 1) / MIRGE_GENOME_STRIP;
                 LaunchScope ls(c, "k_genome_scan_fill", (double)g->n_bases);
@@ -363,9 +380,15 @@ extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, cons
     c->drain();
     genome_tables_release(c, t);
     for (void* p : {(void*)d_range, (void*)d_pos, (void*)d_pos2, (void*)d_roff, (void*)d_cursor, (void*)d_meta, (void*)d_meta2, (void*)d_flag,
-                    (void*)d_rq, (void*)d_rref, (void*)d_rs, (void*)d_rmm, d_tmp})
+                    (void*)d_rq, (void*)d_rref, (void*)d_rs, (void*)d_rmm, (void*)d_best, d_tmp})
         c->release(p);
     return rc;
+}
+
+extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t n,
+                                       int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, int64_t max_loci,
+                                       int32_t norc, uint64_t* totals, mirge_loci** out) {
+    return mirge_genome_align_loci_strata(c, g, queries, offsets, n, n_mm, seedlen, maxtotal, trim5, trim3, max_loci, norc, 0, totals, out);
 }
 
 // ---- clusters of coordinate-sorted records (mirge_loci_cluster)

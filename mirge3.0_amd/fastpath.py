@@ -307,6 +307,9 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
         g = GpuGenome(ctx, load_genome(ctx, str(genome_base(args)), tm_g))  # the genome -ai loaded, when it ran on the device
         tm.setdefault("genome_load_s", tm_g.get("genome_load_s", 0.0))
         out["unmapped_clusters"] = _unmapped.run(args, ctx, workDir, base_names, g, tm)
+        if getattr(args, "unmapped_align", False):  # the next stretch of -nmir (novel_mir.py:152-210,362-421): reads against their clusters
+            from . import unmapped_align as _unmapped_align
+            out["unmapped_align"] = _unmapped_align.run(args, ctx, workDir, base_names, tm)
     if getattr(args, "isoform_entropy", False):  # -ie reads the miRNA rows of the mapped frame: build just those
         from .countjoin import isomir_entropy_tables
         isomir_entropy_tables(mirna_frame(seqs, ps, ref, counts, order, casc, base_names), base_names, out["filtered"], workDir)
