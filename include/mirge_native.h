@@ -414,6 +414,28 @@ int mirge_loci_cluster(mirge_ctx* ctx, int64_t n, const uint32_t* ref, const uin
                        int64_t* n_clusters, uint32_t* c_ref, uint8_t* c_strand, uint64_t* c_start, uint64_t* c_end,
                        int64_t* c_reads, uint32_t* c_members);
 
+/* ---- cluster features (generate_featureFiles.py, readCluster.py, get_precursors): the reads of a sample stacked on their clusters
+ * mirge_cluster_diagonals  per row (a read and the cluster it was aligned to; reads up to 64 nt, clusters up to 128 nt): diag = the best
+ *                          ungapped local diagonal (cluster index - read index) under match +2 / mismatch -1, score = its score,
+ *                          identity = equal bases over the WHOLE overlap of the two sequences on that diagonal, flag: bit 0 = score
+ *                          <= 2 * min(L, C) - 20 (a gapped alignment at 20 per gap character could tie or win: the caller aligns that
+ *                          row's cluster on the host), bit 1 = no positive score.  Equal scores: the diagonal whose end cell comes first
+ *                          in the cluster, then first in the read.  A base that is not A/C/G/T matches nothing.
+ * mirge_cluster_pileup     rows [row_start[k], row_start[k + 1]) are cluster k's.  head / tail[k] = the largest overhang of a read left /
+ *                          right of the cluster; col_off[n_clusters + 1] = where cluster k's head + c_len + tail columns start in
+ *                          tally[cap_cols][5] = the rows' counts summed per column and symbol in the order A, T, C, G, other.
+ * mirge_genome_fetch       windows (reference, 0-based start, length) of the resident genome as ASCII at out + out_off[i] (out_off[n + 1],
+ *                          out_off[i + 1] - out_off[i] = len[i]): 'N' where the genome holds no base, reverse-complemented when minus,
+ *                          'U' for 'T' when rna.  The caller clamps the bounds; nothing is read past a reference's stretches. */
+int mirge_cluster_diagonals(mirge_ctx* ctx, const char* reads, const int64_t* r_off, int64_t n_rows, const char* clusters,
+                            const int64_t* c_off, int64_t n_clusters, const uint32_t* row_cluster, int32_t* diag, int32_t* score,
+                            int32_t* identity, uint8_t* flag);
+int mirge_cluster_pileup(mirge_ctx* ctx, const char* reads, const int64_t* r_off, int64_t n_rows, const int64_t* c_len,
+                         const int64_t* row_start, int64_t n_clusters, const int32_t* diag, const int64_t* count, int32_t* head,
+                         int32_t* tail, int64_t* col_off, int64_t* tally, int64_t cap_cols);
+int mirge_genome_fetch(mirge_ctx* ctx, const mirge_genome* genome, int64_t n, const uint32_t* ref, const int64_t* start,
+                       const int64_t* len, const uint8_t* minus, const uint8_t* rna, const int64_t* out_off, char* out);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

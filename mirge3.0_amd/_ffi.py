@@ -30,6 +30,7 @@ EXPORTS = [
     "mirge_cascade_prepare", "mirge_cascade_walks", "mirge_cascade_wg_times", "mirge_ctx_profile_only", "mirge_ctx_profile_units", "mirge_ctx_profile_reset", "mirge_ctx_profile_count", "mirge_ctx_profile_get",
     "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
+    "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch",
 ]
 
 
@@ -451,6 +452,21 @@ class DeviceGenome:
             lib.mirge_loci_destroy(h)
         out["totals"] = totals[:n]
         return out
+
+    def fetch(self, ref, start, length, minus, rna) -> List[str]:
+        """``mirge_genome_fetch``: the windows ``[start, start + length)`` (0-based) of references ``ref`` as text: 'N' where the
+        genome holds no base, reverse-complemented where ``minus``, 'U' for 'T' where ``rna``"""
+        ref = np.ascontiguousarray(ref, dtype=np.uint32)
+        start, length = (np.ascontiguousarray(a, dtype=np.int64) for a in (start, length))
+        minus, rna = (np.ascontiguousarray(a, dtype=np.uint8) for a in (minus, rna))
+        n = ref.shape[0]
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(length, out=off[1:])
+        out = np.zeros(max(int(off[n]), 1), dtype=np.uint8)
+        _check(load().mirge_genome_fetch(self.ctx._h, self._h, C.c_int64(n), _p(ref), _p(start), _p(length), _p(minus), _p(rna), _p(off),
+                                         _p(out)), "mirge_genome_fetch")
+        text = out.tobytes().decode("ascii")
+        return [text[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
 
     def close(self):
         if self._h:
@@ -893,3 +909,48 @@ def loci_cluster(ctx: Context, ref, off, strand, query, qlen, qcount, ref_skip, 
     out = {k: v[:nc.value] for k, v in tab.items()}
     out["cluster"] = cluster[:n]
     return out
+
+
+PILEUP_MAXREAD, PILEUP_MAXCLUSTER = 64, 128  # csrc/kernels_pileup.hpp
+PILEUP_FLAG_GAP, PILEUP_FLAG_NONE = 1, 2
+
+
+def cluster_diagonals(ctx: Context, reads: FlatSeqs, clusters: FlatSeqs, row_cluster) -> dict:
+    """``mirge_cluster_diagonals``: per row ``diag`` (cluster index - read index of the best ungapped local diagonal), ``score``,
+    ``identity`` (equal bases over the whole overlap on that diagonal) and ``flag`` (PILEUP_FLAG_GAP: a gapped alignment could
+    tie or win, PILEUP_FLAG_NONE: nothing scores)"""
+    row_cluster = np.ascontiguousarray(row_cluster, dtype=np.uint32)
+    n = len(reads)
+    m = max(n, 1)
+    out = dict(diag=np.zeros(m, np.int32), score=np.zeros(m, np.int32), identity=np.zeros(m, np.int32), flag=np.zeros(m, np.uint8))
+    rd, ro = np.ascontiguousarray(reads.data, dtype=np.uint8), np.ascontiguousarray(reads.offsets, dtype=np.int64)
+    cd, co = np.ascontiguousarray(clusters.data, dtype=np.uint8), np.ascontiguousarray(clusters.offsets, dtype=np.int64)
+    _check(load().mirge_cluster_diagonals(ctx._h, _p(rd) if rd.size else C.c_void_p(0), _p(ro), C.c_int64(n),
+                                          _p(cd) if cd.size else C.c_void_p(0), _p(co), C.c_int64(len(clusters)), _p(row_cluster),
+                                          *(_p(out[k]) for k in ("diag", "score", "identity", "flag"))), "mirge_cluster_diagonals")
+    return {k: v[:n] for k, v in out.items()}
+
+
+def cluster_pileup(ctx: Context, reads: FlatSeqs, c_len, row_start, diag, count) -> dict:
+    """``mirge_cluster_pileup``: rows ``[row_start[k], row_start[k + 1])`` are cluster k's -> ``head`` / ``tail`` (int32 per
+    cluster), ``col_off`` (int64 [clusters + 1]) and ``tally`` (int64 [columns, 5]: A, T, C, G, other)"""
+    c_len, row_start, count = (np.ascontiguousarray(a, dtype=np.int64) for a in (c_len, row_start, count))
+    diag = np.ascontiguousarray(diag, dtype=np.int32)
+    nc = c_len.shape[0]
+    # the columns the call will write, from the same diagonals it is given (it checks them and fails on a smaller array): no
+    # worst-case array of 126 spare columns per cluster
+    lens = np.diff(np.ascontiguousarray(reads.offsets, dtype=np.int64))
+    k = np.repeat(np.arange(nc), np.diff(row_start))
+    pad_h, pad_t = np.zeros(nc, np.int64), np.zeros(nc, np.int64)
+    if diag.shape[0] == k.shape[0] == lens.shape[0] and nc:
+        np.maximum.at(pad_h, k, -diag.astype(np.int64))
+        np.maximum.at(pad_t, k, lens + diag - c_len[k])
+    cap = int((c_len + pad_h + pad_t).sum())
+    head, tail = np.zeros(max(nc, 1), np.int32), np.zeros(max(nc, 1), np.int32)
+    col_off = np.zeros(nc + 1, np.int64)
+    tally = np.empty((max(cap, 1), 5), np.int64)
+    rd, ro = np.ascontiguousarray(reads.data, dtype=np.uint8), np.ascontiguousarray(reads.offsets, dtype=np.int64)
+    _check(load().mirge_cluster_pileup(ctx._h, _p(rd) if rd.size else C.c_void_p(0), _p(ro), C.c_int64(len(reads)), _p(c_len), _p(row_start),
+                                       C.c_int64(nc), _p(diag), _p(count), _p(head), _p(tail), _p(col_off), _p(tally), C.c_int64(cap)),
+           "mirge_cluster_pileup")
+    return dict(head=head[:nc], tail=tail[:nc], col_off=col_off, tally=tally[:int(col_off[nc])])

@@ -9,7 +9,8 @@ scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignor
 (+ ``isomirs.csv`` / ``isomirs.samples.csv`` with ``-ie``, ``sample_miRge3.gff`` with ``-gff``, the three
 ``a2IEditing.*`` files with ``-ai``, ``<sample>_umiCounts.csv`` with ``-udd``, ``unmapped_tmp/`` with ``--unmapped-clusters``
 (FASTA files, the genome SAM and ``<sample>_clusters.tsv``) and ``--unmapped-align`` (the cluster filter's two files, the
-cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences)).
+cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences) and ``--unmapped-features``
+(``<sample>_features.tsv``, ``_cluster.txt``, ``_precursor.fa``)).
 
 One process: all samples on one GPU, byte-compatible outputs.  Under ``torch.distributed.run`` with N
 ranks: samples are sharded one per GPU (multigpu.py); rank 0 gathers each sample's count columns and its
@@ -96,6 +97,10 @@ def parse_args(argv=None):
                          "ends; <org>_genome_repeats.pckl) and aligns its unmapped reads to the kept cluster sequences on the device: "
                          "unmapped_tmp/<sample>clusters_trimmed.tsv, _clusters_trimmed_orig.fa, _tmp1.sam, _imperfectMath2Cluster.fa, "
                          "_tmp2.sam, .sam, _modified.sam, _RepSeq_modified.sam, _selected*.tsv, _modified_selected*_sorted.tsv")
+    ap.add_argument("--unmapped-features", dest="unmapped_features", action="store_true",
+                    help="implies --unmapped-align, then stacks each sample's aligned reads on their clusters on the device and writes "
+                         "what the reference's generate_featureFiles / get_precursors write: unmapped_tmp/<sample>_features.tsv, "
+                         "_cluster.txt and _precursor.fa (the input of RNAfold; folding and the novel-miRNA screen stay out of scope)")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -140,10 +145,12 @@ def parse_args(argv=None):
     args.bowtieVersion = "True"
     if (args.AtoI or args.gff_out) and (args.save_pkl or args.resume):
         ap.error("-ai / -gff run on the device-resident route: not together with -spl / -rr")
+    if args.unmapped_features:
+        args.unmapped_align = True
     if args.unmapped_align:
         args.unmapped_clusters = True
     if args.unmapped_clusters and (args.save_pkl or args.resume or args.backend == "bowtie"):
-        ap.error("--unmapped-clusters / --unmapped-align run on the device-resident route: not together with -spl / -rr / --backend bowtie")
+        ap.error("--unmapped-clusters / --unmapped-align / --unmapped-features run on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.unmapped_clusters:
         for k in ("minl", "maxl", "c", "mloc", "sl", "olc") + (("clc",) if args.unmapped_align else ()):
             v = getattr(args, "ignored_" + k)

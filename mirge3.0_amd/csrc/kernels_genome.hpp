@@ -415,3 +415,39 @@ __global__ void k_cluster_assign(uint32_t n, const ClusterItem* __restrict__ sca
     atomicAdd(&t.reads[c], (unsigned long long)qcount[q]);
     atomicAdd(&t.members[c], 1u);
 }
+
+// ---- windows of the resident genome as text (mirge_genome_fetch): one wave per window, a lane per output byte.  Output byte i
+// of a window is reference position start + i ('+') or start + len - 1 - i, complemented ('-'); a position inside no stretch (an
+// ambiguous character, or past what the genome holds of the reference) is 'N'.  The stretch of a position: the last one whose
+// (reference, first position) is not past it -- the stretches lie in that order.
+struct GenomeWindow {
+    uint64_t start;    // 0-based in the reference
+    uint64_t out_off;  // where the window's bytes start in the output
+    uint32_t ref, len;
+    uint8_t minus, rna, pad[6];
+};
+
+__global__ void __launch_bounds__(64)
+k_genome_fetch(uint32_t n_win, const GenomeWindow* __restrict__ win, const uint64_t* __restrict__ text, const uint64_t* __restrict__ s_start,
+               uint32_t n_str, const uint32_t* __restrict__ str_ref, const uint64_t* __restrict__ str_off, char* __restrict__ out) {
+    if (blockIdx.x >= n_win) return;
+    const GenomeWindow w = win[blockIdx.x];
+    for (uint32_t i = threadIdx.x; i < w.len; i += 64) {
+        const uint64_t p = w.start + (w.minus ? (uint64_t)(w.len - 1 - i) : (uint64_t)i);
+        char ch = 'N';
+        if (n_str) {
+            uint32_t l = 0, h = n_str;  // the largest s with (str_ref[s], str_off[s]) <= (ref, p), if stretch 0 is
+            while (h - l > 1) {
+                const uint32_t m = (l + h) >> 1;
+                if (str_ref[m] < w.ref || (str_ref[m] == w.ref && str_off[m] <= p)) l = m; else h = m;
+            }
+            if (str_ref[l] == w.ref && str_off[l] <= p && p - str_off[l] < s_start[l + 1] - s_start[l]) {
+                const uint64_t q = s_start[l] + (p - str_off[l]);
+                uint32_t c = (uint32_t)(text[q >> 5] >> (2 * (q & 31))) & 3u;
+                if (w.minus) c = 3u - c;
+                ch = c == 0 ? 'A' : c == 1 ? 'C' : c == 2 ? 'G' : (w.rna ? 'U' : 'T');
+            }
+        }
+        out[w.out_off + i] = ch;
+    }
+}

@@ -47,3 +47,4 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_csv.hpp"
 #include "native_iso.hpp"
 #include "native_genome.hpp"
+#include "native_pileup.hpp"

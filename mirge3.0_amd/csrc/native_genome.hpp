@@ -488,3 +488,42 @@ extern "C" int mirge_loci_cluster(mirge_ctx* c, int64_t n, const uint32_t* ref, 
         c->release(p);
     return rc;
 }
+
+// ---- windows of the genome as text (mirge_genome_fetch): templateSeq of calculateFeature and the precursor windows of
+// get_precursors.  The caller computes the bounds (it knows the references' lengths); the kernel only copies.
+extern "C" int mirge_genome_fetch(mirge_ctx* c, const mirge_genome* g, int64_t n, const uint32_t* ref, const int64_t* start,
+                                  const int64_t* len, const uint8_t* minus, const uint8_t* rna, const int64_t* out_off, char* out) {
+    if (!c || !g || n < 0 || n > 0x7FFFFFFFll) return fail(-1, "mirge_genome_fetch: bad argument");
+    if (n == 0) return 0;
+    if (!ref || !start || !len || !minus || !rna || !out_off || out_off[0] != 0 || (out_off[n] > 0 && !out))
+        return fail(-1, "mirge_genome_fetch: bad argument");
+    std::vector<GenomeWindow> win((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if (ref[i] >= g->n_refs || start[i] < 0 || len[i] < 0 || len[i] > 0x7FFFFFFFll || out_off[i + 1] - out_off[i] != len[i])
+            return fail(-1, "mirge_genome_fetch: a window names a reference that does not exist, starts before base 0 or its "
+                            "output stretch is not its length");
+        GenomeWindow w{};
+        w.start = (uint64_t)start[i]; w.out_off = (uint64_t)out_off[i]; w.ref = ref[i]; w.len = (uint32_t)len[i];
+        w.minus = minus[i] ? 1 : 0; w.rna = rna[i] ? 1 : 0;
+        win[(size_t)i] = w;
+    }
+    if (out_off[n] == 0) return 0;
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    GenomeWindow* d_win = nullptr; char* d_out = nullptr;
+    auto run = [&]() -> int {
+        CHECK(dalloc(c, &d_win, (size_t)n)); CHECK(dalloc(c, &d_out, (size_t)out_off[n]));
+        HIPOK(hipMemcpyAsync(d_win, win.data(), (size_t)n * sizeof(GenomeWindow), hipMemcpyHostToDevice, c->stream));
+        { LaunchScope ls(c, "k_genome_fetch", (double)out_off[n]);
+          hipLaunchKernelGGL(k_genome_fetch, dim3((uint32_t)n), dim3(64), 0, c->stream, (uint32_t)n, d_win, g->text, g->s_start, g->n_str,
+                             g->str_ref, g->str_off, d_out); }
+        HIPOK(hipMemcpyAsync(out, d_out, (size_t)out_off[n], hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        return 0;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    c->drain();
+    c->release(d_win); c->release(d_out);
+    return rc;
+}

@@ -310,6 +310,9 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
         if getattr(args, "unmapped_align", False):  # the next stretch of -nmir (novel_mir.py:152-210,362-421): reads against their clusters
             from . import unmapped_align as _unmapped_align
             out["unmapped_align"] = _unmapped_align.run(args, ctx, workDir, base_names, tm)
+            if getattr(args, "unmapped_features", False):  # generate_featureFiles / get_precursors (novel_mir.py:424-428)
+                from . import unmapped_features as _unmapped_features
+                out["unmapped_features"] = _unmapped_features.run(args, ctx, workDir, base_names, tm)
     if getattr(args, "isoform_entropy", False):  # -ie reads the miRNA rows of the mapped frame: build just those
         from .countjoin import isomir_entropy_tables
         isomir_entropy_tables(mirna_frame(seqs, ps, ref, counts, order, casc, base_names), base_names, out["filtered"], workDir)
