@@ -436,6 +436,36 @@ int mirge_cluster_pileup(mirge_ctx* ctx, const char* reads, const int64_t* r_off
 int mirge_genome_fetch(mirge_ctx* ctx, const mirge_genome* genome, int64_t n, const uint32_t* ref, const int64_t* start,
                        const int64_t* len, const uint8_t* minus, const uint8_t* rna, const int64_t* out_off, char* out);
 
+/* ---- per-sample SAM alignments (`--sam-out`): the text the reference's -bam route hands to `samtools view` (manifoldAlign.py:12-64,
+ * bamFmt.py:9-170, summary.py:841-880), one line per RAW read, formatted on the device and written chunk by chunk.
+ * One call writes ONE sample's file: `header` (header_len bytes, verbatim), then for every class in class_pass[n_class] order (pass
+ * numbers; at most 7; a pass not named writes nothing) the frame's rows of that pass in frame order (order[k] = handle index of the
+ * read in row k), each with count c >= 1 in column `sample` as c lines `READ_k ...`, k = 0 .. c-1.  passes[n_pass] (n_pass >= the
+ * result's) describe every named pass: its library, the -5 / -3 trim of its policy and the lift of its references to the genome:
+ * chrom_of_ref[n_refs] indexes the chromosome strings (-1: reads of this reference write no line), minus[n_refs] != 0 = minus strand
+ * (FLAG 16, SEQ reverse-complemented), seg_ptr[n_refs + 1] is a CSR into seg_s / seg_e (transcript coordinates, 1-based, inclusive)
+ * and cds_lo / cds_hi (the two genome coordinates of the same segment as the header writes them).  *n_lines_out = lines below the
+ * header, *n_bytes_out = their bytes.  Any failure returns an error code and removes the file.  Chunk and tile sizes:
+ * MIRGE_SAM_CHUNK_BYTES / MIRGE_SAM_TILE_BYTES (README). */
+typedef struct mirge_sam_pass {
+    const mirge_lib* lib;
+    int32_t trim5, trim3;
+    int64_t n_refs;
+    const int32_t* chrom_of_ref;
+    const uint8_t* minus;
+    const int64_t* seg_ptr;
+    const int32_t* seg_s;
+    const int32_t* seg_e;
+    const int64_t* cds_lo;
+    const int64_t* cds_hi;
+    int64_t n_chrom;
+    const char* chrom_data;
+    const int64_t* chrom_off;
+} mirge_sam_pass;
+int mirge_sam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
+                           const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass, const char* path,
+                           const char* header, int64_t header_len, int64_t* n_lines_out, int64_t* n_bytes_out);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

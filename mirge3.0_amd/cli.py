@@ -101,6 +101,12 @@ def parse_args(argv=None):
                     help="implies --unmapped-align, then stacks each sample's aligned reads on their clusters on the device and writes "
                          "what the reference's generate_featureFiles / get_precursors write: unmapped_tmp/<sample>_features.tsv, "
                          "_cluster.txt and _precursor.fa (the input of RNAfold; folding and the novel-miRNA screen stay out of scope)")
+    ap.add_argument("--sam-out", dest="sam_out", action="store_true",
+                    help="write <sample>.sam for every sample: one alignment line per raw read of the snoRNA, rRNA, ncrna others, mRNA, "
+                         "miRNA and hairpin classes, lifted to the genome coordinates the libraries' header lines carry, formatted on "
+                         "the device (the text the reference's -bam hands to samtools; BAM, sorting and indexing stay with samtools)")
+    ap.add_argument("--sam-header", dest="sam_header", default=None, metavar="FILE",
+                    help="with --sam-out: FILE is copied verbatim to the top of every <sample>.sam (default: '@HD VN:1.0 SO:unsorted')")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -156,6 +162,12 @@ def parse_args(argv=None):
             v = getattr(args, "ignored_" + k)
             if v is not None and not str(v).lstrip("-").isdigit():
                 ap.error(f"-{k} takes an integer")
+    if args.sam_header and not args.sam_out:
+        ap.error("--sam-header requires --sam-out")
+    if args.sam_out and (args.save_pkl or args.resume or args.backend == "bowtie"):
+        ap.error("--sam-out runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+    if args.sam_header and not os.path.isfile(args.sam_header):
+        ap.error(f"--sam-header: {args.sam_header} is not a file")
     if args.genome_filter == "gpu" and args.genome_retained:
         ap.error("--genome-filter gpu computes what --genome-retained lists: give one of them")
     if args.backend == "bowtie" and (args.AtoI or args.gff_out or args.isoform_entropy):
@@ -244,6 +256,8 @@ def main(argv=None):
             fh.write(" ".join(sys.argv) + "\n")
     if world > 1 and (args.resume or args.save_pkl):
         sys.exit("-spl / -rr are single-process options")
+    if world > 1 and args.sam_out:
+        sys.exit("--sam-out is a single-process option")
     if not (Path(args.libraries_path) / args.organism_name / "index.Libs").exists():
         sys.exit("\n ERROR: The path to miRge libraries is incorrect or does not exist!\n")
     if args.organism_name == "hamster":  # mirge/__main__.py:61-64

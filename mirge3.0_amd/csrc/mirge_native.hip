@@ -8,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -48,3 +49,4 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_iso.hpp"
 #include "native_genome.hpp"
 #include "native_pileup.hpp"
+#include "native_sam.hpp"

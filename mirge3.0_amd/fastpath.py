@@ -313,6 +313,11 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
             if getattr(args, "unmapped_features", False):  # generate_featureFiles / get_precursors (novel_mir.py:424-428)
                 from . import unmapped_features as _unmapped_features
                 out["unmapped_features"] = _unmapped_features.run(args, ctx, workDir, base_names, tm)
+    if getattr(args, "sam_out", False):  # --sam-out: <sample>.sam, one line per raw read (manifoldAlign.py:12-64, bamFmt.py:115-170)
+        if ann is not None or res is None:
+            raise RuntimeError("--sam-out needs the cascade's result on the device (a single-process run)")
+        from . import sam_export as _sam_export
+        out["sam_out"] = _sam_export.run(args, workDir, base_names, casc, uniq, res, order, tm)
     if getattr(args, "isoform_entropy", False):  # -ie reads the miRNA rows of the mapped frame: build just those
         from .countjoin import isomir_entropy_tables
         isomir_entropy_tables(mirna_frame(seqs, ps, ref, counts, order, casc, base_names), base_names, out["filtered"], workDir)
