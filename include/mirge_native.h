@@ -466,6 +466,20 @@ int mirge_sam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
                            const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass, const char* path,
                            const char* header, int64_t header_len, int64_t* n_lines_out, int64_t* n_bytes_out);
 
+/* ---- per-sample sorted BAM and its index (`--sorted-bam`): the records of mirge_sam_write_device's file (same rows, same lift) as BAM v1,
+ * sorted by (refID, pos, reverse flag) -- stably with respect to that file's row order, a row's copies in k order --, BGZF-compressed
+ * and indexed, all produced on the device in one call.  `header` (header_len bytes) is the front of the uncompressed stream as the
+ * caller built it: magic, l_text, text, n_ref and the n_ref references.  chrom_refid + chrom_refid_off[p] .. [p + 1] maps pass p's
+ * chromosome indices (mirge_sam_pass.chrom_of_ref) to refIDs; -1 = no @SQ names it, an error when a kept row lies there.  Errors are
+ * raised before anything is written: such a chromosome (named in the message), a position outside [0, 2^29), a QNAME beyond 254
+ * characters.  *n_records_out = records, *n_stream_bytes_out = uncompressed bytes, *n_file_bytes_out = bytes of the .bam.
+ * `threads` sizes the host pool of MIRGE_BAM_DEFLATE=host.  MIRGE_BAM_BLOCK_BYTES / MIRGE_BAM_CHUNK_BLOCKS / MIRGE_BAM_DEFLATE: README. */
+int mirge_bam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
+                           const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                           const int32_t* chrom_refid, const int64_t* chrom_refid_off, int32_t n_ref, const char* bam_path,
+                           const char* bai_path, const char* header, int64_t header_len, int32_t threads, int64_t* n_records_out,
+                           int64_t* n_stream_bytes_out, int64_t* n_file_bytes_out);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

@@ -104,9 +104,14 @@ def parse_args(argv=None):
     ap.add_argument("--sam-out", dest="sam_out", action="store_true",
                     help="write <sample>.sam for every sample: one alignment line per raw read of the snoRNA, rRNA, ncrna others, mRNA, "
                          "miRNA and hairpin classes, lifted to the genome coordinates the libraries' header lines carry, formatted on "
-                         "the device (the text the reference's -bam hands to samtools; BAM, sorting and indexing stay with samtools)")
+                         "the device (the text the reference's -bam hands to samtools; --sorted-bam writes the sorted, indexed BAM)")
     ap.add_argument("--sam-header", dest="sam_header", default=None, metavar="FILE",
-                    help="with --sam-out: FILE is copied verbatim to the top of every <sample>.sam (default: '@HD VN:1.0 SO:unsorted')")
+                    help="with --sam-out: FILE is copied verbatim to the top of every <sample>.sam (default: '@HD VN:1.0 SO:unsorted'); "
+                         "with --sorted-bam (required there): its @SQ SN:/LN: lines are the BAM's reference list, in that order")
+    ap.add_argument("--sorted-bam", dest="sorted_bam", action="store_true",
+                    help="write <sample>_sorted.bam and <sample>_sorted.bai for every sample: the records of --sam-out's <sample>.sam as "
+                         "BAM, coordinate-sorted, BGZF-compressed and indexed on the device (what the reference's -bam gets from samtools "
+                         "view / sort / index); needs --sam-header FILE with the genome's @SQ lines; independent of --sam-out")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -162,12 +167,23 @@ def parse_args(argv=None):
             v = getattr(args, "ignored_" + k)
             if v is not None and not str(v).lstrip("-").isdigit():
                 ap.error(f"-{k} takes an integer")
-    if args.sam_header and not args.sam_out:
-        ap.error("--sam-header requires --sam-out")
+    if args.sam_header and not (args.sam_out or args.sorted_bam):
+        ap.error("--sam-header requires --sam-out or --sorted-bam")
+    if args.sorted_bam and (args.save_pkl or args.resume or args.backend == "bowtie"):
+        ap.error("--sorted-bam runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+    if args.sorted_bam and not args.sam_header:
+        ap.error("--sorted-bam requires --sam-header FILE with the @SQ SN:/LN: lines of the genome the libraries were built on")
     if args.sam_out and (args.save_pkl or args.resume or args.backend == "bowtie"):
         ap.error("--sam-out runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.sam_header and not os.path.isfile(args.sam_header):
         ap.error(f"--sam-header: {args.sam_header} is not a file")
+    if args.sorted_bam:
+        from .bam_export import parse_sq
+        try:
+            with open(args.sam_header, "rb") as fh:
+                parse_sq(fh.read())
+        except ValueError as e:
+            ap.error(str(e))
     if args.genome_filter == "gpu" and args.genome_retained:
         ap.error("--genome-filter gpu computes what --genome-retained lists: give one of them")
     if args.backend == "bowtie" and (args.AtoI or args.gff_out or args.isoform_entropy):
@@ -258,6 +274,8 @@ def main(argv=None):
         sys.exit("-spl / -rr are single-process options")
     if world > 1 and args.sam_out:
         sys.exit("--sam-out is a single-process option")
+    if world > 1 and args.sorted_bam:
+        sys.exit("--sorted-bam is a single-process option")
     if not (Path(args.libraries_path) / args.organism_name / "index.Libs").exists():
         sys.exit("\n ERROR: The path to miRge libraries is incorrect or does not exist!\n")
     if args.organism_name == "hamster":  # mirge/__main__.py:61-64

@@ -143,6 +143,16 @@ __device__ __forceinline__ char sam_text_at(const SamPass& sp, unsigned long lon
 }
 __device__ __forceinline__ char sam_complement(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
+// START of a read of Ls bases at offset o of reference r, lifted to the genome: fetch_pos_coordinate / fetch_neg_coordinate
+// (bamFmt.py:36-113): the FIRST segment that holds POS decides; none: POS itself
+__device__ __forceinline__ long long sam_lift_start(const SamPass& sp, int32_t r, int32_t o, int Ls, bool minus) {
+    const long long pos1 = (long long)o + 1;
+    for (uint32_t s = sp.seg_ptr[r]; s < sp.seg_ptr[r + 1]; s++)
+        if (pos1 >= (long long)sp.seg_s[s] && pos1 <= (long long)sp.seg_e[s])
+            return minus ? sp.cds_hi[s] - (pos1 - (long long)sp.seg_s[s]) - (long long)Ls + 1 : sp.cds_lo[s] + (pos1 - (long long)sp.seg_s[s]);
+    return pos1;
+}
+
 // copy k of the row of unique read `read` (a row k_sam_select kept)
 template <bool WRITE>
 __device__ __forceinline__ void sam_line(const SamTables& t, uint32_t read, uint32_t k, SamOut<WRITE>& w) {
@@ -162,15 +172,7 @@ __device__ __forceinline__ void sam_line(const SamTables& t, uint32_t read, uint
     const int32_t ci = sp.chrom_of_ref[r];
     for (uint32_t x = sp.chrom_off[ci]; x < sp.chrom_off[ci + 1]; x++) w.ch((char)sp.chrom_data[x]);
     w.ch('\t');
-    // fetch_pos_coordinate / fetch_neg_coordinate (bamFmt.py:36-113): the FIRST segment that holds POS decides; none: POS itself
-    const long long pos1 = (long long)o + 1;
-    long long start = pos1;
-    for (uint32_t s = sp.seg_ptr[r]; s < sp.seg_ptr[r + 1]; s++)
-        if (pos1 >= (long long)sp.seg_s[s] && pos1 <= (long long)sp.seg_e[s]) {
-            start = minus ? sp.cds_hi[s] - (pos1 - (long long)sp.seg_s[s]) - (long long)Ls + 1 : sp.cds_lo[s] + (pos1 - (long long)sp.seg_s[s]);
-            break;
-        }
-    w.i64(start);
+    w.i64(sam_lift_start(sp, r, o, Ls, minus));
     w.str("\t255\t"); w.u64((unsigned long long)Ls); w.str("M\t*\t0\t0\t");
     if (minus) for (int p = Ls - 1; p >= 0; p--) w.ch(sam_complement(rd.at(sp.trim5 + p)));
     else for (int p = 0; p < Ls; p++) w.ch(rd.at(sp.trim5 + p));

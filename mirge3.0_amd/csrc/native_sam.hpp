@@ -14,100 +14,86 @@ static size_t sam_env_bytes(const char* name, size_t dflt) {
     return x > 0 ? (size_t)x : dflt;
 }
 
-extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
-                                      const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
-                                      const char* path, const char* header, int64_t header_len, int64_t* n_lines_out,
-                                      int64_t* n_bytes_out) {
-    if (!c || !U || !res || (U->n && !order) || !class_pass || n_class < 1 || n_class > MIRGE_SAM_NCLASS || !passes || n_pass < 1 ||
-        n_pass > MIRGE_MAX_PASSES || n_pass < res->n_pass || !path || (!header && header_len) || header_len < 0 || U->n_samples < 1 ||
-        sample < 0 || sample >= U->n_samples || res->n != U->n)
-        return fail(-1, "mirge_sam_write_device: bad argument");
-    // hipCUB's scans take an `int` item count, and the flag array holds one entry per class and frame row
-    if ((unsigned long long)U->n * MIRGE_SAM_NCLASS >= 0x7FFFFFF0ull) return fail(-5, "mirge_sam_write_device: too many unique reads for one call");
-    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
-        if (U->g[gi].n && U->g[gi].orig) return fail(-1, "mirge_sam_write_device: the read set is not a collapse result");
-        if (U->g[gi].n != res->g[gi].n && !res->dmeta) return fail(-1, "mirge_sam_write_device: result and read set differ");
-    }
-    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
-    HostClock hc("sam_write_device");
-    const size_t n = (size_t)U->n;
-    // ---- the passes' tables as ONE blob: 8-byte items first, then 4-byte, then bytes
-    std::vector<SamPass> hp((size_t)n_pass);
-    std::memset(hp.data(), 0, hp.size() * sizeof(SamPass));
-    std::vector<long long> b8;
-    std::vector<uint32_t> b4;
-    std::vector<uint8_t> b1;
-    struct At { size_t lo, hi, chrom, minus, ptr, s, e, coff, cdata; };
-    std::vector<At> at((size_t)n_pass);
-    for (int p = 0; p < n_pass; p++) hp[(size_t)p].cls = -1;
-    for (int k = 0; k < n_class; k++) {
-        const int32_t p = class_pass[k];
-        if (p < 0 || p >= n_pass || hp[(size_t)p].cls >= 0) return fail(-1, "mirge_sam_write_device: class order names a pass twice or out of range");
-        hp[(size_t)p].cls = k;
-    }
-    for (int p = 0; p < n_pass; p++) {
-        SamPass& sp = hp[(size_t)p];
-        if (sp.cls < 0) continue;
-        const mirge_sam_pass& in = passes[p];
-        if (!in.lib || in.n_refs != in.lib->n_refs || in.n_refs < 0 || in.n_refs >= 0x7FFFFFF0ll || in.trim5 < 0 || in.trim3 < 0 ||
-            in.n_chrom < 0 || (in.n_refs && (!in.chrom_of_ref || !in.minus || !in.seg_ptr)) || (in.n_chrom && (!in.chrom_off || !in.chrom_data)))
-            return fail(-1, "mirge_sam_write_device: lift tables of pass " + std::to_string(p) + " do not fit its library");
-        const int64_t n_seg = in.n_refs ? in.seg_ptr[in.n_refs] : 0;
-        const int64_t n_cb = in.n_chrom ? in.chrom_off[in.n_chrom] - in.chrom_off[0] : 0;
-        if (n_seg < 0 || n_seg >= 0x7FFFFFF0ll || n_cb < 0 || n_cb >= 0x7FFFFFF0ll || in.n_chrom >= 0x7FFFFFF0ll ||
-            (n_seg && (!in.seg_s || !in.seg_e || !in.cds_lo || !in.cds_hi)))
-            return fail(-1, "mirge_sam_write_device: lift tables of pass " + std::to_string(p) + " are malformed");
-        for (int64_t r = 0; r < in.n_refs; r++)
-            if (in.seg_ptr[r] < 0 || in.seg_ptr[r + 1] < in.seg_ptr[r] || in.chrom_of_ref[r] >= in.n_chrom)
-                return fail(-1, "mirge_sam_write_device: lift tables of pass " + std::to_string(p) + " are malformed");
-        At& a = at[(size_t)p];
-        a.lo = b8.size(); b8.insert(b8.end(), in.cds_lo, in.cds_lo + n_seg);
-        a.hi = b8.size(); b8.insert(b8.end(), in.cds_hi, in.cds_hi + n_seg);
-        a.chrom = b4.size(); for (int64_t r = 0; r < in.n_refs; r++) b4.push_back((uint32_t)in.chrom_of_ref[r]);
-        a.ptr = b4.size(); for (int64_t r = 0; r <= in.n_refs; r++) b4.push_back(in.n_refs ? (uint32_t)in.seg_ptr[r] : 0u);
-        a.s = b4.size(); for (int64_t s = 0; s < n_seg; s++) b4.push_back((uint32_t)in.seg_s[s]);
-        a.e = b4.size(); for (int64_t s = 0; s < n_seg; s++) b4.push_back((uint32_t)in.seg_e[s]);
-        a.coff = b4.size(); for (int64_t k = 0; k <= in.n_chrom; k++) b4.push_back(in.n_chrom ? (uint32_t)(in.chrom_off[k] - in.chrom_off[0]) : 0u);
-        a.minus = b1.size(); b1.insert(b1.end(), in.minus, in.minus + in.n_refs);
-        a.cdata = b1.size();
-        if (n_cb) b1.insert(b1.end(), (const uint8_t*)in.chrom_data + in.chrom_off[0], (const uint8_t*)in.chrom_data + in.chrom_off[0] + n_cb);
-        sp.T = in.lib->dT; sp.inv = in.lib->dinv; sp.ref_start = in.lib->dref_start;
-        sp.n_refs = (uint32_t)in.n_refs; sp.n_chrom = (uint32_t)in.n_chrom; sp.trim5 = in.trim5; sp.trim3 = in.trim3;
-    }
-    const size_t bytes8 = b8.size() * 8, bytes4 = b4.size() * 4, bytesP = hp.size() * sizeof(SamPass);
-    const size_t o4 = bytes8, o1 = o4 + bytes4, oP = (o1 + b1.size() + 15) & ~size_t(15), blob_bytes = oP + bytesP;
-    std::vector<uint8_t> blob(blob_bytes, 0);
-    if (bytes8) std::memcpy(blob.data(), b8.data(), bytes8);
-    if (bytes4) std::memcpy(blob.data() + o4, b4.data(), bytes4);
-    if (!b1.empty()) std::memcpy(blob.data() + o1, b1.data(), b1.size());
-    // ---- sizes of the chunked output
-    size_t tile = sam_env_bytes("MIRGE_SAM_TILE_BYTES", 8160);  // 255 probe points of 32 bytes + the one behind the tile's end: one per thread
-    tile = std::min<size_t>(MIRGE_SAM_MAX_TILE, std::max<size_t>(64, tile)) & ~size_t(15);
-    size_t chunk = sam_env_bytes("MIRGE_SAM_CHUNK_BYTES", (size_t)32 << 20);
-    chunk = std::min<size_t>((size_t)1 << 30, std::max(chunk, tile)) / tile * tile;
-
-    uint8_t *d_blob = nullptr, *d_text[2] = {nullptr, nullptr};
-    uint32_t *d_order = nullptr, *d_keep = nullptr, *d_pos = nullptr, *d_rows = nullptr, *d_fixed = nullptr, *d_flags = nullptr;
-    unsigned long long *d_total = nullptr, *d_off = nullptr, *d_nlines = nullptr;
+// What `--sam-out` and `--sorted-bam` share: the passes' lift tables on the device (ONE blob: 8-byte items first, then 4-byte, then
+// bytes) and the file's rows in class order (k_sam_select, one scan, k_sam_rows).  build() leaves the stream synchronised.
+struct SamPrep {
+    uint8_t* d_blob = nullptr;
+    uint32_t *d_order = nullptr, *d_keep = nullptr, *d_pos = nullptr, *d_rows = nullptr, *d_flags = nullptr;
     void* tmp = nullptr;
-    int rc = 0, fd = -1;
-    int64_t n_lines = 0, n_bytes = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    do {
+    size_t tb = 0, n_rows = 0;
+    SamTables t;
+    int build(mirge_ctx* c, const std::string& who, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+              const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass) {
+        if (!c || !U || !res || (U->n && !order) || !class_pass || n_class < 1 || n_class > MIRGE_SAM_NCLASS || !passes || n_pass < 1 ||
+            n_pass > MIRGE_MAX_PASSES || n_pass < res->n_pass || U->n_samples < 1 || sample < 0 || sample >= U->n_samples || res->n != U->n)
+            return fail(-1, who + ": bad argument");
+        // hipCUB's scans take an `int` item count, and the flag array holds one entry per class and frame row
+        if ((unsigned long long)U->n * MIRGE_SAM_NCLASS >= 0x7FFFFFF0ull) return fail(-5, who + ": too many unique reads for one call");
+        for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
+            if (U->g[gi].n && U->g[gi].orig) return fail(-1, who + ": the read set is not a collapse result");
+            if (U->g[gi].n != res->g[gi].n && !res->dmeta) return fail(-1, who + ": result and read set differ");
+        }
+        const size_t n = (size_t)U->n;
+        std::vector<SamPass> hp((size_t)n_pass);
+        std::memset(hp.data(), 0, hp.size() * sizeof(SamPass));
+        std::vector<long long> b8;
+        std::vector<uint32_t> b4;
+        std::vector<uint8_t> b1;
+        struct At { size_t lo, hi, chrom, minus, ptr, s, e, coff, cdata; };
+        std::vector<At> at((size_t)n_pass);
+        for (int p = 0; p < n_pass; p++) hp[(size_t)p].cls = -1;
+        for (int k = 0; k < n_class; k++) {
+            const int32_t p = class_pass[k];
+            if (p < 0 || p >= n_pass || hp[(size_t)p].cls >= 0) return fail(-1, who + ": class order names a pass twice or out of range");
+            hp[(size_t)p].cls = k;
+        }
+        for (int p = 0; p < n_pass; p++) {
+            SamPass& sp = hp[(size_t)p];
+            if (sp.cls < 0) continue;
+            const mirge_sam_pass& in = passes[p];
+            if (!in.lib || in.n_refs != in.lib->n_refs || in.n_refs < 0 || in.n_refs >= 0x7FFFFFF0ll || in.trim5 < 0 || in.trim3 < 0 ||
+                in.n_chrom < 0 || (in.n_refs && (!in.chrom_of_ref || !in.minus || !in.seg_ptr)) || (in.n_chrom && (!in.chrom_off || !in.chrom_data)))
+                return fail(-1, who + ": lift tables of pass " + std::to_string(p) + " do not fit its library");
+            const int64_t n_seg = in.n_refs ? in.seg_ptr[in.n_refs] : 0;
+            const int64_t n_cb = in.n_chrom ? in.chrom_off[in.n_chrom] - in.chrom_off[0] : 0;
+            if (n_seg < 0 || n_seg >= 0x7FFFFFF0ll || n_cb < 0 || n_cb >= 0x7FFFFFF0ll || in.n_chrom >= 0x7FFFFFF0ll ||
+                (n_seg && (!in.seg_s || !in.seg_e || !in.cds_lo || !in.cds_hi)))
+                return fail(-1, who + ": lift tables of pass " + std::to_string(p) + " are malformed");
+            for (int64_t r = 0; r < in.n_refs; r++)
+                if (in.seg_ptr[r] < 0 || in.seg_ptr[r + 1] < in.seg_ptr[r] || in.chrom_of_ref[r] >= in.n_chrom)
+                    return fail(-1, who + ": lift tables of pass " + std::to_string(p) + " are malformed");
+            At& a = at[(size_t)p];
+            a.lo = b8.size(); b8.insert(b8.end(), in.cds_lo, in.cds_lo + n_seg);
+            a.hi = b8.size(); b8.insert(b8.end(), in.cds_hi, in.cds_hi + n_seg);
+            a.chrom = b4.size(); for (int64_t r = 0; r < in.n_refs; r++) b4.push_back((uint32_t)in.chrom_of_ref[r]);
+            a.ptr = b4.size(); for (int64_t r = 0; r <= in.n_refs; r++) b4.push_back(in.n_refs ? (uint32_t)in.seg_ptr[r] : 0u);
+            a.s = b4.size(); for (int64_t s = 0; s < n_seg; s++) b4.push_back((uint32_t)in.seg_s[s]);
+            a.e = b4.size(); for (int64_t s = 0; s < n_seg; s++) b4.push_back((uint32_t)in.seg_e[s]);
+            a.coff = b4.size(); for (int64_t k = 0; k <= in.n_chrom; k++) b4.push_back(in.n_chrom ? (uint32_t)(in.chrom_off[k] - in.chrom_off[0]) : 0u);
+            a.minus = b1.size(); b1.insert(b1.end(), in.minus, in.minus + in.n_refs);
+            a.cdata = b1.size();
+            if (n_cb) b1.insert(b1.end(), (const uint8_t*)in.chrom_data + in.chrom_off[0], (const uint8_t*)in.chrom_data + in.chrom_off[0] + n_cb);
+            sp.T = in.lib->dT; sp.inv = in.lib->dinv; sp.ref_start = in.lib->dref_start;
+            sp.n_refs = (uint32_t)in.n_refs; sp.n_chrom = (uint32_t)in.n_chrom; sp.trim5 = in.trim5; sp.trim3 = in.trim3;
+        }
+        const size_t bytes8 = b8.size() * 8, bytes4 = b4.size() * 4, bytesP = hp.size() * sizeof(SamPass);
+        const size_t o4 = bytes8, o1 = o4 + bytes4, oP = (o1 + b1.size() + 15) & ~size_t(15), blob_bytes = oP + bytesP;
+        std::vector<uint8_t> blob(blob_bytes, 0);
+        if (bytes8) std::memcpy(blob.data(), b8.data(), bytes8);
+        if (bytes4) std::memcpy(blob.data() + o4, b4.data(), bytes4);
+        if (!b1.empty()) std::memcpy(blob.data() + o1, b1.data(), b1.size());
+        int rc = 0;
         const size_t nf = n * MIRGE_SAM_NCLASS;
         std::vector<uint32_t> o32(std::max<size_t>(n, 1));
         for (size_t k = 0; k < n; k++) {
-            if (order[k] < 0 || order[k] >= U->n) { rc = fail(-1, "mirge_sam_write_device: row index out of range"); break; }
+            if (order[k] < 0 || order[k] >= U->n) return fail(-1, who + ": row index out of range");
             o32[k] = (uint32_t)order[k];
         }
-        if (rc) break;
-        if ((rc = dalloc(c, &d_blob, blob_bytes + 16))) break;
-        if ((rc = dalloc(c, &d_order, std::max<size_t>(n, 1)))) break;
-        if ((rc = dalloc(c, &d_keep, nf + 1))) break;
-        if ((rc = dalloc(c, &d_pos, nf + 1))) break;
-        if ((rc = dalloc(c, &d_flags, 16))) break;
-        if ((rc = dalloc(c, &d_nlines, 2))) break;
-        SamTables t;
+        if ((rc = dalloc(c, &d_blob, blob_bytes + 16))) return rc;
+        if ((rc = dalloc(c, &d_order, std::max<size_t>(n, 1)))) return rc;
+        if ((rc = dalloc(c, &d_keep, nf + 1))) return rc;
+        if ((rc = dalloc(c, &d_pos, nf + 1))) return rc;
+        if ((rc = dalloc(c, &d_flags, 16))) return rc;
         std::memset(&t, 0, sizeof(t));
         t.n_pass = n_pass; t.S = U->n_samples; t.sample = sample;
         for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
@@ -137,41 +123,75 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
         if (e == hipSuccess && n) e = hipMemcpyAsync(d_order, o32.data(), n * 4, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_keep, 0, (nf + 1) * 4, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 64, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_nlines, 0, 16, c->stream);
-        if (e != hipSuccess) { rc = fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e)); break; }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(-2, who + ": " + hipGetErrorString(e)); }
         // ---- the file's rows, in class order
         if (n) {
             LaunchScope ls(c, "k_sam_select", (double)n);
             hipLaunchKernelGGL(k_sam_select, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_order, (uint32_t)n, d_keep, d_flags);
         }
-        size_t tb = 0;
         e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_keep, d_pos, (int)(nf + 1), c->stream);
-        if (e == hipSuccess && (rc = dalloc(c, (uint8_t**)&tmp, std::max<size_t>(tb, 16)))) break;
+        if (e == hipSuccess && (rc = dalloc(c, (uint8_t**)&tmp, std::max<size_t>(tb, 16)))) { (void)hipStreamSynchronize(c->stream); return rc; }
         if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, d_keep, d_pos, (int)(nf + 1), c->stream);
         uint32_t n_rows32 = 0, hflag = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&n_rows32, d_pos + nf, 4, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&hflag, d_flags, 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e)); break; }
-        if (hflag) { rc = fail(-1, "mirge_sam_write_device: pass, reference or offset out of range"); break; }
-        const size_t n_rows = n_rows32;
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // (also when a call failed: the host vectors above leave scope)
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(-2, who + ": " + hipGetErrorString(e));
+        if (hflag) return fail(-1, who + ": pass, reference or offset out of range");
+        n_rows = n_rows32;
+        if ((rc = dalloc(c, &d_rows, std::max<size_t>(n_rows, 1)))) return rc;
+        if (n_rows)
+            hipLaunchKernelGGL(k_sam_rows, dim3(grid_for(c, nf)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_order, (uint32_t)n, (const uint32_t*)d_keep,
+                               (const uint32_t*)d_pos, d_rows);
+        return 0;
+    }
+    void release(mirge_ctx* c) {
+        c->release(d_blob); c->release(d_order); c->release(d_keep); c->release(d_pos); c->release(d_rows); c->release(d_flags); c->release(tmp);
+    }
+};
+
+extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                                      const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                      const char* path, const char* header, int64_t header_len, int64_t* n_lines_out,
+                                      int64_t* n_bytes_out) {
+    if (!c || !path || (!header && header_len) || header_len < 0) return fail(-1, "mirge_sam_write_device: bad argument");
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    HostClock hc("sam_write_device");
+    // ---- sizes of the chunked output
+    size_t tile = sam_env_bytes("MIRGE_SAM_TILE_BYTES", 8160);  // 255 probe points of 32 bytes + the one behind the tile's end: one per thread
+    tile = std::min<size_t>(MIRGE_SAM_MAX_TILE, std::max<size_t>(64, tile)) & ~size_t(15);
+    size_t chunk = sam_env_bytes("MIRGE_SAM_CHUNK_BYTES", (size_t)32 << 20);
+    chunk = std::min<size_t>((size_t)1 << 30, std::max(chunk, tile)) / tile * tile;
+
+    SamPrep prep;
+    uint8_t* d_text[2] = {nullptr, nullptr};
+    uint32_t* d_fixed = nullptr;
+    unsigned long long *d_total = nullptr, *d_off = nullptr, *d_nlines = nullptr;
+    int rc = 0, fd = -1;
+    int64_t n_lines = 0, n_bytes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    do {
+        if ((rc = prep.build(c, "mirge_sam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
+        const SamTables& t = prep.t;
+        uint32_t* const d_rows = prep.d_rows;
+        const size_t n_rows = prep.n_rows;
         hc.lap("rows chosen");
-        if ((rc = dalloc(c, &d_rows, std::max<size_t>(n_rows, 1)))) break;
+        if ((rc = dalloc(c, &d_nlines, 2))) break;
         if ((rc = dalloc(c, &d_fixed, std::max<size_t>(n_rows, 1)))) break;
         if ((rc = dalloc(c, &d_total, n_rows + 1))) break;
         if ((rc = dalloc(c, &d_off, n_rows + 1))) break;
-        e = hipMemsetAsync(d_total + n_rows, 0, 8, c->stream);
+        hipError_t e = hipMemsetAsync(d_total + n_rows, 0, 8, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_nlines, 0, 16, c->stream);
         if (e == hipSuccess && n_rows) {
-            hipLaunchKernelGGL(k_sam_rows, dim3(grid_for(c, nf)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_order, (uint32_t)n, (const uint32_t*)d_keep,
-                               (const uint32_t*)d_pos, d_rows);
             LaunchScope ls(c, "k_sam_measure", (double)n_rows);
             hipLaunchKernelGGL(k_sam_measure, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n_rows, d_fixed,
                                d_total, d_nlines);
         }
         size_t tb2 = 0;
         if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, d_total, d_off, (int)(n_rows + 1), c->stream);
-        if (e == hipSuccess && tb2 > tb) { c->release(tmp); tmp = nullptr; if ((rc = dalloc(c, (uint8_t**)&tmp, tb2))) break; }
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb2, d_total, d_off, (int)(n_rows + 1), c->stream);
+        if (e == hipSuccess && tb2 > prep.tb) { c->release(prep.tmp); prep.tmp = nullptr; if ((rc = dalloc(c, (uint8_t**)&prep.tmp, tb2))) break; }
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(prep.tmp, tb2, d_total, d_off, (int)(n_rows + 1), c->stream);
         unsigned long long body = 0, lines = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&body, d_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&lines, d_nlines, 8, hipMemcpyDeviceToHost, c->stream);
@@ -239,8 +259,8 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     }
     if (rc != 0 && regular) (void)::unlink(path);  // never a partial file that looks like a result
     for (auto& x : ev) if (x) c->evt_pool.push_back(x);
-    c->release(d_blob); c->release(d_text[0]); c->release(d_text[1]); c->release(d_order); c->release(d_keep); c->release(d_pos); c->release(d_rows);
-    c->release(d_fixed); c->release(d_flags); c->release(d_total); c->release(d_off); c->release(d_nlines); c->release(tmp);
+    prep.release(c);
+    c->release(d_text[0]); c->release(d_text[1]); c->release(d_fixed); c->release(d_total); c->release(d_off); c->release(d_nlines);
     if (rc == 0) {
         if (n_lines_out) *n_lines_out = n_lines;
         if (n_bytes_out) *n_bytes_out = n_bytes;

@@ -318,6 +318,11 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
             raise RuntimeError("--sam-out needs the cascade's result on the device (a single-process run)")
         from . import sam_export as _sam_export
         out["sam_out"] = _sam_export.run(args, workDir, base_names, casc, uniq, res, order, tm)
+    if getattr(args, "sorted_bam", False):  # --sorted-bam: <sample>_sorted.bam / .bai, the same records sorted (bamFmt.py:173-205)
+        if ann is not None or res is None:
+            raise RuntimeError("--sorted-bam needs the cascade's result on the device (a single-process run)")
+        from . import bam_export as _bam_export
+        out["sorted_bam"] = _bam_export.run(args, workDir, base_names, casc, uniq, res, order, tm)
     if getattr(args, "isoform_entropy", False):  # -ie reads the miRNA rows of the mapped frame: build just those
         from .countjoin import isomir_entropy_tables
         isomir_entropy_tables(mirna_frame(seqs, ps, ref, counts, order, casc, base_names), base_names, out["filtered"], workDir)

@@ -10,7 +10,7 @@ the lines are chosen, measured and formatted there, one call per sample (``csrc/
 
 What stays in Python is per REFERENCE, not per read: the header lines' coordinates as flat tables (``lift_tables``).
 ``format_sam_host`` restates the whole file format slowly on host arrays; it is what the tests compare the device with, not
-a route of the product.  BAM, sorting and indexing stay out of scope: ``-bam`` is still refused.
+a route of the product.  The same records as a sorted, indexed BAM: ``bam_export`` (``--sorted-bam``); ``-bam`` is still refused.
 """
 from __future__ import annotations
 

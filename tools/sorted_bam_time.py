@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Time ``--sorted-bam``'s device call (``mirge_bam_write_device``) on the two synthetic samples of ``tools/sam_out_time.py`` -- Zipf
+counts over a few hundred thousand unique reads, and all-distinct -- of ``--reads`` raw reads.  Per shape three calls are interleaved
+round by round (after one unrecorded warm-up round, which pays for the staging buffers and the lift tables): the device deflate, the
+``MIRGE_BAM_DEFLATE=host`` route (zlib level 6 on ``--threads`` host threads: the same blocks, so its file size is zlib's on them) and
+``--sam-out``'s call on the same build, the closest existing work.  Reported: median, min and max seconds of ``--repeats`` rounds,
+stream bytes, file bytes of both routes.
+
+  python tools/sorted_bam_time.py --reads 10000000 --repeats 7 --out profiles/sorted_bam_time.txt
+"""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.abspath(os.path.dirname(__file__)))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+import mirge3_amd  # noqa: E402,F401
+from mirge3_amd import _ffi, bam_export, sam_export  # noqa: E402
+from mirge3_amd.cascade import Cascade  # noqa: E402
+from mirge3_amd.seqio import FlatSeqs  # noqa: E402
+from sam_out_time import libraries, unique_reads  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=10_000_000)
+    ap.add_argument("--zipf-unique", type=int, default=300_000)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rng = np.random.Generator(np.random.PCG64(5))
+    libs = libraries(rng)
+    header = ("@HD\tVN:1.0\n" + "".join(f"@SQ\tSN:chr{k}\tLN:{1 << 28}\n" for k in range(1, 23))).encode()
+    ctx = _ffi.Context(0)
+    casc = Cascade(ctx, libs)
+    report = []
+    for shape in ("zipf", "distinct"):
+        n_u = a.zipf_unique if shape == "zipf" else a.reads
+        reads = unique_reads(rng, libs, n_u)
+        if shape == "zipf":
+            w = 1.0 / np.arange(1, n_u + 1) ** 1.1
+            cnt = np.maximum(1, np.floor(w / w.sum() * a.reads)).astype(np.uint32)
+            rng.shuffle(cnt)
+        else:
+            cnt = np.ones(n_u, dtype=np.uint32)
+        raw = _ffi.DeviceReads.pack(ctx, FlatSeqs.from_list(reads))
+        uniq = raw.collapse(None, 1, weights=cnt)
+        raw.close()
+        res = casc.run(uniq)
+        order = uniq.first_appearance_order()
+        ctx.sync()
+        tmp = tempfile.mkdtemp(prefix="sorted_bam_time_")
+        bam, bai, sam = (os.path.join(tmp, f) for f in ("S1_sorted.bam", "S1_sorted.bai", "S1.sam"))
+        ts = {"device": [], "host": [], "sam_out": []}
+        line = {"shape": shape, "unique_reads": len(uniq), "threads": a.threads}
+        for rnd in range(a.repeats + 1):
+            for route in ("device", "host", "sam_out"):
+                os.environ.pop("MIRGE_BAM_DEFLATE", None)
+                if route == "host":
+                    os.environ["MIRGE_BAM_DEFLATE"] = "host"
+                t0 = time.perf_counter()
+                if route == "sam_out":
+                    _, n_text = sam_export.write_sample(casc, uniq, res, order, 0, sam, sam_export.DEFAULT_HEADER, "synthorg")
+                    line["sam_text_bytes"] = n_text
+                else:
+                    n_rec, n_stream, n_file = bam_export.write_sample(casc, uniq, res, order, 0, bam, bai, header, "synthorg", threads=a.threads)
+                    line.update({"records": n_rec, "stream_bytes": n_stream, route + "_file_bytes": n_file, "bai_bytes": os.path.getsize(bai)})
+                if rnd:
+                    ts[route].append(time.perf_counter() - t0)
+        os.environ.pop("MIRGE_BAM_DEFLATE", None)
+        for route, v in ts.items():
+            line.update({route + "_median_s": round(statistics.median(v), 4), route + "_min_s": round(min(v), 4), route + "_max_s": round(max(v), 4)})
+        line["device_over_zlib6_size"] = round(line["device_file_bytes"] / line["host_file_bytes"], 3)
+        for f in (bam, bai, sam):
+            os.remove(f)
+        os.rmdir(tmp)
+        res.close(); uniq.close()
+        report.append(line)
+        print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            for line in report:
+                fh.write(repr(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
