@@ -13,6 +13,10 @@
 #include <mutex>
 #include <condition_variable>
 #include <atomic>
+#include <climits>
+#include <linux/futex.h>
+#include <sys/syscall.h>
+#include <unistd.h>
 #define __device__
 #define __host__
 #define __global__
@@ -23,8 +27,18 @@
 struct D3 { unsigned x; };
 static thread_local D3 threadIdx;
 static D3 blockIdx, blockDim, gridDim;
-struct Barrier { std::mutex m; std::condition_variable cv; int n, count = 0, gen = 0;
-  void wait() { std::unique_lock<std::mutex> l(m); int g = gen; if (++count == n) { gen++; count = 0; cv.notify_all(); } else cv.wait(l, [&]{ return g != gen; }); } };
+// (a futex on the generation: the 255 threads the last one wakes do not queue for a mutex again, which is what a block of 64 bytes'
+// eight barriers cost when thousands of blocks go through tests/test_bam_deflate_hostsim.py)
+struct Barrier { int n = 0; std::atomic<int> count{0}; std::atomic<int> gen{0};
+  void wait() {
+    static_assert(sizeof(std::atomic<int>) == sizeof(int), "the futex word");
+    const int g = gen.load(std::memory_order_acquire);
+    if (count.fetch_add(1, std::memory_order_acq_rel) + 1 == n) {
+      count.store(0, std::memory_order_relaxed); gen.store(g + 1, std::memory_order_release);
+      syscall(SYS_futex, reinterpret_cast<int*>(&gen), FUTEX_WAKE_PRIVATE, INT32_MAX, nullptr, nullptr, 0);
+    } else
+      while (gen.load(std::memory_order_acquire) == g) syscall(SYS_futex, reinterpret_cast<int*>(&gen), FUTEX_WAIT_PRIVATE, g, nullptr, nullptr, 0);
+  } };
 static Barrier* g_bar;
 static void __syncthreads() { g_bar->wait(); }
 struct uint4 { uint32_t x, y, z, w; };

@@ -40,6 +40,20 @@ def golden_header():
     return ("@HD\tVN:1.0\tSO:unsorted\n" + "".join(f"@SQ\tSN:{nm}\tLN:{(1 << 29) - k}\n" for k, nm in enumerate(names)) + "@CO\tgolden\n").encode(), names
 
 
+# (block size, what the stream's header bytes H leave modulo it).  k_bam_blocks hands a record to the first 32-byte probe point at or
+# behind its start, and the header's end is where that rule begins: at block 256 H takes every residue modulo the probe distance 32, and
+# modulo 256 the residues 0, 1 and 255 with them; at block 64 the header is longer than two blocks and ends inside a probe's stretch
+HEADER_CASES = [(256, {0: 0, 1: 1, 31: 255}.get(r, r + 32 * (r % 8))) for r in range(32)] + [(64, 37)]
+
+
+def header_of_length(header: bytes, block: int, want: int) -> bytes:
+    """header with one more @CO line, padded so that the stream's header bytes (header_blob) leave `want` modulo block"""
+    base = len(bam_export.header_blob(header + b"@CO\t\n")[0])
+    out = header + b"@CO\t" + b"p" * ((want - base) % block + (2 * block if block == 64 else 0)) + b"\n"
+    assert len(bam_export.header_blob(out)[0]) % block == want and (block != 64 or len(bam_export.header_blob(out)[0]) > 2 * block)
+    return out
+
+
 def expected_lines(body: bytes, names):
     refid_of = {nm: k for k, nm in enumerate(names)}
     lines = [ln for ln in body.decode().split("\n") if ln]

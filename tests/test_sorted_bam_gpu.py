@@ -1,7 +1,8 @@
 """``--sorted-bam`` on the GPU: the golden run through the CLI (tests/golden/sam_out: the reference's own files) with the device deflate
 and with ``MIRGE_BAM_DEFLATE=host``, and without the switch; ``mirge_bam_write_device`` against ``bam_export.format_bam_host`` on a few
 hundred unique reads with a row of 1500 copies, ties, positions around the bin boundaries and an N, at block sizes 256, 4096 and the
-default; a sample of all-distinct reads for the stored fallback.  Files are read back through tests/bam_reader.py."""
+default, and at header lengths of every residue modulo the probe distance; a sample of all-distinct reads, which needs no stored
+block (the stored fallback itself: tests/test_bam_deflate_gpu.py).  Files are read back through tests/bam_reader.py."""
 import os
 
 import numpy as np
@@ -15,7 +16,7 @@ from mirge3_amd.seqio import FlatSeqs, Library
 import bam_reader
 from test_sam_out import GOLDEN, ORG, golden_inputs
 from test_sam_out_gpu import OTHER_OUTPUTS, _cli, _fuzz_reads, _rnd
-from test_sorted_bam import expected_lines, golden_bodies, golden_header
+from test_sorted_bam import HEADER_CASES, expected_lines, golden_bodies, golden_header, header_of_length
 
 pytestmark = pytest.mark.gpu
 
@@ -194,6 +195,26 @@ def test_device_equals_format_bam_host(fuzz_case, block, route, tmp_path, monkey
             assert d["block"] == block
         if route == "device" and block != 256 and s == 0:  # 1500 copies of one record: matches, not literals
             assert n_file < n_stream // 2, (n_file, n_stream)
+
+
+@pytest.mark.parametrize("block,want", HEADER_CASES, ids=[f"block{b}_H{w}" for b, w in HEADER_CASES])
+def test_header_length_against_the_records(fuzz_case, block, want, tmp_path, monkeypatch):
+    """where the header ends inside a block and inside a probe's 32 bytes decides which probe writes the first records"""
+    for var in ("MIRGE_BAM_BLOCK_BYTES", "MIRGE_BAM_CHUNK_BLOCKS", "MIRGE_BAM_DEFLATE"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv("MIRGE_BAM_BLOCK_BYTES", str(block))
+    f = fuzz_case
+    header = header_of_length(f["header"], block, want)
+    H = len(bam_export.header_blob(header)[0])
+    assert H % block == want and (block != 256 or H % 32 == want % 32)
+    for s in range(f["S"]):
+        bam_path, bai_path = tmp_path / f"S{s}_sorted.bam", tmp_path / f"S{s}_sorted.bai"
+        n_rec, n_stream, n_file = bam_export.write_sample(f["casc"], f["uniq"], f["res"], f["order"], s, bam_path, bai_path, header, ORG, threads=4)
+        host_bam, _ = bam_export.format_bam_host(f["bodies"][s], header, block_bytes=block)
+        want_lines = expected_lines(f["bodies"][s], f["names"])
+        d = check_file(bam_path.read_bytes(), bai_path.read_bytes(), len(f["names"]), want_lines, host_bam)
+        assert d["block"] == block and n_rec == len(want_lines) and n_file == os.path.getsize(bam_path)
+        assert n_stream == sum(len(m["payload"]) for m in d["members"]) > H
 
 
 def test_device_errors_name_the_chromosome_and_write_nothing(fuzz_case, tmp_path):

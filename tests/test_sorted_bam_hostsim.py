@@ -1,8 +1,10 @@
 """The ``--sorted-bam`` kernels on the CPU: ``csrc/kernels_bam.hpp`` itself, compiled for the host (tests/hostsim/bam_sim.cpp: a
 workgroup's threads are std::threads behind a barrier).  The kernels use no wave-level steps, so not only the uncompressed stream
-(block sizes 256 and 4096, against ``format_bam_host``) but also the LDS deflate, its bit offsets, the stored fallback's decision and
-the CRC-32 combination run here: the members are inflated and checked by tests/bam_reader.py.  Inputs: the golden case of
-tests/golden/sam_out, one row raised to 1234 copies so that digit bands 1 to 4 occur and one row spans many blocks."""
+(block sizes 256 and 4096, against ``format_bam_host``; header lengths of every residue modulo the probe distance) but also the LDS
+deflate, its bit offsets and the CRC-32 combination run here: the members are inflated and checked by tests/bam_reader.py.  Inputs:
+the golden case of tests/golden/sam_out, one row raised to 1234 copies so that digit bands 1 to 4 occur and one row spans many blocks.
+Records always shrink, so every member here is a fixed-Huffman block: the stored fallback and the edge of its decision, 9-bit literals
+and every length and distance code run in tests/test_bam_deflate_hostsim.py, on payloads that records cannot produce."""
 import ctypes as C
 import os
 import subprocess
@@ -18,7 +20,7 @@ from mirge3_amd.seqio import FlatSeqs
 import bam_reader
 from test_sam_out import ORG, golden_inputs, host_passes_of
 from test_sam_out_hostsim import SP, _oracle_annotation, pack_lib, pack_reads
-from test_sorted_bam import expected_lines, golden_header
+from test_sorted_bam import HEADER_CASES, expected_lines, golden_header, header_of_length
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostsim", "bam_sim.cpp")
@@ -93,6 +95,20 @@ def test_uncompressed_stream_equals_format_bam_host(case, block):
         want = b"".join(m["payload"] for m in bam_reader.read_bgzf(bam))
         assert stream == want, s
         assert n_rec == body.count(b"\n")
+
+
+@pytest.mark.parametrize("block,want", HEADER_CASES, ids=[f"block{b}_H{w}" for b, w in HEADER_CASES])
+def test_header_length_against_the_records(case, block, want):
+    """where the header ends inside a block and inside a probe's 32 bytes decides which probe writes the first records (the sample
+    without the 1234-copy row: a few blocks each)"""
+    header = header_of_length(case["header"], block, want)
+    H = len(bam_export.header_blob(header)[0])
+    assert H % block == want and (block != 256 or H % 32 == want % 32)
+    body = case["bodies"][1]
+    stream, n_rec = run(case["libs"], case["seqs"], *case["ann"], case["counts"], case["order"], 1, header, block, 0)
+    bam, _ = bam_export.format_bam_host(body, header, block_bytes=block)
+    assert stream == b"".join(m["payload"] for m in bam_reader.read_bgzf(bam))
+    assert n_rec == body.count(b"\n") > 20 and len(stream) > H + 4 * block
 
 
 @pytest.mark.parametrize("block", [256, 4096, 65280])
