@@ -541,7 +541,7 @@ class DeviceReads:
         return load().mirge_reads_n_samples(self._h)
 
     def group_counts(self) -> np.ndarray:
-        """reads per storage group: width classes (1, 2, 4, 8 words) without an ambiguous call, then the same with an N"""
+        """reads per storage group: width classes (up to 31, 64, 128, 255 nt, longer) without an ambiguous call, then the same with an N"""
         out = np.zeros(16, dtype=np.int64)
         n = load().mirge_reads_group_counts(self._h, _p(out), C.c_int32(16))
         return out[:n]

@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MIRGE_I
             pi = tb.pre_of_master[mi];
             p0 = tb.pre_off[pi]; lp = tb.pre_off[pi + 1] - p0;
         }
-        if (MIRGE_ISO_FAST && fast && typed && la <= MIRGE_ISO_MAXA) {  // everything in registers (mirge_isotype_fast)
+        if (MIRGE_ISO_FAST && fast && typed && la <= MIRGE_ISO_FAST_MAXA) {  // everything in registers (mirge_isotype_fast)
             mirge_iso::Seq qa, qb;
             iso_seq_of_read<W>(r, qb);
             if (mirge_iso::seq_of_ascii(tb.master + a0, la, qa)) {

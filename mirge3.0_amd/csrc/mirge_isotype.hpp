@@ -26,7 +26,8 @@
 #endif
 #endif
 
-#define MIRGE_ISO_MAXA 40                                  // canonical miRNA, nt
+#define MIRGE_ISO_MAXA 48                                  // canonical miRNA, nt (a longer one is refused by the callers: iso_device_tables)
+#define MIRGE_ISO_FAST_MAXA 40                             // ... of the register form (mirge_isotype_fast); a longer canonical goes through the array form
 #define MIRGE_ISO_MAXB 64                                  // read, nt
 #define MIRGE_ISO_MAXN (MIRGE_ISO_MAXA + MIRGE_ISO_MAXB)   // aligned columns
 #define MIRGE_ISO_TEXT 320                                 // variant + cigar bytes of one record
@@ -444,7 +445,7 @@ MIRGE_HD bool mirge_isotype_fast(const mirge_iso::Seq& a, const mirge_iso::Seq& 
                                  int32_t* o_start, int32_t* o_end, uint8_t* o_kind, uint16_t* o_vlen, uint16_t* o_clen, char* text) {
     using namespace mirge_iso;
     const int la = a.n, lb = b.n;
-    if (la > MIRGE_ISO_MAXA || lb > MIRGE_ISO_MAXB || la + lb > 64 || la < 1 || lb < 1) return false;
+    if (la > MIRGE_ISO_FAST_MAXA || lb > MIRGE_ISO_MAXB || la + lb > 64 || la < 1 || lb < 1) return false;
     int start = start0, end = start0 + la - 1;
     TextOut o;
     o.t = text; o.at = 0; o.last = 0;

@@ -66,6 +66,10 @@ static int iso_device_tables(mirge_ctx* c, IsoDevice& dv, const mirge_reads* U, 
                              const int32_t* pre_off, int64_t n_pre, int64_t n_rows) {
     int32_t*& d_mof = dv.d_mof; int32_t*& d_moff = dv.d_moff; int32_t*& d_pom = dv.d_pom; int32_t*& d_s0 = dv.d_s0; int32_t*& d_poff = dv.d_poff;
     int32_t*& d_slot = dv.d_slot; char*& d_m = dv.d_m; char*& d_p = dv.d_p; MirgeIsoRec*& d_out = dv.d_out;
+    // k_isotype leaves the rows of a longer canonical untyped, and an untyped row has no line in the GFF3: said here, not found later
+    for (int64_t m = 0; m < n_master; m++)
+        if (master_off[m + 1] - master_off[m] > MIRGE_ISO_MAXA)
+            return fail(-5, "isomiR typing: canonical sequence " + std::to_string(m) + " is longer than " + std::to_string(MIRGE_ISO_MAXA) + " nt");
     const size_t nm = (size_t)std::max<int64_t>(n_master, 1), np = (size_t)std::max<int64_t>(n_pre, 1);
     const size_t mbytes = (size_t)std::max<int32_t>(master_off[n_master], 1), pbytes = (size_t)std::max<int32_t>(pre_off[n_pre], 1);
     CHECK(dalloc(c, &d_mof, (size_t)std::max<int64_t>(n_mirna, 1)));

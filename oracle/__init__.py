@@ -642,6 +642,61 @@ def gff_record(master: str, read: str, precursor: str):
 
 
 # --------------------------------------------------------------------------------------
+# One whole line of the miRTop GFF3, restated from create_gff (mirge/libs/summary.py:131-192, :465-492) and from
+# miRgeEssential.UID (:364-370).  The reference looks every 1..5-mer up in a 1364-entry table; the table is a numbering,
+# and gff_uid computes the number instead.  PINNED against the file the reference wrote and against the UIDs its own
+# function returned (tests/golden/case4_gff_a2i, case6_gff_a2i: sample_miRge3.gff, a2i_direct.json).
+# --------------------------------------------------------------------------------------
+UID_SYMBOLS = "BD0EF1HI2JK3LM4NO5PQ6RS7UV8WX9YZ"
+
+
+def gff_uid(seq: str, prefix: str) -> str:
+    """miRgeEssential.UID: ``prefix-len-`` and then, for every stretch of five bases, its value as a base-4 number (A C G T
+    = 0..3, the first base the most significant digit) written as two base-32 digits in UID_SYMBOLS.  A last stretch of
+    k < 5 bases is numbered behind all shorter stretches (k = 1: 0..3, k = 2: 4..19, k = 3: 20..83, k = 4: 84..339) and
+    takes one digit while its number is below 32, two from there on."""
+    out = [prefix, "-", str(len(seq)), "-"]
+    for at in range(0, len(seq), 5):
+        piece = seq[at:at + 5]
+        value = 0
+        for base in piece:
+            value = 4 * value + "ACGT".index(base)
+        if len(piece) < 5:
+            value += sum(4 ** k for k in range(1, len(piece)))  # how many stretches are shorter than this one
+        hi, lo = divmod(value, 32)
+        out.append(UID_SYMBOLS[lo] if len(piece) < 5 and hi == 0 else UID_SYMBOLS[hi] + UID_SYMBOLS[lo])
+    return "".join(out)
+
+
+def gff_names(name: str, mirDict: Dict[str, str], pre_of: Dict[str, str], pre_mirDict: Dict[str, str]):
+    """What create_gff looks up from the NAME in a row of the mapped frame (summary.py:136-171): -> (name as printed,
+    canonical sequence, precursor name, precursor sequence), or None where one of the lookups raises the KeyError that
+    makes the reference drop the row (:492)."""
+    printed = name.split(".")[0] if "." in name else name
+    if printed not in pre_of:
+        for suffix in ("-3p", "-5p", "-3p*", "-5p*"):
+            printed = printed.replace(suffix, "")
+    try:
+        return printed, mirDict[printed], pre_of[printed], pre_mirDict[pre_of[printed]]
+    except KeyError:
+        return None
+
+
+def gff_line(name: str, source: str, master: Optional[str], read: str, precursor: Optional[str], parent: Optional[str],
+             counts: Sequence[int]) -> Optional[str]:
+    """One line of sample_miRge3.gff, newline included: ``name`` as printed, ``source`` the third header line's data base
+    version, ``master`` / ``precursor`` / ``parent`` the canonical sequence, the precursor's sequence and its name,
+    ``counts`` the read's count per sample.  None when the name resolved to nothing (gff_names): the row has no line."""
+    if master is None or precursor is None or parent is None:
+        return None
+    kind, start, end, variant, cigar = gff_record(master, read, precursor)
+    uid = "." if "N" in read else gff_uid(read, "ref" if kind == "ref_miRNA" else "iso")
+    expression = ",".join(str(int(c)) for c in counts)
+    return (f"{name}\t{source}\t{kind}\t{start}\t{end}\t.\t+\t.\tRead={read}; UID={uid}; Name={name}; Parent={parent}; "
+            f"Variant={variant}; Cigar={cigar}; Expression={expression}; Filter=Pass; Hits={expression}\n")
+
+
+# --------------------------------------------------------------------------------------
 # read trimming (row N4): the modifier chain the reference builds from cutadapt (mirge/libs/digest.py:59-101) and the
 # way its worker counts reads (:320-375).  PARITY UNPINNED: cutadapt is third-party and absent here, and the reference
 # holds no vectors for it -- these functions restate cutadapt 2.x-4.x's published algorithms (qualtrim.pyx:

@@ -75,6 +75,29 @@ def oracle_libs_from(libs, n_pass=9):
     return [(libs[PASS_LIBKEY[p]].seqs.data, libs[PASS_LIBKEY[p]].seqs.offsets) for p in range(n_pass)]
 
 
+def write_gff_name_files(libdir, mirDict, pre_of, org=ORG, db=DB):
+    """The two files the -gff route reads per miRNA NAME (mirge3_amd.gff.name_tables) into a library directory: the mature
+    FASTA (name -> canonical sequence) and the annotation in miRBase's layout (mature name -> precursor name; the matures of
+    a precursor follow its primary-transcript line).  -> the namespace the route takes as ``args``."""
+    from types import SimpleNamespace
+    os.makedirs(os.path.join(libdir, org, "fasta.Libs"), exist_ok=True)
+    os.makedirs(os.path.join(libdir, org, "annotation.Libs"), exist_ok=True)
+    with open(os.path.join(libdir, org, "fasta.Libs", f"{org}_mature_{db}.fa"), "w") as fh:
+        fh.write("".join(f">{nm}\n{s}\n" for nm, s in mirDict.items()))
+    by_pre = {}
+    for nm, p in pre_of.items():
+        by_pre.setdefault(p, []).append(nm)
+    with open(os.path.join(libdir, org, "annotation.Libs", f"{org}_{db}.gff3"), "w") as fh:
+        fh.write("##gff-version 3\n")
+        k = 0
+        for i, (p, matures) in enumerate(by_pre.items()):
+            fh.write(f"chr1\t.\tmiRNA_primary_transcript\t{1000 * i + 1}\t{1000 * i + 200}\t.\t+\t.\tID=MI{i:07d};Alias=MI{i:07d};Name={p}\n")
+            for nm in matures:
+                fh.write(f"chr1\t.\tmiRNA\t{1000 * i + 11}\t{1000 * i + 32}\t.\t+\t.\tID=MIMAT{k:07d};Alias=MIMAT{k:07d};Name={nm};Derives_from=MI{i:07d}\n")
+                k += 1
+    return SimpleNamespace(libraries_path=str(libdir), organism_name=org)
+
+
 LEX_DIGIT = {"A": 1, "C": 2, "G": 3, "N": 4, "T": 5}
 
 

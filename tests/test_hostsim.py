@@ -279,6 +279,46 @@ def test_isotype_core_equals_the_oracle_on_random_pairs():
     assert n > 5000 and len(shapes) >= 8
 
 
+def test_isotype_array_form_types_canonicals_of_up_to_48_nt():
+    """canonicals of 36..48 nt (MIRGE_ISO_MAXA) against the difflib restatement: reads as long as the canonical (trimmed,
+    extended, substituted, with an N), and reads of 16..23 nt cut from inside it, which the isomiR pass also aligns.  The
+    register form stops at 40 nt (MIRGE_ISO_FAST_MAXA) and at 64 positions for the two sequences together: it takes the short
+    reads of the canonicals of up to 40 nt and must decline every pair of a longer one, which the array form alone types --
+    until a test wrote such rows into a GFF3, a canonical of more than 40 nt left its rows untyped and without a line"""
+    rng = np.random.default_rng(12)
+    n = beyond = short_beyond = took = 0
+    for it in range(2400):
+        la = int(rng.integers(36, 49))
+        master = "".join("ACGT"[int(c)] for c in rng.integers(0, 4, size=la))
+        lead = "".join("ACGT"[int(c)] for c in rng.integers(0, 4, size=int(rng.integers(0, 12))))
+        trail = "".join("ACGT"[int(c)] for c in rng.integers(0, 4, size=int(rng.integers(3, 12))))
+        precursor = "" if it % 11 == 0 else lead + master + trail
+        o = len(lead)
+        short = it % 3 == 0
+        if short:
+            lb = int(rng.integers(16, 24))
+            s = o + int(rng.integers(0, la - lb + 1))
+            e = s + lb
+        else:
+            s, e = max(o - int(rng.integers(-2, 2)), 0), o + la + int(rng.integers(-3, 4))
+        read = list((lead + master + trail)[s:e])
+        for _ in range(int(rng.choice([0, 1, 1, 2, 3]))):
+            read[int(rng.integers(0, len(read)))] = "ACGTN"[int(rng.integers(0, 5))]
+        read = "".join(read)
+        want = oracle.gff_record(master, read, precursor)
+        assert hostsim_isotype(master, read, precursor) == want, (master, read, precursor)
+        fast = hostsim_isotype(master, read, precursor, "registers")  # (None: not a pair for the register form)
+        if la > 40 or la + len(read) > 64:
+            assert fast is None, (master, read)
+        else:
+            assert fast in (None, want), (master, read, precursor)
+            took += fast is not None
+        beyond += la > 40
+        short_beyond += short and la > 40
+        n += 1
+    assert n == 2400 and beyond > 1000 and short_beyond > 300 and took > 200
+
+
 def test_isotype_register_form_equals_the_array_form_on_millions_of_pairs():
     """k_isotype's register-resident typing (mirge_isotype_fast: sequences and the aligned lists as bit planes, difflib's longest
     match along diagonals) against the array form it replaced on the hot path, field for field, on 3 M pairs made in C++: shifted,
