@@ -371,8 +371,9 @@ int mirge_gff_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
  *                             every valid alignment (-a): trim5 / trim3 bases cut (-5 / -3), at most n_mm mismatches in the first
  *                             min(seedlen, L) bases of the read's 5' end and maxtotal in all (-n; -e 70 with FASTA qualities: 2); an N in
  *                             a query mismatches everything, a window with an ambiguous base or across two references is invalid; a
- *                             query with L < 1 or L <= n_mm has none.  0 <= n_mm <= 2, maxtotal <= 2, L <= 64.  Restated from bowtie's
- *                             documented -n policy (parity unpinned).                                                     */
+ *                             query with L < 1 or L <= n_mm has none.  0 <= n_mm <= 2, maxtotal <= 2, L <= 64, seedlen >= 5 (bowtie's own floor for -l: every piece
+ *                             of the seed holds a base); anything else is refused.  Restated from bowtie's documented -n policy
+ *                             (parity unpinned).                                                                          */
 typedef struct mirge_genome mirge_genome;
 int mirge_genome_create(mirge_ctx* ctx, const char* ascii, const int64_t* offsets, int64_t n_refs, mirge_genome** out);
 int mirge_genome_create_packed(mirge_ctx* ctx, const uint8_t* packed, int64_t n_packed, const uint64_t* rec_off,

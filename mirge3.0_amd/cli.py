@@ -167,6 +167,11 @@ def parse_args(argv=None):
             v = getattr(args, "ignored_" + k)
             if v is not None and not str(v).lstrip("-").isdigit():
                 ap.error(f"-{k} takes an integer")
+        # what the device's genome scan refuses (include/mirge_native.h), said here before a file is written
+        if args.ignored_sl is not None and int(args.ignored_sl) < 5:
+            ap.error("-sl is bowtie's -l: at least 5")
+        if args.ignored_maxl is not None and int(args.ignored_maxl) > 64:
+            ap.error("-maxl above 64: the genome scan on the device takes reads of at most 64 nt")
     if args.sam_header and not (args.sam_out or args.sorted_bam):
         ap.error("--sam-header requires --sam-out or --sorted-bam")
     if args.sorted_bam and (args.save_pkl or args.resume or args.backend == "bowtie"):

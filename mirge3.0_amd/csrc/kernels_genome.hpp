@@ -10,6 +10,7 @@
 
 #define MIRGE_GENOME_MAXLEN 64    // trimmed query length held in two words
 #define MIRGE_GENOME_MAXPIECES 3  // n_mm <= 2
+#define MIRGE_GENOME_MINSEED 5    // bowtie's floor for -l; every one of the <= 3 pieces of a seed holds a base
 #define MIRGE_GENOME_MAXK 13      // longest table key (a 4^13-bit = 8 MiB presence bitmap)
 #define MIRGE_GENOME_STRIP 32     // genome positions per thread and loop trip: one text word
 

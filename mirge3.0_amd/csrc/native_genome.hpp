@@ -129,8 +129,13 @@ static void genome_tables_release(mirge_ctx* c, GenomeTables& t) {
 static int genome_check_args(const char* who, mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t n,
                              int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3) {
     const std::string w(who);
-    if (!c || !g || !offsets || n < 0 || n_mm < 0 || n_mm > 2 || seedlen < 1 || maxtotal < 0 || maxtotal > 2 || trim5 < 0 || trim3 < 0)
-        return fail(-1, w + ": bad argument (0 <= n_mm <= 2, 0 <= maxtotal <= 2, seedlen >= 1)");
+    if (!c || !g || !offsets || n < 0 || n_mm < 0 || n_mm > 2 || maxtotal < 0 || maxtotal > 2 || trim5 < 0 || trim3 < 0)
+        return fail(-1, w + ": bad argument (0 <= n_mm <= 2, 0 <= maxtotal <= 2)");
+    // bowtie's own floor for -l.  Below n_mm + 1 a piece of the seed would be empty -- exact in every window, so that it would own
+    // every alignment and, having no table, report none
+    if (seedlen < MIRGE_GENOME_MINSEED)
+        return fail(-1, w + ": seedlen " + std::to_string(seedlen) + " is below the floor of " + std::to_string(MIRGE_GENOME_MINSEED) +
+                            " (bowtie -l)");
     if (n > (int64_t)(0xFFFFFFFFu / 8)) return fail(-1, w + ": too many queries for one call");
     if (n == 0) return 0;
     if (offsets[n] > 0 && !queries) return fail(-1, w + ": no query text");

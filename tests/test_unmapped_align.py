@@ -192,9 +192,9 @@ def brute_strata(refs, queries, n_mm, seedlen, maxtotal, trim5, trim3, norc):
     return out
 
 
-def strata_case(rng, n_refs=260, n_reads=420):
-    """random references of 20 to 30 nt, some of them copies or near copies of others (one base changed inside the first 15, or
-    two past them), and reads cut from them with 0 to 3 changes, on both strands"""
+def strata_case(rng, n_refs=260, n_reads=420, ref_len=(20, 30), read_len=(16, 25), past=(17, 19)):
+    """random references of ref_len nt, some of them copies or near copies of others (one base changed inside the first 15, or
+    two past them, at ``past``), and reads of read_len nt cut from either end of them with 0 to 3 changes, on both strands"""
     def rand(n):
         return "".join("ACGT"[int(c)] for c in rng.integers(0, 4, n))
 
@@ -202,7 +202,7 @@ def strata_case(rng, n_refs=260, n_reads=420):
         return s[:at] + "ACGT"[("ACGT".index(s[at]) + 1 + int(rng.integers(0, 3))) % 4] + s[at + 1:]
     refs, pairs = [], []
     while len(refs) < n_refs:
-        r = rand(int(rng.integers(20, 31)))
+        r = rand(int(rng.integers(ref_len[0], ref_len[1] + 1)))
         refs.append(r)
         k = rng.random()
         if k < 0.08:
@@ -214,14 +214,14 @@ def strata_case(rng, n_refs=260, n_reads=420):
         elif k < 0.35:
             refs.append(change(r, int(rng.integers(2, 14))))
         elif k < 0.55:
-            refs.append(change(change(r, 17), 19))
+            refs.append(change(change(r, past[0]), past[1]))
         elif k < 0.65:
-            refs.append(change(change(change(r, 17), 19), int(rng.integers(2, 14))))
+            refs.append(change(change(change(r, past[0]), past[1]), int(rng.integers(2, 14))))
             pairs.append((r, refs[-1]))
     reads = []
     for _ in range(n_reads):
         r = refs[int(rng.integers(0, len(refs)))]
-        L = int(rng.integers(16, min(len(r), 25) + 1))
+        L = int(rng.integers(read_len[0], min(len(r), read_len[1]) + 1))
         s = r[:L] if rng.random() < 0.7 else r[len(r) - L:]
         for _ in range(int(rng.choice([0, 0, 1, 1, 2, 3]))):
             s = change(s, int(rng.integers(0, L)))
@@ -229,8 +229,9 @@ def strata_case(rng, n_refs=260, n_reads=420):
             s = rand(L)
         reads.append(s if rng.random() < 0.7 else s.translate(_RC)[::-1])
     for r, v in pairs:  # against r: two mismatches past the seed; against its variant: one, in the seed
-        if len(r) >= 23:
-            reads.append((r[:17] + v[17] + r[18] + v[19] + r[20:])[:int(rng.integers(23, min(len(r), 25) + 1))])
+        if len(r) >= past[1] + 4:
+            s = r[:past[0]] + v[past[0]] + r[past[0] + 1:past[1]] + v[past[1]] + r[past[1] + 1:]
+            reads.append(s[:int(rng.integers(max(past[1] + 4, read_len[0]), min(len(r), read_len[1]) + 1))])
     return refs, reads
 
 

@@ -141,7 +141,7 @@ def test_cluster_file_equals_the_references(tmp_path, sample):
     assert len(minus) == len(set(minus)) >= 2  # one minus-strand cluster per reference, though chr1 has two piles
 
 
-def test_switch_parsing_defaults_and_refusals():
+def test_switch_parsing_defaults_and_refusals(capsys):
     from mirge3_amd.cli import parse_args
     base = ["-s", "a.fq", "-lib", "/x", "-on", "human"]
     off = parse_args(base + ["-minl", "18", "-olc", "12"])
@@ -154,6 +154,14 @@ def test_switch_parsing_defaults_and_refusals():
                 ["-nmir"]):
         with pytest.raises(SystemExit):
             parse_args(base + bad)
+    # what the genome scan refuses is refused here, before a file is written: a seed below bowtie's floor, reads past two words
+    for ok in (["-sl", "5"], ["-maxl", "64"]):
+        parse_args(base + ["--unmapped-clusters"] + ok)
+    for bad, word in ((["-sl", "4"], "at least 5"), (["-sl", "0"], "at least 5"), (["-sl", "-3"], "at least 5"), (["-maxl", "65"], "64 nt")):
+        with pytest.raises(SystemExit):
+            parse_args(base + ["--unmapped-clusters"] + bad)
+        assert word in capsys.readouterr().err, bad
+        parse_args(base + bad)  # read only with the switch, as before
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
