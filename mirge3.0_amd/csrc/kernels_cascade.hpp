@@ -1002,11 +1002,15 @@ k_cascade_bulk(const BulkWalks* __restrict__ walks, GroupView<W> g, uint32_t* __
     }
     if (threadIdx.x == 0) seg_n[(size_t)(MIRGE_MAX_PASSES_K + 2) * gridDim.x + blockIdx.x] = (uint32_t)wall_clock64();
     // (k_resolve stays a launch of its own: done here, for the workgroup's own reads, it is a chain of dependent loads with
-    // four waves to hide it -- the kernel grew by 0.04 ms to save a 0.046 ms launch that the whole chip runs at once)
+    // four waves to hide it -- the kernel grew by 0.04 ms to save a 0.046 ms launch that the whole chip runs at once.  For the
+    // bulk group that launch is no longer queued right behind this kernel: mirge_ctx::PendingResolve, native_ctx.hpp)
 }
 
 // (Four reads per thread with their loads issued together -- before and after the table became one access -- changed nothing:
 // 45 -> 49-53 us.  7.6 M wave-level VALU instructions per launch, most of them the 16-way pointer select, 73 MB moved.)
+// Nothing in a step's tail waits for the bulk group's launch of this kernel: the count join resolves the positions of the miRNA
+// reads -- the only references its tables need -- itself, with resolve_entry on the two miRNA libraries' rows (kernels_join.hpp),
+// and queues this kernel behind the event the host waits for; every other consumer finds it launched first (join_pending_now).
 __global__ void k_resolve(ResolveTable tb, const int8_t* __restrict__ res_pass, const uint32_t* __restrict__ res_pos,
                           uint32_t n, int32_t* __restrict__ res_ref, int32_t* __restrict__ res_off,
                           const uint32_t* __restrict__ n_dev) {

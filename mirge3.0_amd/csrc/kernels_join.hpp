@@ -38,13 +38,38 @@ __global__ void k_join(const int8_t* __restrict__ res_pass, const int32_t* __res
 }
 
 // the small read groups of a result in ONE launch (each its own launch was 4-5 us of a step's tail, four times)
+// The reference of a miRNA read (exact_pass / iso_pass: the only reads whose reference the tables need) comes from its POSITION: one
+// granule entry of that pass's library (ResolveTable's row, handed over by value: `mi[0]` exact_pass, `mi[1]` iso_pass) through
+// resolve_entry -- the device function k_resolve answers with, so the same reference by construction.  The miRNA library's granule
+// table is a few tens of KB and stays in cache; the join then needs nothing of k_resolve, whose look-ups for every OTHER annotated
+// read (one random granule entry each, out of tables as large as the mRNA library's) run behind the join (native_join.hpp).
+// from_pos == 0: the references are read from `ref` (a result whose positions or granule tables this context cannot vouch for).
+struct JoinResolveRow { const uint32_t* ref_start; const uint32_t* coarse; uint32_t n_refs; };
 struct JoinGroups {
     const int8_t* pass[MIRGE_NCLS];
     const int32_t* ref[MIRGE_NCLS];
+    const uint32_t* pos[MIRGE_NCLS];
     const uint32_t* counts[MIRGE_NCLS];
     uint32_t start[MIRGE_NCLS + 1];  // group k holds the items [start[k], start[k + 1]) of the launch
     int32_t n_groups;
+    int32_t from_pos;
+    JoinResolveRow mi[2];
 };
+__device__ __forceinline__ PairU32 join_granule(const JoinResolveRow& t, uint32_t g) {
+    return load_pair32((gptr_u32)t.coarse + 2 * (size_t)(g >> MIRGE_COARSE_SHIFT));
+}
+__device__ __forceinline__ uint32_t join_ref_at(const JoinResolveRow& t, const PairU32 e, uint32_t g) {
+    int32_t ref, off;
+    resolve_entry(e, t.ref_start, t.n_refs, g, ref, off);
+    return (uint32_t)ref;
+}
+// the reference of read i of a group, annotated by pass p (one of the two miRNA passes)
+__device__ __forceinline__ uint32_t join_ref(const JoinGroups& gs, bool is_iso, const int32_t* gr, const uint32_t* gq, uint32_t i) {
+    if (!gs.from_pos) return (uint32_t)gr[i];
+    const JoinResolveRow t = is_iso ? gs.mi[1] : gs.mi[0];
+    const uint32_t g = gq[i];
+    return join_ref_at(t, join_granule(t, g), g);
+}
 __global__ void k_join_multi(JoinGroups gs, int32_t S, int32_t n_pass, int32_t exact_pass, int32_t iso_pass,
                              unsigned long long* __restrict__ class_sums, unsigned long long* __restrict__ exact,
                              unsigned long long* __restrict__ iso) {
@@ -61,12 +86,13 @@ __global__ void k_join_multi(JoinGroups gs, int32_t S, int32_t n_pass, int32_t e
 #pragma unroll
         for (int q = 1; q < MIRGE_NCLS; q++) if (q < gs.n_groups && t >= gs.start[q]) k = q;
         const uint32_t i = t - gs.start[k];
-        const int8_t* gp = nullptr; const int32_t* gr = nullptr; const uint32_t* gc = nullptr;
+        const int8_t* gp = nullptr; const int32_t* gr = nullptr; const uint32_t* gq = nullptr; const uint32_t* gc = nullptr;
 #pragma unroll
-        for (int q = 0; q < MIRGE_NCLS; q++) if (q == k) { gp = gs.pass[q]; gr = gs.ref[q]; gc = gs.counts[q]; }
+        for (int q = 0; q < MIRGE_NCLS; q++) if (q == k) { gp = gs.pass[q]; gr = gs.ref[q]; gq = gs.pos[q]; gc = gs.counts[q]; }
         const int p = gp[i];
         if (p < 0) continue;
-        const int32_t ref = gr[i];
+        const bool mirna = p == exact_pass || p == iso_pass;
+        const uint32_t ref = mirna ? join_ref(gs, p != exact_pass, gr, gq, i) : 0u;
         for (int32_t s = 0; s < S; s++) {
             const unsigned long long c = gc[(size_t)i * S + s];
             if (!c) continue;
@@ -103,6 +129,8 @@ k_join_rows(JoinGroups gs, int32_t S, int32_t n_pass, int32_t exact_pass, int32_
         // the bulk group of one sample: four reads per thread and sweep, their loads issued together (16 dependent
         // pass -> reference -> count walks per thread before: 23 us for 38 MB)
         const int8_t* __restrict__ gp = gs.pass[0]; const int32_t* __restrict__ gr = gs.ref[0]; const uint32_t* __restrict__ gc = gs.counts[0];
+        const uint32_t* __restrict__ gq = gs.pos[0];
+        const bool from_pos = gs.from_pos != 0;
         const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;  // 64-bit: t0 + 3 * stride passes 2^32 for a group near that size
         for (uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t0 < total; t0 += 4 * stride) {
             int p[4]; uint32_t r[4]; unsigned long long c[4];
@@ -111,8 +139,19 @@ k_join_rows(JoinGroups gs, int32_t S, int32_t n_pass, int32_t exact_pass, int32_
                 const uint64_t i = t0 + (uint64_t)u * stride;
                 const bool in = i < total;
                 p[u] = in ? (int)gp[i] : -1;
-                r[u] = in ? (uint32_t)gr[i] : 0u;
+                r[u] = in ? (from_pos ? gq[i] : (uint32_t)gr[i]) : 0u;  // the position, or the reference itself
                 c[u] = in ? (unsigned long long)gc[i] : 0ull;
+            }
+            if (from_pos) {  // the granule entries of the up to four miRNA reads, their loads issued together
+                PairU32 e[4]; bool m[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    m[u] = p[u] >= 0 && (p[u] == exact_pass || p[u] == iso_pass);
+                    e[u] = m[u] ? join_granule(p[u] == exact_pass ? gs.mi[0] : gs.mi[1], r[u]) : PairU32{0u, 0u};
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (m[u]) r[u] = join_ref_at(p[u] == exact_pass ? gs.mi[0] : gs.mi[1], e[u], r[u]);
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -127,13 +166,14 @@ k_join_rows(JoinGroups gs, int32_t S, int32_t n_pass, int32_t exact_pass, int32_
         int k = 0;  // one group (the bulk) or the few small ones, back to back
 #pragma unroll
         for (int q = 1; q < MIRGE_NCLS; q++) if (q < gs.n_groups && t >= gs.start[q]) k = q;
-        const int8_t* gp = gs.pass[0]; const int32_t* gr = gs.ref[0]; const uint32_t* gc = gs.counts[0];
+        const int8_t* gp = gs.pass[0]; const int32_t* gr = gs.ref[0]; const uint32_t* gq = gs.pos[0]; const uint32_t* gc = gs.counts[0];
 #pragma unroll
-        for (int q = 1; q < MIRGE_NCLS; q++) if (q == k) { gp = gs.pass[q]; gr = gs.ref[q]; gc = gs.counts[q]; }
+        for (int q = 1; q < MIRGE_NCLS; q++) if (q == k) { gp = gs.pass[q]; gr = gs.ref[q]; gq = gs.pos[q]; gc = gs.counts[q]; }
         const uint32_t i = t - gs.start[k];
         const int p = gp[i];
         if (p < 0) continue;
-        const uint32_t ref = (uint32_t)gr[i];
+        const bool mirna = p == exact_pass || p == iso_pass;
+        const uint32_t ref = mirna ? join_ref(gs, p != exact_pass, gr, gq, i) : 0u;
         for (int32_t s = 0; s < S; s++) {
             const unsigned long long c = gc[(size_t)i * S + s];
             if (!c) continue;

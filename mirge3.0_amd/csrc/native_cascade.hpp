@@ -19,6 +19,10 @@ struct mirge_result {
     const mirge_reads* reads = nullptr;  // borrowed: orig/base mapping (must outlive the fetch)
     uint32_t n_refs[MIRGE_MAX_PASSES] = {0};  // references of each pass's library (bounds of res.ref; checked by the join)
     uint32_t* dmeta = nullptr;           // mirge_collapse_cascade: the device-side read counts its kernels read
+    // the granule tables of the passes' libraries and the library epoch they were read at: while that epoch stands the count join
+    // resolves a miRNA read's position itself (kernels_join.hpp, JoinGroups::from_pos)
+    ResolveTable rt;
+    uint64_t lib_epoch = ~0ull;
 };
 
 extern "C" void mirge_result_destroy(mirge_result* r) {
@@ -114,7 +118,11 @@ static void launch_heavy(mirge_ctx* c, const ReadGroup& rg, const ResGroup& out,
 template <int W>
 static int cascade_group(mirge_ctx* c, const ReadGroup& rg, ResGroup& out, const std::vector<PassStep>& steps,
                          const mirge_policy* pol, const ResolveTable& rt, const char* gtag,
-                         const uint32_t* n_dev = nullptr, uint32_t n_cap = 0, const BulkWalks* dwalks = nullptr) {
+                         const uint32_t* n_dev = nullptr, uint32_t n_cap = 0, const BulkWalks* dwalks = nullptr, bool defer_resolve = false) {
+    // defer_resolve (the bulk group, on the main stream): k_resolve is not launched here but left with the ctx (PendingResolve) for the
+    // count join to queue BEHIND its tables, or for whichever entry point comes first (join_pending_now).  Only with libraries of
+    // this context's own (casc_libs_own): mirge_lib_destroy launches the pending kernel of the library's context and no other's
+    defer_resolve = defer_resolve && c->casc_libs_own;
     // n_dev != nullptr: the group's read count is not on the host yet (see k_pass); everything is sized for
     // n_cap >= the count, the caller fills out.n in later
     out.n = n_dev ? 0 : rg.n;
@@ -171,6 +179,7 @@ static int cascade_group(mirge_ctx* c, const ReadGroup& rg, ResGroup& out, const
     uint32_t* act_out = actA;
     int stage = 0;
     char name[32];
+    const uint32_t* wg_src = nullptr;  // the workgroups' clocks of a profiled k_cascade_bulk<1> launch
     std::vector<std::pair<int, int>> stage_of_pass;  // (profile record, stage) for unit accounting
     // all passes in ONE launch (k_cascade_bulk): a workgroup's segment and survivor lists are its own through the whole
     // cascade, so the launches between the passes were chip-wide barriers nothing needed.  MIRGE_BULK_FUSED=0: one launch
@@ -192,12 +201,15 @@ static int cascade_group(mirge_ctx* c, const ReadGroup& rg, ResGroup& out, const
         stage = (int)steps.size();
         if (c->profiling && W == 1) {  // the workgroups' clocks of this launch, for mirge_cascade_wg_times (stream-ordered copy)
             if (c->wg_pinned_words < 2 * (size_t)grid) {
-                if (c->wg_pinned) (void)hipHostFree(c->wg_pinned);
+                if (c->wg_pinned) { HIPOK(hipStreamSynchronize(c->stream)); (void)hipHostFree(c->wg_pinned); }
                 c->wg_pinned = nullptr; c->wg_pinned_words = 0;
                 if (hipHostMalloc((void**)&c->wg_pinned, 2 * (size_t)grid * 4, hipHostMallocDefault) == hipSuccess) c->wg_pinned_words = 2 * (size_t)grid;
             }
-            if (c->wg_pinned_words >= 2 * (size_t)grid) {
-                HIPOK(hipMemcpyAsync(c->wg_pinned, seg_n + (size_t)grid * (MIRGE_MAX_PASSES + 1), 2 * (size_t)grid * 4, hipMemcpyDeviceToHost, c->cur));
+            // (nothing on the device reads the copy: with a deferred k_resolve it is queued behind that kernel, not between the bulk
+            //  kernel and the join -- 4.5 us of copy kernel and a 6 us queue gap in the step's tail)
+            if (c->wg_pinned_words >= 2 * (size_t)grid) wg_src = seg_n + (size_t)grid * (MIRGE_MAX_PASSES + 1);
+            if (wg_src && !defer_resolve) {
+                HIPOK(hipMemcpyAsync(c->wg_pinned, wg_src, 2 * (size_t)grid * 4, hipMemcpyDeviceToHost, c->cur));
                 c->wg_grid = grid;
             }
         }
@@ -237,8 +249,15 @@ static int cascade_group(mirge_ctx* c, const ReadGroup& rg, ResGroup& out, const
         stage++;
     }
     if (hcnt && stage > 0) launch_heavy<W>(c, rg, out, c->casc_dsteps, rt, gtag, hcnt, hlist, v, false);  // (k_resolve follows for every read)
-    {
-        std::snprintf(name, sizeof(name), "k_resolve%s", gtag);
+    std::snprintf(name, sizeof(name), "k_resolve%s", gtag);
+    if (defer_resolve) {
+        CHECK(resolve_pending_now(c));  // (every entry point launches what is pending before it gets here: nothing to do)
+        mirge_ctx::PendingResolve& r = c->resolve_pending;
+        r.rt = rt; r.pass = out.pass; r.pos = out.pos; r.n = n; r.ref = out.ref; r.off = out.off; r.n_dev = n_dev;
+        std::snprintf(r.name, sizeof(r.name), "%s", name);
+        r.wg_src = wg_src; r.wg_grid = grid;
+        r.set = true;
+    } else {
         LaunchScope ls(c, name, n);
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->cur, rt, out.pass, out.pos, n, out.ref, out.off, n_dev);
     }
@@ -274,9 +293,8 @@ static int cascade_group_fused(mirge_ctx* c, const ReadGroup& rg, ResGroup& out,
     char name[32];
     // (round 6) a tiny group: all passes at once (k_cascade_spec), then the first answer per read (k_cascade_pick).  MIRGE_SPEC_MAX: the
     // largest group (reads) that takes this route, 0 = never (tests, A/B)
-    static const uint32_t spec_max = std::getenv("MIRGE_SPEC_MAX") ? (uint32_t)std::strtoul(std::getenv("MIRGE_SPEC_MAX"), nullptr, 10) : 32768u;
     const int nsteps = (int)c->casc_steps.size();
-    if (n <= spec_max && nsteps > 1) {
+    if (n <= small_spec_max(c)) {  // (native_collapse.hpp: the one reading of the variable; 0 with a single step)
         unsigned long long* answers = nullptr;
         const uint32_t rounds = (n + MIRGE_BLOCK - 1) / MIRGE_BLOCK, stride = rounds * MIRGE_BLOCK;
         CHECK(dalloc(c, &answers, (size_t)nsteps * stride));
@@ -340,6 +358,8 @@ static int cascade_prepare(mirge_ctx* c, const mirge_lib* const* libs, const mir
                            const BulkWalks** dwalks_out) {
     for (int p = 0; p < MIRGE_MAX_PASSES; p++) { rt.ref_start[p] = nullptr; rt.coarse[p] = nullptr; rt.n_refs[p] = 0; }
     steps.clear();
+    c->casc_libs_own = true;
+    for (int32_t p = 0; p < n_pass; p++) if (libs[p] && libs[p]->ctx != c) c->casc_libs_own = false;
     for (int32_t p = 0; p < n_pass; p++) {
         if (!libs[p]) continue;
         if (libs[p]->ctx->device != c->device) return fail(-1, "library lives on another device");
@@ -570,17 +590,29 @@ static int cascade_launch_groups(mirge_ctx* c, const mirge_reads* R, mirge_resul
     // enqueue order: the small groups first (one fused launch each, or the staged launches if a group is too
     // large for that), the bulk group last: measured, its 2048-workgroup launches otherwise hold every CU and the
     // small kernels squeeze in between them, stretching single passes of the bulk group by 30 %
-    int order[MIRGE_NGROUPS], no = 0;
-    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) if (gi != big) order[no++] = gi;
-    // the largest small group first: it gets extra stream 0, the one the main stream waits for directly (stream_join)
-    std::stable_sort(order, order + no, [&](int a, int b) { return R->g[a].n > R->g[b].n; });
-    order[no++] = big;
     // every small group's one-launch cascade on an extra stream, behind whatever `aux` still holds for them (with `xaux_forked`:
     // behind its own scatter kernel, which collapse_impl put on the slot this computes again from the same counts)
     uint32_t n[MIRGE_NGROUPS];
     int slot[MIRGE_NGROUPS];
     for (int gi = 0; gi < MIRGE_NGROUPS; gi++) n[gi] = R->g[gi].n;
-    if (small_group_slots(n, big, skip, slot) && !c->xaux_forked) CHECK(xaux_fork(c));
+    const uint32_t spec_max = small_spec_max(c);
+    if (small_group_slots(n, big, skip, slot, spec_max) && !c->xaux_forked) CHECK(xaux_fork(c));
+    // Within an extra stream: no k_cascade_spec / k_cascade_pick group behind a k_cascade_fused one, and the largest one-launch group
+    // last (this matters when both extra streams hold a k_cascade_fused group and the tiny ones have to share with them).  So: the
+    // staged groups and the long class, largest first (as ever: a staged group races the bulk group for the CUs,
+    // profiles/r06_ab_c4_shape.txt), then the tiny groups, largest first, then the k_cascade_fused groups, smallest first.
+    auto rank = [&](int gi) {
+        if (is_long_group(gi) || n[gi] > fused_max) return 1;
+        return n[gi] <= spec_max ? 2 : 3;
+    };
+    int order[MIRGE_NGROUPS], no = 0;
+    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) if (gi != big) order[no++] = gi;
+    std::stable_sort(order, order + no, [&](int a, int b) {
+        const int ra = rank(a), rb = rank(b);
+        if (ra != rb) return ra < rb;
+        return ra == 3 ? n[a] < n[b] : n[a] > n[b];
+    });
+    order[no++] = big;
     for (int k = 0; k < MIRGE_NGROUPS && rc == 0; k++) {
         const int gi = order[k];
         if (gi == skip) continue;
@@ -594,7 +626,7 @@ static int cascade_launch_groups(mirge_ctx* c, const mirge_reads* R, mirge_resul
             MIRGE_BY_WIDTH(gi, rc, cascade_group_fused<W>(c, R->g[gi], res->g[gi], dsteps, rt, group_tag(gi)));
             continue;
         }
-        MIRGE_BY_WIDTH(gi, rc, cascade_group<W>(c, R->g[gi], res->g[gi], steps, pol, rt, group_tag(gi), nullptr, 0, c->casc_dwalks[W == 1 ? 0 : 1]));
+        MIRGE_BY_WIDTH(gi, rc, cascade_group<W>(c, R->g[gi], res->g[gi], steps, pol, rt, group_tag(gi), nullptr, 0, c->casc_dwalks[W == 1 ? 0 : 1], gi == big));
     }
     // (round 6, the mirge_collapse_cascade route) extra stream 0 collects the other extra streams now, behind its own last cascade: the
     // join then has ONE stream to wait for (stream_join)
@@ -640,6 +672,7 @@ extern "C" int mirge_cascade_run(mirge_ctx* c, const mirge_reads* R, const mirge
     hc.lap("plans+fused");
     auto res = std::make_unique<mirge_result>();
     res->ctx = c; res->n = R->n; res->n_pass = n_pass; res->reads = R;
+    res->rt = c->casc_rt; res->lib_epoch = g_lib_epoch.load();
     for (int32_t p = 0; p < n_pass; p++) res->n_refs[p] = libs[p] ? (uint32_t)libs[p]->n_refs : 0u;
     const int rc = cascade_launch_groups(c, R, res.get(), pol, -1);
     hc.lap("enqueue+join");
@@ -714,6 +747,7 @@ extern "C" int mirge_collapse_cascade(mirge_ctx* c, const mirge_reads* raw, cons
     CHECK(cascade_config(c, libs, pol, n_pass, raw->len_hist, raw->long_max > 0));
     auto res = std::make_unique<mirge_result>();
     res->ctx = c; res->n_pass = n_pass;
+    res->rt = c->casc_rt; res->lib_epoch = g_lib_epoch.load();
     for (int32_t p = 0; p < n_pass; p++) res->n_refs[p] = libs[p] ? (uint32_t)libs[p]->n_refs : 0u;
     const size_t prof_mark = c->prof_pending.size();
     int hooked_group = -1;
@@ -722,7 +756,7 @@ extern "C" int mirge_collapse_cascade(mirge_ctx* c, const mirge_reads* raw, cons
         ReadGroup rg = partial->g[big];  // the unique reads' arrays, allocated for the raw count
         rg.n = raw->g[big].n;
         c->cur = c->stream;
-        const int rc = cascade_group<1>(c, rg, res->g[big], c->casc_steps, pol, c->casc_rt, group_tag(big), dmeta + big, raw->g[big].n, c->casc_dwalks[0]);
+        const int rc = cascade_group<1>(c, rg, res->g[big], c->casc_steps, pol, c->casc_rt, group_tag(big), dmeta + big, raw->g[big].n, c->casc_dwalks[0], true);
         if (rc == 0) { hooked_group = big; c->overlap_mode = true; }
         return rc;
     };
@@ -735,6 +769,7 @@ extern "C" int mirge_collapse_cascade(mirge_ctx* c, const mirge_reads* raw, cons
         (void)hipStreamSynchronize(c->aux);
         for (int k = 0; k < MIRGE_N_XAUX; k++) (void)hipStreamSynchronize(c->xaux[k]);
         c->overlap_mode = false;
+        c->resolve_pending.set = false;  // (its buffers go back to the pool below)
         c->join_pending = false;  // (everything has drained: nothing is left to join)
         c->xaux_used = false;
         c->x0_gathered = c->aux_drained = false;

@@ -399,11 +399,23 @@ static uint32_t small_fused_max() {  // (cascade_launch_groups: the largest grou
     static const uint32_t v = std::getenv("MIRGE_FUSED_MAX") ? (uint32_t)std::strtoul(std::getenv("MIRGE_FUSED_MAX"), nullptr, 10) : (1u << 19);
     return v;
 }
+// The largest group (reads) whose one-launch cascade is k_cascade_spec + k_cascade_pick (all passes at once) instead of k_cascade_fused;
+// 0 = none: MIRGE_SPEC_MAX=0 (tests, A/B), or a configuration of a single step.
+static uint32_t small_spec_max(const mirge_ctx* c) {
+    static const uint32_t v = std::getenv("MIRGE_SPEC_MAX") ? (uint32_t)std::strtoul(std::getenv("MIRGE_SPEC_MAX"), nullptr, 10) : 32768u;
+    // (the steps of the ctx's CURRENT configuration: collapse_impl asks only on the hooked route, mirge_collapse_cascade, which has
+    //  configured the cascade just before -- the same steps cascade_launch_groups then sees, so scatter kernel and cascade get one slot)
+    return c->casc_steps.size() > 1 ? v : 0u;
+}
 // Which extra stream the one-launch cascade of every small read group takes (collapse_impl puts its scatter kernel there too): the
 // groups other than `big` and `skip` by size, largest first, dealt over the extra streams in turn for those that take the one-launch
 // route; -1: the second stream.  n[gi] = reads of group gi.  Returns whether the small groups are spread (more than one, the long
 // class counted); otherwise every slot is -1.
-static bool small_group_slots(const uint32_t* n, int big, int skip, int* slot) {
+// A group of up to `spec_max` reads (k_cascade_spec / k_cascade_pick: some tens of us wherever it runs) is dealt over the streams that
+// hold no k_cascade_fused group -- over all of them when every stream holds one or none does.  Behind a k_cascade_fused group, which
+// ends when the bulk kernel's workgroups retire, its 26 us were the last thing the step's join waited for; on the other stream they
+// are over long before.  Scatter kernel and cascade move together: both callers take their slots from here.
+static bool small_group_slots(const uint32_t* n, int big, int skip, int* slot, uint32_t spec_max) {
     const uint32_t fused_max = small_fused_max();
     int order[MIRGE_NGROUPS], no = 0;
     for (int gi = 0; gi < MIRGE_NGROUPS; gi++) { slot[gi] = -1; if (gi != big && gi != skip) order[no++] = gi; }
@@ -412,10 +424,21 @@ static bool small_group_slots(const uint32_t* n, int big, int skip, int* slot) {
     for (int k = 0; k < no; k++) if (n[order[k]] && n[order[k]] <= fused_max) n_small++;
     if (n_small <= 1) return false;
     int next = 0;
+    bool holds_fused[MIRGE_N_SLOTS] = {false};
     for (int k = 0; k < no; k++) {
         const int gi = order[k];
-        if (is_long_group(gi) || !n[gi] || n[gi] > fused_max) continue;
+        if (is_long_group(gi) || !n[gi] || n[gi] > fused_max || n[gi] <= spec_max) continue;
         slot[gi] = next++ % MIRGE_N_SLOTS;  // 0: the largest, the stream stream_join waits for directly
+        holds_fused[slot[gi]] = true;
+    }
+    int n_free = 0;
+    for (int q = 0; q < MIRGE_N_SLOTS; q++) n_free += holds_fused[q] ? 0 : 1;
+    for (int k = 0; k < no; k++) {
+        const int gi = order[k];
+        if (is_long_group(gi) || !n[gi] || n[gi] > fused_max || n[gi] > spec_max) continue;
+        int q = next++ % MIRGE_N_SLOTS;
+        while (n_free && holds_fused[q]) q = next++ % MIRGE_N_SLOTS;
+        slot[gi] = q;
     }
     return true;
 }
@@ -523,7 +546,7 @@ static int collapse_impl(mirge_ctx* c, const mirge_reads* raw, const int32_t* sa
                 int xslot[MIRGE_NGROUPS];
                 uint32_t n_small_u[MIRGE_NGROUPS];
                 for (int gi = 0; gi < MIRGE_NGROUPS; gi++) n_small_u[gi] = gi == big ? 0u : small[gi];
-                small_group_slots(n_small_u, big, big, xslot);
+                small_group_slots(n_small_u, big, big, xslot, small_spec_max(c));
                 bool forked = false;
                 for (int gi = 0; gi < MIRGE_NGROUPS; gi++) forked |= xslot[gi] >= 0;
                 // Not when a small group is large enough for the staged cascade (beyond MIRGE_FUSED_MAX unique reads: a 20 M-read sample's

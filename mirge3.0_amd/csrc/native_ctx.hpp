@@ -112,12 +112,28 @@ struct mirge_ctx {
     std::string casc_key;           // configuration of the previous mirge_cascade_run ...
     std::vector<PassStep> casc_steps;  // ... and what was prepared for it
     ResolveTable casc_rt;
+    // every library of the configuration was made in this context: only then may a k_resolve stay pending (PendingResolve) -- the
+    // owner of a borrowed library destroys it without knowing of this context, and frees the granule tables the kernel reads
+    bool casc_libs_own = false;
     const FusedSteps* casc_dsteps = nullptr;
     struct WalksEntry { std::unique_ptr<BulkWalks> host; BulkWalks* dev; };
     std::vector<WalksEntry> walks;      // walk lists of k_cascade_bulk already on the device
     const BulkWalks* casc_dwalks[2] = {nullptr, nullptr};  // [0] the one-word group's list (exact steps ride along), [1] wider groups
     size_t prof_used = 0;
     std::vector<ProfUnits> prof_pending;
+    // The bulk group's k_resolve, not launched yet (cascade_group): the count join finds a miRNA read's reference from its position and
+    // needs none of what k_resolve writes, so the launch waits until the join has queued its kernels and the event the host waits
+    // for -- or until any other entry point touches the ctx (join_pending_now, mirge_lib_destroy): resolution at the first consumer.
+    // The main stream's order then puts res_ref / res_off in front of whatever reads them, as before.  `rt` is a copy: the ctx's table may be reconfigured before the launch.
+    struct PendingResolve {
+        bool set = false;
+        ResolveTable rt;
+        const int8_t* pass = nullptr; const uint32_t* pos = nullptr; uint32_t n = 0;
+        int32_t* ref = nullptr; int32_t* off = nullptr; const uint32_t* n_dev = nullptr;
+        char name[32] = {0};
+        // the workgroups' clocks of a profiled k_cascade_bulk launch go to the host behind k_resolve instead of in front of it
+        const uint32_t* wg_src = nullptr; uint32_t wg_grid = 0;
+    } resolve_pending;
 
     int alloc(void** out, size_t bytes) {
         bytes = (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
@@ -166,6 +182,8 @@ struct mirge_ctx {
         if (!evt_pool.empty()) { hipEvent_t e = evt_pool.back(); evt_pool.pop_back(); return e; }
         hipEvent_t e; (void)hipEventCreate(&e); return e;
     }
+    // (a profile read that wants the k_resolve queued behind a count join's event goes through mirge_ctx_sync first, as
+    //  mirge_ctx_profile_count does: a drain right behind the join carries that pair over to the next one)
     void drain() {  // resolve pending event pairs (caller has synchronised the stream)
         for (auto& u : prof_pending) {
             double units = u.n_first;
@@ -174,13 +192,17 @@ struct mirge_ctx {
         }
         prof_pending.clear();
         prof_used = 0;
+        std::vector<PendingEvt> later;  // a launch queued behind the point the caller waited for (the deferred k_resolve): next time
         for (auto& p : pending) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) recs[p.rec].total_ms += ms;
+            const hipError_t e = hipEventElapsedTime(&ms, p.a, p.b);
+            if (e == hipErrorNotReady) { later.push_back(p); continue; }
+            if (e == hipSuccess) recs[p.rec].total_ms += ms;
             evt_pool.push_back(p.a);
             evt_pool.push_back(p.b);
         }
-        pending.clear();
+        if (!later.empty()) (void)hipGetLastError();  // ("not ready" is no error to report from the next launch check)
+        pending.swap(later);
     }
 };
 
@@ -258,17 +280,37 @@ static int stream_join(mirge_ctx* c) {
     if (e != hipSuccess) return fail(-2, std::string("stream join: ") + hipGetErrorString(e));
     return 0;
 }
+static inline int grid_for(const mirge_ctx* c, size_t n, int per_block = MIRGE_BLOCK);
+// the bulk group's deferred k_resolve (mirge_ctx::PendingResolve), on the main stream, now
+static int resolve_pending_now(mirge_ctx* c) {
+    mirge_ctx::PendingResolve& r = c->resolve_pending;
+    if (!r.set) return 0;
+    r.set = false;
+    hipStream_t const cur = c->cur;
+    c->cur = c->stream;
+    {
+        LaunchScope ls(c, r.name, r.n);
+        hipLaunchKernelGGL(k_resolve, dim3(grid_for(c, r.n)), dim3(MIRGE_BLOCK), 0, c->stream, r.rt, r.pass, r.pos, r.n, r.ref, r.off, r.n_dev);
+    }
+    c->cur = cur;
+    if (r.wg_src) {
+        HIPOK(hipMemcpyAsync(c->wg_pinned, r.wg_src, 2 * (size_t)r.wg_grid * 4, hipMemcpyDeviceToHost, c->stream));
+        c->wg_grid = r.wg_grid;
+    }
+    return 0;
+}
 // mirge_cascade_run / mirge_collapse_cascade leave their side streams unjoined; every entry point that enqueues on the main
 // stream, hands buffers back to the pool or synchronises joins them first.  mirge_count_join uses the slack: the bulk
 // group's part of the join runs before the wait, beside the small groups' cascades.
 static int join_pending_now(mirge_ctx* c) {
+    CHECK(resolve_pending_now(c));  // (in front of the wait: it runs beside what is left of the side streams' work)
     if (!c->join_pending) return 0;
     c->join_pending = false;
     return stream_join(c);
 }
 static int largest_group(const struct mirge_reads* R);
 
-static inline int grid_for(const mirge_ctx* c, size_t n, int per_block = MIRGE_BLOCK) {
+static inline int grid_for(const mirge_ctx* c, size_t n, int per_block) {
     size_t blocks = (n + per_block - 1) / per_block;
     static const size_t per_cu = std::getenv("MIRGE_GRID_PER_CU") ? (size_t)std::atoi(std::getenv("MIRGE_GRID_PER_CU")) : 8;
     size_t cap = (size_t)c->n_cu * per_cu;

@@ -40,6 +40,11 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
     // The bulk group's rows are computed before the cascade's side streams are joined (its annotation is complete in the
     // main stream's own order): k_join_rows of 4.2 M reads runs beside the tail of the small groups' cascades instead of
     // behind the wait for them.  Otherwise: everything in one launch with atomics (k_join_multi).
+    // Neither needs the bulk group's k_resolve: a miRNA read's reference comes from its position (JoinGroups::from_pos).  The
+    // main stream reads k_cascade_bulk, k_join_rows (bulk), the wait for the side streams, k_join_rows (small groups),
+    // k_join_reduce, the event the host waits for, k_resolve (bulk): its 40 us for 4.2 M reads run while the host takes the
+    // tables.  (In front of the wait they outlasted it: the small groups are ready ~10 us behind the bulk rows,
+    // profiles/tail_join_from_positions.md.)  Stream order still puts res_ref / res_off in front of every later reader.
     static const bool rows_off = std::getenv("MIRGE_JOIN_ROWS") && std::atoi(std::getenv("MIRGE_JOIN_ROWS")) == 0;  // A/B
     // `join_pending` stays set until stream_join has actually been issued: an early return below (argument check, out of
     // memory) then leaves the side streams to the next entry point's join_pending_now instead of unjoined for good
@@ -54,13 +59,23 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         ~PoolBlock() { c->release(p); p = nullptr; }
     } partial_guard{c, partial};
     const int big = largest_group(U);
+    // positions and granule tables are this context's own cascade's, and no library has been destroyed since it ran; any other result
+    // is joined from the references it holds (resolved by then: k_resolve goes first)
+    const bool from_pos = res->ctx == c && res->lib_epoch == g_lib_epoch.load();
     auto group_list = [&](bool bulk, JoinGroups& gs) -> uint64_t {
         std::memset(&gs, 0, sizeof(gs));
+        gs.from_pos = from_pos ? 1 : 0;
+        const int32_t mirna_pass[2] = {exact_pass, iso_pass};
+        for (int k = 0; k < 2 && from_pos; k++) {
+            const int32_t p = mirna_pass[k];
+            if (p < 0 || p >= res->n_pass) continue;
+            gs.mi[k].ref_start = res->rt.ref_start[p]; gs.mi[k].coarse = res->rt.coarse[p]; gs.mi[k].n_refs = res->rt.n_refs[p];
+        }
         uint64_t total = 0;
         for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
             const ResGroup& g = res->g[gi];
             if (!g.n || (gi == big) != bulk) continue;
-            gs.pass[gs.n_groups] = g.pass; gs.ref[gs.n_groups] = g.ref; gs.counts[gs.n_groups] = U->g[gi].counts;
+            gs.pass[gs.n_groups] = g.pass; gs.ref[gs.n_groups] = g.ref; gs.pos[gs.n_groups] = g.pos; gs.counts[gs.n_groups] = U->g[gi].counts;
             gs.start[gs.n_groups++] = (uint32_t)total;
             total += g.n;
         }
@@ -75,6 +90,7 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         const uint32_t rows_b = n_bulk ? (uint32_t)std::min<uint64_t>((uint64_t)c->n_cu, (n_bulk + 4095) / 4096) : 0u;
         const uint32_t rows_s = n_small ? (uint32_t)std::min<uint64_t>((uint64_t)c->n_cu, (n_small + 4095) / 4096) : 0u;
         CHECK(dalloc(c, &partial, (size_t)(rows_b + rows_s) * words));
+        if (!from_pos) CHECK(resolve_pending_now(c));
         if (rows_b) {
             LaunchScope ls(c, "k_join", (double)n_bulk);
             hipLaunchKernelGGL(k_join_rows, dim3(rows_b), dim3(MIRGE_JOIN_ROWS_THREADS), words * 8, c->stream, gb, S, P, exact_pass, iso_pass,
@@ -91,6 +107,7 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         hipLaunchKernelGGL(k_join_reduce, dim3((unsigned)((words + 63) / 64)), dim3(1024), 0, c->stream, partial, rows_b + rows_s, (uint32_t)words, d,
                            c->join_pinned);
     } else {
+        if (!from_pos) CHECK(resolve_pending_now(c));
         CHECK(join_side_streams());
         for (JoinGroups* gs : {&gb, &gsm}) {
             const uint64_t total = gs == &gb ? n_bulk : n_small;
@@ -106,6 +123,8 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         HIPOK(hipMemcpyAsync(c->join_pinned, d, words * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPOK(hipEventRecord(c->ev_meta, c->stream));
+    // the bulk group's k_resolve: behind the event the host waits for, in front of whatever the main stream is given next
+    CHECK(resolve_pending_now(c));
     // cleared for the next call now, behind the copy: the host waits for the copy only
     if (!by_rows) cleared = hipMemsetAsync(d, 0, c->join_dev_words * 8, c->stream) == hipSuccess;
     hc.lap("enqueue");

@@ -4,6 +4,9 @@
 // library: 2-bit text + invalid bitmap + per-k tables
 // ------------------------------------------------------------------------------------------
 static std::atomic<uint64_t> g_lib_uid{1};
+// counts the libraries destroyed so far: a cascade result remembers the granule tables of its libraries (mirge_result::rt) and the
+// count join reads them only while no library has gone since (otherwise it reads the references k_resolve wrote)
+static std::atomic<uint64_t> g_lib_epoch{0};
 
 struct mirge_lib {
     mirge_ctx* ctx = nullptr;
@@ -122,6 +125,8 @@ static int lib_upload(mirge_ctx* c, std::unique_ptr<mirge_lib>& L, int64_t n_ref
 extern "C" void mirge_lib_destroy(mirge_lib* L) {
     if (!L) return;
     (void)hipSetDevice(L->ctx->device);
+    (void)resolve_pending_now(L->ctx);  // a deferred k_resolve reads this library's granule table
+    g_lib_epoch.fetch_add(1);
     (void)hipStreamSynchronize(L->ctx->stream);
     (void)hipFree(L->dT); (void)hipFree(L->dinv); (void)hipFree(L->dref_start); (void)hipFree(L->dcoarse); (void)hipFree(L->dtables);
     for (auto& t : L->htables) { (void)hipFree((void*)t.bucket); (void)hipFree((void*)t.pos); (void)hipFree((void*)((uintptr_t)t.bits & ~(uintptr_t)3)); }
