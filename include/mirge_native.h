@@ -481,6 +481,37 @@ int mirge_bam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
                            const char* bai_path, const char* header, int64_t header_len, int32_t threads, int64_t* n_records_out,
                            int64_t* n_stream_bytes_out, int64_t* n_file_bytes_out);
 
+/* ---- the sequence work behind the tRNA fragment report (the reference's -trf: summary.py:1060-1220, mirge2_tRF_a2i.py:22-62)
+ * mirge_trf_hits_run  every best-stratum alignment (bowtie -a --best --strata) of the tRNA reads rows[n_rows] (handle indices of `uniq`;
+ *                     a record's row is the index INTO rows).  A read the cascade gave to mature_pass: every forward window of
+ *                     mature_lib whose total mismatches equal the read's stratum (the result's mm; N in the read is a mismatch, a
+ *                     window over a separator or a reference N is no hit).  A read of primary_pass: every exact window of the read
+ *                     without its T{3,}$ run in primary_lib.  Both policies are -v policies without trims.  The probe tables the rows
+ *                     need are built on first use.  anticodon[mature references] = 0-based start of the anticodon.  Records
+ *                     (mirge_trf_hits_count / _fetch / _destroy) are sorted by (row, ref, off), every window once: ref / off = reference
+ *                     and 0-based offset in the class's library, mm = the stratum, cls = 0 mature / 1 primary, type = trfTypes
+ *                     (summary.py:649-674) decided by the class: 0 tRF-whole, 1 5'-half, 2 5'-tRF, 3 3'-half, 4 3'-tRF, 5 i-tRF, 6 tRF-1.
+ * mirge_trf_assign    assign_cluster / getDistance2 for n_rows report rows: read[] = handle index of the row's read, tref[] = the row's
+ *                     reference as an index into ref_ptr[n_tref + 1] (a CSR over the n_trf predefined tRFs; -1: the reference has none),
+ *                     start[] = 1-based start.  tRF k: its dashed string str[str_off[k] .. str_off[k + 1]) as text, its coordinate()
+ *                     pair c_start / c_end, and rank = the rank of its cluster name in string order.  dist[] / trf[] = the minimum of
+ *                     (distance, rank) and its tRF index; 100 / -1 for a reference without tRFs.  Distance = |start difference| + |end
+ *                     difference| (the row's end coordinate is start - 1 + len(read), T run included) + positions where both strings
+ *                     hold a letter and differ (as text: N equals only N) + every letter of the row at or beyond len(string). */
+typedef struct mirge_trf_hits mirge_trf_hits;
+int mirge_trf_hits_run(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, int32_t mature_pass, const mirge_lib* mature_lib,
+                       const mirge_policy* mature_pol, int32_t primary_pass, const mirge_lib* primary_lib, const mirge_policy* primary_pol,
+                       const int64_t* rows, int64_t n_rows, const int32_t* anticodon, mirge_trf_hits** out);
+int64_t mirge_trf_hits_count(const mirge_trf_hits* hits);
+int mirge_trf_hits_fetch(const mirge_trf_hits* hits, uint32_t* row, uint32_t* ref, int32_t* off, uint8_t* mm, uint8_t* cls, uint8_t* type);
+void mirge_trf_hits_destroy(mirge_trf_hits* hits);
+int mirge_trf_assign(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, int64_t n_rows, const int64_t* read,
+                     const int32_t* tref, const int32_t* start, int64_t n_tref, const int64_t* ref_ptr, int64_t n_trf,
+                     const int64_t* str_off, const char* str, const int32_t* c_start, const int32_t* c_end, const int32_t* rank,
+                     int32_t* dist, int32_t* trf);
+/* out[n_rows][n_samples] = the count matrix of `uniq` for the reads rows[] alone (the report's rows: no fetch of the whole matrix) */
+int mirge_trf_row_counts(mirge_ctx* ctx, const mirge_reads* uniq, const int64_t* rows, int64_t n_rows, uint32_t* out);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

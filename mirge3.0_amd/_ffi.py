@@ -31,6 +31,7 @@ EXPORTS = [
     "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
     "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device",
+    "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
 ]
 
 
@@ -115,6 +116,9 @@ def load() -> C.CDLL:
     if hasattr(lib, "mirge_loci_count"):  # absent from an older A/B build (MIRGE_NATIVE_SO)
         lib.mirge_loci_count.restype = C.c_int64
         lib.mirge_loci_destroy.restype = None
+    if hasattr(lib, "mirge_trf_hits_count"):
+        lib.mirge_trf_hits_count.restype = C.c_int64
+        lib.mirge_trf_hits_destroy.restype = None
     _lib = lib
     return lib
 
@@ -908,6 +912,64 @@ def loci_cluster(ctx: Context, ref, off, strand, query, qlen, qcount, ref_skip, 
                                      *(_p(tab[k]) for k in ("ref", "strand", "start", "end", "reads", "members"))), "mirge_loci_cluster")
     out = {k: v[:nc.value] for k, v in tab.items()}
     out["cluster"] = cluster[:n]
+    return out
+
+
+TRF_TYPES = ("tRF-whole", "5'-half", "5'-tRF", "3'-half", "3'-tRF", "i-tRF", "tRF-1")  # csrc/kernels_trf.hpp: MIRGE_TRF_*
+TRF_NO_DIST = 100
+
+
+def trf_hits(ctx: Context, uniq: DeviceReads, res: CascadeResult, mature_pass: int, mature_lib: DeviceLibrary, mature_pol: MirgePolicy,
+             primary_pass: int, primary_lib: DeviceLibrary, primary_pol: MirgePolicy, rows, anticodon) -> dict:
+    """``mirge_trf_hits_run``: every best-stratum alignment of the tRNA reads ``rows`` (handle indices of ``uniq``) -> ``row`` (uint32,
+    index into ``rows``), ``ref`` (uint32), ``off`` (int32, 0-based), ``mm``, ``cls`` (0 mature, 1 primary), ``type`` (index into
+    ``TRF_TYPES``) per window, sorted by (row, ref, off).  ``anticodon``: 0-based anticodon start of every mature reference."""
+    lib = load()
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    anticodon = np.ascontiguousarray(anticodon, dtype=np.int32)
+    if anticodon.shape[0] != mature_lib.n_refs:
+        raise ValueError("one anticodon start per mature reference")
+    h = C.c_void_p()
+    _check(lib.mirge_trf_hits_run(ctx._h, uniq._h, res._h, C.c_int32(mature_pass), mature_lib._h, C.byref(mature_pol),
+                                  C.c_int32(primary_pass), primary_lib._h, C.byref(primary_pol),
+                                  _p(rows) if rows.size else C.c_void_p(0), C.c_int64(rows.shape[0]),
+                                  _p(anticodon) if anticodon.size else C.c_void_p(0), C.byref(h)), "mirge_trf_hits_run")
+    try:
+        m = int(lib.mirge_trf_hits_count(h))
+        out = dict(row=np.zeros(m, np.uint32), ref=np.zeros(m, np.uint32), off=np.zeros(m, np.int32), mm=np.zeros(m, np.uint8),
+                   cls=np.zeros(m, np.uint8), type=np.zeros(m, np.uint8))
+        if m:
+            _check(lib.mirge_trf_hits_fetch(h, *(_p(out[k]) for k in ("row", "ref", "off", "mm", "cls", "type"))), "mirge_trf_hits_fetch")
+    finally:
+        lib.mirge_trf_hits_destroy(h)
+    return out
+
+
+def trf_assign(ctx: Context, uniq: DeviceReads, res: CascadeResult, read, tref, start, ref_ptr, strings: Sequence[bytes], c_start, c_end,
+               rank):
+    """``mirge_trf_assign``: per report row (``read`` = handle index, ``tref`` = index into the CSR ``ref_ptr`` over the predefined
+    tRFs or -1, ``start`` 1-based) -> (``dist`` int32, ``trf`` int32 index or -1).  ``strings``: the tRFs' dashed strings."""
+    read = np.ascontiguousarray(read, dtype=np.int64)
+    tref, start = (np.ascontiguousarray(a, dtype=np.int32) for a in (tref, start))
+    ref_ptr = np.ascontiguousarray(ref_ptr, dtype=np.int64)
+    c_start, c_end, rank = (np.ascontiguousarray(a, dtype=np.int32) for a in (c_start, c_end, rank))
+    n, n_trf = read.shape[0], len(strings)
+    str_off = np.zeros(n_trf + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in strings], out=str_off[1:])
+    blob = np.frombuffer(b"".join(strings) or b"\0", dtype=np.uint8)
+    dist, trf = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    _check(load().mirge_trf_assign(ctx._h, uniq._h, res._h, C.c_int64(n), _p(read), _p(tref), _p(start), C.c_int64(max(ref_ptr.shape[0] - 1, 0)),
+                                   _p(ref_ptr), C.c_int64(n_trf), _p(str_off), _p(blob), _p(c_start), _p(c_end), _p(rank), _p(dist),
+                                   _p(trf)), "mirge_trf_assign")
+    return dist[:n], trf[:n]
+
+
+def trf_row_counts(ctx: Context, uniq: DeviceReads, rows) -> np.ndarray:
+    """``mirge_trf_row_counts``: the count matrix of the reads ``rows`` alone -> uint32 [len(rows), samples]"""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    out = np.zeros((rows.shape[0], max(uniq.n_samples, 1)), dtype=np.uint32)
+    if rows.size:
+        _check(load().mirge_trf_row_counts(ctx._h, uniq._h, _p(rows), C.c_int64(rows.shape[0]), _p(out)), "mirge_trf_row_counts")
     return out
 
 

@@ -112,6 +112,11 @@ def parse_args(argv=None):
                     help="write <sample>_sorted.bam and <sample>_sorted.bai for every sample: the records of --sam-out's <sample>.sam as "
                          "BAM, coordinate-sorted, BGZF-compressed and indexed on the device (what the reference's -bam gets from samtools "
                          "view / sort / index); needs --sam-header FILE with the genome's @SQ lines; independent of --sam-out")
+    ap.add_argument("--trf-report", dest="trf_report", action="store_true",
+                    help="write the tRNA fragment reports of the reference's -trf up to its per-sample reports: tRFs.aligned.report.tsv, "
+                         "tRF.Counts.csv, tRF.RP100K.csv, discarded.reads.summary.assigningtRFs.csv and tRFs.samples.tmp/<sample>."
+                         "aligned_tRFs.report / .summary.report; every best-stratum alignment of the tRNA reads and their assignment to "
+                         "the predefined tRFs are computed on the device (the clustering files behind them stay out of scope)")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -180,6 +185,8 @@ def parse_args(argv=None):
         ap.error("--sorted-bam requires --sam-header FILE with the @SQ SN:/LN: lines of the genome the libraries were built on")
     if args.sam_out and (args.save_pkl or args.resume or args.backend == "bowtie"):
         ap.error("--sam-out runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+    if args.trf_report and (args.save_pkl or args.resume or args.backend == "bowtie"):
+        ap.error("--trf-report runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.sam_header and not os.path.isfile(args.sam_header):
         ap.error(f"--sam-header: {args.sam_header} is not a file")
     if args.sorted_bam:
@@ -281,6 +288,8 @@ def main(argv=None):
         sys.exit("--sam-out is a single-process option")
     if world > 1 and args.sorted_bam:
         sys.exit("--sorted-bam is a single-process option")
+    if world > 1 and args.trf_report:
+        sys.exit("--trf-report is a single-process option")
     if not (Path(args.libraries_path) / args.organism_name / "index.Libs").exists():
         sys.exit("\n ERROR: The path to miRge libraries is incorrect or does not exist!\n")
     if args.organism_name == "hamster":  # mirge/__main__.py:61-64

@@ -1,0 +1,266 @@
+// native_trf.hpp -- part of mirge_native.hip (one translation unit): the two device calls behind the tRNA fragment report
+// (kernels_trf.hpp).  mirge_trf_hits: the rows' probe tables made sure of, a counting pass, one exclusive scan, the writing pass into
+// every row's own stretch, one radix sort of (row, global position) keys, the records finished and copied to the host.
+// mirge_trf_assign: the predefined tRFs uploaded as one CSR, one kernel over the rows.
+#pragma once
+
+struct mirge_trf_hits {  // on the host: the records in (row, reference, offset) order
+    std::vector<uint32_t> row, ref;
+    std::vector<int32_t> off;
+    std::vector<uint8_t> mm, cls, type;
+};
+
+extern "C" void mirge_trf_hits_destroy(mirge_trf_hits* h) { delete h; }
+extern "C" int64_t mirge_trf_hits_count(const mirge_trf_hits* h) { return h ? (int64_t)h->row.size() : 0; }
+extern "C" int mirge_trf_hits_fetch(const mirge_trf_hits* h, uint32_t* row, uint32_t* ref, int32_t* off, uint8_t* mm, uint8_t* cls, uint8_t* type) {
+    if (!h) return fail(-1, "mirge_trf_hits_fetch: bad argument");
+    const size_t n = h->row.size();
+    if (n && (!row || !ref || !off || !mm || !cls || !type)) return fail(-1, "mirge_trf_hits_fetch: bad argument");
+    if (n) {
+        std::memcpy(row, h->row.data(), n * 4); std::memcpy(ref, h->ref.data(), n * 4); std::memcpy(off, h->off.data(), n * 4);
+        std::memcpy(mm, h->mm.data(), n); std::memcpy(cls, h->cls.data(), n); std::memcpy(type, h->type.data(), n);
+    }
+    return 0;
+}
+
+// the read groups and the cascade's answer (res == nullptr: none) as the tRF kernels read them
+static int trf_groups(const std::string& who, const mirge_reads* U, const mirge_result* res, TrfTables& t) {
+    if (res && res->n != U->n) return fail(-1, who + ": result and read set differ");
+    static_assert(MIRGE_TRF_MAXG == MIRGE_NGROUPS, "read groups");
+    for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
+        const ReadGroup& g = U->g[gi];
+        if (g.n && g.orig) return fail(-1, who + ": the read set is not a collapse result");
+        if (res && g.n != res->g[gi].n && !res->dmeta) return fail(-1, who + ": result and read set differ");
+        t.g[gi] = TrfGroup{g.seq, g.nmask, g.len, res ? res->g[gi].pass : nullptr, res ? res->g[gi].mm : nullptr, g.counts, g.base, g.n,
+                           is_long_group(gi) ? 0 : g.W, 0};
+    }
+    return 0;
+}
+
+extern "C" int mirge_trf_hits_run(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, int32_t mature_pass, const mirge_lib* mature_lib,
+                                  const mirge_policy* mature_pol, int32_t primary_pass, const mirge_lib* primary_lib,
+                                  const mirge_policy* primary_pol, const int64_t* rows, int64_t n_rows, const int32_t* anticodon,
+                                  mirge_trf_hits** out) {
+    const std::string who = "mirge_trf_hits_run";
+    if (!c || !U || !res || !out || !mature_lib || !mature_pol || !primary_lib || !primary_pol || n_rows < 0 || (n_rows && !rows) ||
+        (mature_lib->n_refs && !anticodon) || mature_pass < 0 || primary_pass < 0 || mature_pass == primary_pass ||
+        mature_pass >= res->n_pass || primary_pass >= res->n_pass)
+        return fail(-1, who + ": bad argument");
+    if (n_rows >= 0x7FFFFFF0ll) return fail(-5, who + ": too many rows for one call");
+    // offsets are reported as the window's start in the reference and the stratum is a TOTAL mismatch count: end-to-end policies
+    // without a 5' trim (the two tRNA passes, manifoldAlign.py:85)
+    for (const mirge_policy* p : {mature_pol, primary_pol})
+        if (p->mode != 1 || p->trim5 || p->trim3 || p->mm < 0 || p->mm > 2 || p->maxtotal != p->mm) return fail(-1, who + ": not a -v policy without trims");
+    std::unique_ptr<mirge_trf_hits> hits(new mirge_trf_hits);
+    if (n_rows == 0) { *out = hits.release(); return 0; }
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    TrfTables t;
+    std::memset(&t, 0, sizeof(t));
+    CHECK(trf_groups(who, U, res, t));
+    std::vector<uint32_t> r32((size_t)n_rows);
+    for (int64_t k = 0; k < n_rows; k++) {
+        if (rows[k] < 0 || rows[k] >= U->n) return fail(-1, who + ": row index out of range");
+        r32[(size_t)k] = (uint32_t)rows[k];
+    }
+    // every probe table the rows can ask for (the cascade may have answered these passes from whole-read tables or a merged library)
+    int32_t hist[MIRGE_MAX_READ_LEN + 1];
+    reads_lengths_present(U, hist);
+    CHECK(prepare_tables(const_cast<mirge_lib*>(mature_lib), *mature_pol, hist, false));
+    CHECK(prepare_tables(const_cast<mirge_lib*>(primary_lib), *primary_pol, hist, false));
+    t.cls[0].lib = mature_lib->view(); t.cls[1].lib = primary_lib->view();
+    std::memcpy(&t.cls[0].pol, mature_pol, sizeof(MirgePolicy)); std::memcpy(&t.cls[1].pol, primary_pol, sizeof(MirgePolicy));
+    t.cls[0].pass = mature_pass; t.cls[1].pass = primary_pass;
+
+    const size_t n = (size_t)n_rows;
+    uint32_t *d_rows = nullptr, *d_flags = nullptr, *d_row = nullptr, *d_ref = nullptr;
+    int32_t *d_ac = nullptr, *d_off = nullptr;
+    unsigned long long *d_cnt = nullptr, *d_start = nullptr, *d_keys = nullptr, *d_keys2 = nullptr;
+    uint8_t *d_mm = nullptr, *d_cls = nullptr, *d_type = nullptr;
+    void* d_tmp = nullptr;
+    auto hits_pass = [&](bool write) {
+        for (int W : {1, 2, 4, 8}) {
+            bool present = false;
+            for (int gi = 0; gi < MIRGE_NGROUPS; gi++) present = present || (t.g[gi].n && t.g[gi].W == W);
+            if (!present) continue;
+            LaunchScope ls(c, write ? "k_trf_hits_write" : "k_trf_hits_count", (double)n);
+            const dim3 grid(grid_for(c, n)), block(MIRGE_BLOCK);
+#define MIRGE_TRF_LAUNCH(WW)                                                                                                              \
+    if (write) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_hits<WW, true>), grid, block, 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n, \
+                                  d_cnt, (const unsigned long long*)d_start, d_keys, d_flags);                                            \
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_hits<WW, false>), grid, block, 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n,    \
+                            d_cnt, (const unsigned long long*)d_start, d_keys, d_flags)
+            switch (W) {
+                case 1: MIRGE_TRF_LAUNCH(1); break;
+                case 2: MIRGE_TRF_LAUNCH(2); break;
+                case 4: MIRGE_TRF_LAUNCH(4); break;
+                default: MIRGE_TRF_LAUNCH(8); break;
+            }
+#undef MIRGE_TRF_LAUNCH
+        }
+    };
+    auto run = [&]() -> int {
+        const size_t n_ac = std::max<size_t>((size_t)mature_lib->n_refs, 1);
+        CHECK(dalloc(c, &d_rows, n)); CHECK(dalloc(c, &d_flags, 16)); CHECK(dalloc(c, &d_ac, n_ac));
+        CHECK(dalloc(c, &d_cnt, n + 1)); CHECK(dalloc(c, &d_start, n + 1));
+        HIPOK(hipMemcpyAsync(d_rows, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        if (mature_lib->n_refs) HIPOK(hipMemcpyAsync(d_ac, anticodon, (size_t)mature_lib->n_refs * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemsetAsync(d_flags, 0, 64, c->stream));
+        HIPOK(hipMemsetAsync(d_cnt, 0, (n + 1) * 8, c->stream));
+        t.anticodon = d_ac;
+        hits_pass(false);
+        size_t tb = 0;
+        HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt, d_start, (int)(n + 1), c->stream));
+        CHECK(c->alloc(&d_tmp, std::max<size_t>(tb, 16)));
+        HIPOK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_cnt, d_start, (int)(n + 1), c->stream));
+        unsigned long long n_rec = 0;
+        uint32_t flag = 0;
+        HIPOK(hipMemcpyAsync(&n_rec, d_start + n, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        if (flag & 1u) return fail(-1, who + ": a row is neither a mature-tRNA nor a primary-tRNA read");
+        if (flag & 4u) return fail(-1, who + ": a probe table is missing");
+        if (n_rec >= 0x7FFFFFF0ull) return fail(-5, who + ": " + std::to_string(n_rec) + " alignments to report in one call");
+        if (n_rec == 0) return 0;
+        CHECK(dalloc(c, &d_keys, (size_t)n_rec)); CHECK(dalloc(c, &d_keys2, (size_t)n_rec));
+        hits_pass(true);
+        // ---- (row, global position) ascending = (row, reference, offset)
+        int rbits = 1;
+        while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
+        size_t tb2 = 0;
+        HIPOK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb2, d_keys, d_keys2, (int)n_rec, 0, 32 + rbits, c->stream));
+        if (tb2 > std::max<size_t>(tb, 16)) { c->release(d_tmp); d_tmp = nullptr; CHECK(c->alloc(&d_tmp, tb2)); }
+        HIPOK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb2, d_keys, d_keys2, (int)n_rec, 0, 32 + rbits, c->stream));
+        CHECK(dalloc(c, &d_row, (size_t)n_rec)); CHECK(dalloc(c, &d_ref, (size_t)n_rec)); CHECK(dalloc(c, &d_off, (size_t)n_rec));
+        CHECK(dalloc(c, &d_mm, (size_t)n_rec)); CHECK(dalloc(c, &d_cls, (size_t)n_rec)); CHECK(dalloc(c, &d_type, (size_t)n_rec));
+        {
+            LaunchScope ls(c, "k_trf_finish", (double)n_rec);
+            hipLaunchKernelGGL(k_trf_finish, dim3(grid_for(c, (size_t)n_rec)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows,
+                               (const unsigned long long*)d_keys2, (uint32_t)n_rec, d_row, d_ref, d_off, d_mm, d_cls, d_type);
+        }
+        hits->row.resize(n_rec); hits->ref.resize(n_rec); hits->off.resize(n_rec); hits->mm.resize(n_rec); hits->cls.resize(n_rec); hits->type.resize(n_rec);
+        HIPOK(hipMemcpyAsync(hits->row.data(), d_row, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(hits->ref.data(), d_ref, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(hits->off.data(), d_off, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(hits->mm.data(), d_mm, n_rec, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(hits->cls.data(), d_cls, n_rec, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(hits->type.data(), d_type, n_rec, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        if (flag) return fail(-1, who + ": the writing pass and the counting pass disagree");
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(c->stream);
+    c->drain();
+    for (void* p : {(void*)d_rows, (void*)d_flags, (void*)d_row, (void*)d_ref, (void*)d_ac, (void*)d_off, (void*)d_cnt, (void*)d_start,
+                    (void*)d_keys, (void*)d_keys2, (void*)d_mm, (void*)d_cls, (void*)d_type, d_tmp})
+        c->release(p);
+    if (rc) return rc;
+    *out = hits.release();
+    return 0;
+}
+
+extern "C" int mirge_trf_assign(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, int64_t n_rows, const int64_t* read,
+                                const int32_t* tref, const int32_t* start, int64_t n_tref, const int64_t* ref_ptr, int64_t n_trf,
+                                const int64_t* str_off, const char* str, const int32_t* c_start, const int32_t* c_end, const int32_t* rank,
+                                int32_t* dist, int32_t* trf) {
+    const std::string who = "mirge_trf_assign";
+    if (!c || !U || !res || n_rows < 0 || n_tref < 0 || n_trf < 0 || (n_rows && (!read || !tref || !start || !dist || !trf)) ||
+        (n_tref && !ref_ptr) || (n_trf && (!str_off || !c_start || !c_end || !rank)) || n_rows >= 0x7FFFFFF0ll || n_tref >= 0x7FFFFFF0ll ||
+        n_trf >= 0x7FFFFFF0ll)
+        return fail(-1, who + ": bad argument");
+    if (n_rows == 0) return 0;
+    const int64_t n_str = n_trf ? str_off[n_trf] : 0;
+    if (n_str < 0 || n_str >= 0x7FFFFFF0ll || (n_str && !str) || (n_trf && str_off[0] != 0)) return fail(-1, who + ": the tRF strings are malformed");
+    for (int64_t k = 0; k < n_trf; k++)
+        if (str_off[k + 1] < str_off[k]) return fail(-1, who + ": the tRF strings are malformed");
+    for (int64_t r = 0; r < n_tref; r++)
+        if (ref_ptr[r] < 0 || ref_ptr[r + 1] < ref_ptr[r] || ref_ptr[r + 1] > n_trf) return fail(-1, who + ": the tRF table is malformed");
+    std::vector<uint32_t> r32((size_t)n_rows), p32((size_t)n_tref + 1, 0u), o32((size_t)n_trf + 1, 0u);
+    for (int64_t k = 0; k < n_rows; k++) {
+        if (read[k] < 0 || read[k] >= U->n || tref[k] >= n_tref || start[k] < 1) return fail(-1, who + ": a row is out of range");
+        r32[(size_t)k] = (uint32_t)read[k];
+    }
+    for (int64_t r = 0; r <= n_tref && n_tref; r++) p32[(size_t)r] = (uint32_t)ref_ptr[r];
+    for (int64_t k = 0; k <= n_trf && n_trf; k++) o32[(size_t)k] = (uint32_t)str_off[k];
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    TrfTables t;
+    std::memset(&t, 0, sizeof(t));
+    CHECK(trf_groups(who, U, res, t));
+    const size_t n = (size_t)n_rows, nt = (size_t)n_trf;
+    uint32_t *d_read = nullptr, *d_ptr = nullptr, *d_soff = nullptr;
+    int32_t *d_tref = nullptr, *d_start = nullptr, *d_cs = nullptr, *d_ce = nullptr, *d_rank = nullptr, *d_dist = nullptr, *d_trf = nullptr;
+    uint8_t* d_str = nullptr;
+    auto run = [&]() -> int {
+        CHECK(dalloc(c, &d_read, n)); CHECK(dalloc(c, &d_tref, n)); CHECK(dalloc(c, &d_start, n)); CHECK(dalloc(c, &d_dist, n)); CHECK(dalloc(c, &d_trf, n));
+        CHECK(dalloc(c, &d_ptr, (size_t)n_tref + 1)); CHECK(dalloc(c, &d_soff, nt + 1)); CHECK(dalloc(c, &d_str, (size_t)n_str + 16));
+        CHECK(dalloc(c, &d_cs, nt + 1)); CHECK(dalloc(c, &d_ce, nt + 1)); CHECK(dalloc(c, &d_rank, nt + 1));
+        HIPOK(hipMemcpyAsync(d_read, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_tref, tref, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_start, start, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_ptr, p32.data(), ((size_t)n_tref + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_soff, o32.data(), (nt + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (n_str) HIPOK(hipMemcpyAsync(d_str, str, (size_t)n_str, hipMemcpyHostToDevice, c->stream));
+        if (nt) {
+            HIPOK(hipMemcpyAsync(d_cs, c_start, nt * 4, hipMemcpyHostToDevice, c->stream));
+            HIPOK(hipMemcpyAsync(d_ce, c_end, nt * 4, hipMemcpyHostToDevice, c->stream));
+            HIPOK(hipMemcpyAsync(d_rank, rank, nt * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        TrfInfor f{d_ptr, d_soff, d_str, d_cs, d_ce, d_rank, (uint32_t)n_tref, (uint32_t)n_trf};
+        {
+            LaunchScope ls(c, "k_trf_assign", (double)n);
+            hipLaunchKernelGGL(k_trf_assign, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, f, (const uint32_t*)d_read, (const int32_t*)d_tref,
+                               (const int32_t*)d_start, (uint32_t)n, d_dist, d_trf);
+        }
+        HIPOK(hipMemcpyAsync(dist, d_dist, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(trf, d_trf, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(c->stream);  // (also when a call failed: the host vectors above leave scope)
+    c->drain();
+    for (void* p : {(void*)d_read, (void*)d_ptr, (void*)d_soff, (void*)d_tref, (void*)d_start, (void*)d_cs, (void*)d_ce, (void*)d_rank,
+                    (void*)d_dist, (void*)d_trf, (void*)d_str})
+        c->release(p);
+    return rc;
+}
+
+extern "C" int mirge_trf_row_counts(mirge_ctx* c, const mirge_reads* U, const int64_t* rows, int64_t n_rows, uint32_t* out) {
+    const std::string who = "mirge_trf_row_counts";
+    if (!c || !U || n_rows < 0 || (n_rows && (!rows || !out)) || U->n_samples < 1) return fail(-1, who + ": bad argument");
+    if ((unsigned long long)n_rows * (unsigned long long)U->n_samples >= 0x7FFFFFF0ull) return fail(-5, who + ": too many rows for one call");
+    if (n_rows == 0) return 0;
+    std::vector<uint32_t> r32((size_t)n_rows);
+    for (int64_t k = 0; k < n_rows; k++) {
+        if (rows[k] < 0 || rows[k] >= U->n) return fail(-1, who + ": row index out of range");
+        r32[(size_t)k] = (uint32_t)rows[k];
+    }
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    TrfTables t;
+    std::memset(&t, 0, sizeof(t));
+    CHECK(trf_groups(who, U, nullptr, t));
+    const size_t n = (size_t)n_rows, total = n * (size_t)U->n_samples;
+    uint32_t *d_rows = nullptr, *d_out = nullptr;
+    auto run = [&]() -> int {
+        CHECK(dalloc(c, &d_rows, n)); CHECK(dalloc(c, &d_out, total));
+        HIPOK(hipMemcpyAsync(d_rows, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        {
+            LaunchScope ls(c, "k_trf_row_counts", (double)total);
+            hipLaunchKernelGGL(k_trf_row_counts, dim3(grid_for(c, total)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n,
+                               (int32_t)U->n_samples, d_out);
+        }
+        HIPOK(hipMemcpyAsync(out, d_out, total * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(c->stream);
+    c->drain();
+    c->release(d_rows); c->release(d_out);
+    return rc;
+}
