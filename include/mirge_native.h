@@ -512,6 +512,25 @@ int mirge_trf_assign(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result
 /* out[n_rows][n_samples] = the count matrix of `uniq` for the reads rows[] alone (the report's rows: no fetch of the whole matrix) */
 int mirge_trf_row_counts(mirge_ctx* ctx, const mirge_reads* uniq, const int64_t* rows, int64_t n_rows, uint32_t* out);
 
+/* ---- density-peak clustering of the reads stacked on a tRNA (--trf-clusters: getDistance / local_density / min_distance and the
+ * centre / halo loop of trna_deliverables, mirge2_tRF_a2i.py:122-207, 776-839)
+ * mirge_trf_cluster   n_grp groups of points as a CSR grp_ptr[n_grp + 1]; a point = a row of <sample>.aligned_tRFs.report: read[] = the
+ *                     handle index in `uniq`, off[] = its 0-based offset in the template, rp100k[] = its RP100K as the report prints
+ *                     it; tlen[n_grp] = the template's length (at most 256, or the call fails: "a template of N columns is longer than
+ *                     256"; off + len(read) <= tlen).  gauss[n_gauss] = exp(-(d / 3) ** 2) for d = 0 .. n_gauss - 1, n_gauss >= 2 * the
+ *                     longest template + 1: the device evaluates no exp.  Distance of two points = |start difference| + |end
+ *                     difference| + columns where both hold a letter and the letters differ (N equals only N), from the packed words;
+ *                     it is recomputed wherever it is needed and no n x n matrix exists.  Per point, 1-based within its group:
+ *                     rho = float32 of (sum over j != i, ascending, of gauss[d] * rp100k[j], + rp100k[i]) in doubles, product and sum
+ *                     rounded separately; order = the 0-based position in the order ascending (-rho, index); delta / nneigh = the
+ *                     nearest point ahead in that order, of equal distances the last (nneigh 0 and delta = the largest other delta, or
+ *                     0, for the first); cl = the cluster (-1: none), halo = cl or 0.  Per group nclust, and centre[grp_ptr[g] + k] =
+ *                     the centre of cluster k + 1 (0 behind the last).  Centres: rho >= 5 and delta >= 8, else the densest point when
+ *                     every delta <= 8 and its rho >= 5. */
+int mirge_trf_cluster(mirge_ctx* ctx, const mirge_reads* uniq, int64_t n_grp, const int64_t* grp_ptr, const int64_t* read, const int32_t* off,
+                      const double* rp100k, const int32_t* tlen, int64_t n_gauss, const double* gauss, float* rho, float* delta,
+                      int32_t* nneigh, int32_t* order, int32_t* cl, int32_t* halo, int32_t* nclust, int32_t* centre);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

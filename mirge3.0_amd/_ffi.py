@@ -32,6 +32,7 @@ EXPORTS = [
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
     "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device",
     "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
+    "mirge_trf_cluster",
 ]
 
 
@@ -962,6 +963,39 @@ def trf_assign(ctx: Context, uniq: DeviceReads, res: CascadeResult, read, tref, 
                                    _p(ref_ptr), C.c_int64(n_trf), _p(str_off), _p(blob), _p(c_start), _p(c_end), _p(rank), _p(dist),
                                    _p(trf)), "mirge_trf_assign")
     return dist[:n], trf[:n]
+
+
+TRF_CLUSTER_MAXCOL = 256  # csrc/kernels_trf.hpp: MIRGE_TRF_CL_MAXCOL
+
+
+def trf_gauss(max_tlen: int) -> np.ndarray:
+    """the reference's ``guass_func`` (mirge2_tRF_a2i.py:137) with dc = 3.0 for every distance two points of a template of ``max_tlen``
+    columns can have, by Python's ``math.exp``: the device looks the values up"""
+    import math
+    return np.asarray([math.exp(-(float(d) / 3.0) ** 2) for d in range(2 * int(max_tlen) + 1)], dtype=np.float64)
+
+
+def trf_cluster(ctx: Context, uniq: DeviceReads, grp_ptr, read, off, rp100k, tlen, gauss=None) -> dict:
+    """``mirge_trf_cluster``: groups of points (CSR ``grp_ptr``; per point ``read`` = handle index, ``off`` = 0-based offset in the
+    template, ``rp100k``; per group ``tlen``) -> per point ``rho`` / ``delta`` (float32), ``nneigh`` / ``order`` / ``cl`` / ``halo`` /
+    ``centre`` (int32), per group ``nclust``: see include/mirge_native.h"""
+    grp_ptr, read = (np.ascontiguousarray(a, dtype=np.int64) for a in (grp_ptr, read))
+    off, tlen = (np.ascontiguousarray(a, dtype=np.int32) for a in (off, tlen))
+    rp100k = np.ascontiguousarray(rp100k, dtype=np.float64)
+    n_grp, n = grp_ptr.shape[0] - 1, read.shape[0]
+    if n_grp < 0 or int(grp_ptr[-1]) != n or off.shape[0] != n or rp100k.shape[0] != n or tlen.shape[0] != n_grp:
+        raise ValueError("trf_cluster: the arrays do not fit the group table")
+    if gauss is None:
+        gauss = trf_gauss(int(tlen.max()) if n_grp else 1)
+    gauss = np.ascontiguousarray(gauss, dtype=np.float64)
+    out = dict(rho=np.zeros(max(n, 1), np.float32), delta=np.zeros(max(n, 1), np.float32))
+    for k in ("nneigh", "order", "cl", "halo", "centre"):
+        out[k] = np.zeros(max(n, 1), np.int32)
+    out["nclust"] = np.zeros(max(n_grp, 1), np.int32)
+    _check(load().mirge_trf_cluster(ctx._h, uniq._h, C.c_int64(n_grp), _p(grp_ptr), _p(read), _p(off), _p(rp100k), _p(tlen),
+                                    C.c_int64(gauss.shape[0]), _p(gauss), *(_p(out[k]) for k in ("rho", "delta", "nneigh", "order", "cl", "halo",
+                                                                                                 "nclust", "centre"))), "mirge_trf_cluster")
+    return {k: (a[:n_grp] if k == "nclust" else a[:n]) for k, a in out.items()}
 
 
 def trf_row_counts(ctx: Context, uniq: DeviceReads, rows) -> np.ndarray:

@@ -10,7 +10,8 @@ scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignor
 ``a2IEditing.*`` files with ``-ai``, ``<sample>_umiCounts.csv`` with ``-udd``, ``unmapped_tmp/`` with ``--unmapped-clusters``
 (FASTA files, the genome SAM and ``<sample>_clusters.tsv``) and ``--unmapped-align`` (the cluster filter's two files, the
 cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences) and ``--unmapped-features``
-(``<sample>_features.tsv``, ``_cluster.txt``, ``_precursor.fa``)).
+(``<sample>_features.tsv``, ``_cluster.txt``, ``_precursor.fa``), the tRNA fragment reports with ``--trf-report`` and the two
+clustering files per sample behind them with ``--trf-clusters``).
 
 One process: all samples on one GPU, byte-compatible outputs.  Under ``torch.distributed.run`` with N
 ranks: samples are sharded one per GPU (multigpu.py); rank 0 gathers each sample's count columns and its
@@ -116,7 +117,11 @@ def parse_args(argv=None):
                     help="write the tRNA fragment reports of the reference's -trf up to its per-sample reports: tRFs.aligned.report.tsv, "
                          "tRF.Counts.csv, tRF.RP100K.csv, discarded.reads.summary.assigningtRFs.csv and tRFs.samples.tmp/<sample>."
                          "aligned_tRFs.report / .summary.report; every best-stratum alignment of the tRNA reads and their assignment to "
-                         "the predefined tRFs are computed on the device (the clustering files behind them stay out of scope)")
+                         "the predefined tRFs are computed on the device (--trf-clusters adds the clustering files behind them)")
+    ap.add_argument("--trf-clusters", dest="trf_clusters", action="store_true",
+                    help="implies --trf-report, then clusters each sample's reads on every tRNA by density peaks on the device and writes "
+                         "the rest of the reference's -trf: tRFs.samples.tmp/<sample>.aligned_tRFs.clusters.detail and <sample>.tRFs."
+                         "report.tsv (a tRNA or primary tRNA of more than 256 nt is refused before anything is written)")
     ap.add_argument("-cpu", "--threads", dest="threads", type=int, default=0, help="accepted; only -ai's bowtie runs use it")
     ap.add_argument("--device", type=int, default=None)
     ap.add_argument("--backend", choices=("gpu", "bowtie"), default="gpu",
@@ -185,8 +190,11 @@ def parse_args(argv=None):
         ap.error("--sorted-bam requires --sam-header FILE with the @SQ SN:/LN: lines of the genome the libraries were built on")
     if args.sam_out and (args.save_pkl or args.resume or args.backend == "bowtie"):
         ap.error("--sam-out runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+    if args.trf_clusters:
+        args.trf_report = True
     if args.trf_report and (args.save_pkl or args.resume or args.backend == "bowtie"):
-        ap.error("--trf-report runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+        ap.error("--trf-report / --trf-clusters run on the device-resident route: not together with -spl / -rr / --backend bowtie"
+                 if args.trf_clusters else "--trf-report runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.sam_header and not os.path.isfile(args.sam_header):
         ap.error(f"--sam-header: {args.sam_header} is not a file")
     if args.sorted_bam:
@@ -289,7 +297,7 @@ def main(argv=None):
     if world > 1 and args.sorted_bam:
         sys.exit("--sorted-bam is a single-process option")
     if world > 1 and args.trf_report:
-        sys.exit("--trf-report is a single-process option")
+        sys.exit("--trf-report / --trf-clusters are single-process options")
     if not (Path(args.libraries_path) / args.organism_name / "index.Libs").exists():
         sys.exit("\n ERROR: The path to miRge libraries is incorrect or does not exist!\n")
     if args.organism_name == "hamster":  # mirge/__main__.py:61-64

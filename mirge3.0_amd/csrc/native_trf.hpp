@@ -2,6 +2,8 @@
 // (kernels_trf.hpp).  mirge_trf_hits: the rows' probe tables made sure of, a counting pass, one exclusive scan, the writing pass into
 // every row's own stretch, one radix sort of (row, global position) keys, the records finished and copied to the host.
 // mirge_trf_assign: the predefined tRFs uploaded as one CSR, one kernel over the rows.
+// mirge_trf_cluster (--trf-clusters): the points packed to their templates' columns, then density, nearest denser point and border
+// over a tile list of (group, MIRGE_BLOCK points), with the O(n) steps of the reference's loop on the host between the launches.
 #pragma once
 
 struct mirge_trf_hits {  // on the host: the records in (row, reference, offset) order
@@ -262,5 +264,133 @@ extern "C" int mirge_trf_row_counts(mirge_ctx* c, const mirge_reads* U, const in
     (void)hipStreamSynchronize(c->stream);
     c->drain();
     c->release(d_rows); c->release(d_out);
+    return rc;
+}
+
+// ---- density-peak clustering (kernels_trf.hpp: k_trf_cluster_pack, k_trf_density, k_trf_nearest, k_trf_border)
+// Per point (CSR grp_ptr over the groups), 1-based within the group as the reference's indices are: rho, delta, nneigh (0: none), order (the
+// 0-based position in sort_rho_idx), cl (-1: none), halo (0: halo or no cluster); per group nclust, and centre[grp_ptr[g] + k] = the
+// centre of cluster k + 1 (0 behind the group's last cluster).
+extern "C" int mirge_trf_cluster(mirge_ctx* c, const mirge_reads* U, int64_t n_grp, const int64_t* grp_ptr, const int64_t* read,
+                                 const int32_t* off, const double* rp100k, const int32_t* tlen, int64_t n_gauss, const double* gauss,
+                                 float* rho, float* delta, int32_t* nneigh, int32_t* order, int32_t* cl, int32_t* halo, int32_t* nclust,
+                                 int32_t* centre) {
+    const std::string who = "mirge_trf_cluster";
+    if (!c || !U || n_grp < 0 || n_grp >= 0x7FFFFFF0ll || !grp_ptr || (n_grp && (!tlen || !nclust)) || n_gauss < 1 || !gauss)
+        return fail(-1, who + ": bad argument");
+    if (grp_ptr[0] != 0) return fail(-1, who + ": the group table is malformed");
+    int max_tlen = 0;
+    for (int64_t g = 0; g < n_grp; g++) {
+        if (grp_ptr[g + 1] < grp_ptr[g]) return fail(-1, who + ": the group table is malformed");
+        if (tlen[g] < 1) return fail(-1, who + ": a template has no columns");
+        if (tlen[g] > MIRGE_TRF_CL_MAXCOL)
+            return fail(-1, who + ": a template of " + std::to_string(tlen[g]) + " columns is longer than " + std::to_string(MIRGE_TRF_CL_MAXCOL));
+        max_tlen = std::max(max_tlen, (int)tlen[g]);
+    }
+    const int64_t n_pts = grp_ptr[n_grp];
+    if (n_pts >= 0x7FFFFFF0ll) return fail(-5, who + ": too many points for one call");
+    if (n_pts && (!read || !off || !rp100k || !rho || !delta || !nneigh || !order || !cl || !halo || !centre)) return fail(-1, who + ": bad argument");
+    if (n_gauss < 2 * (int64_t)max_tlen + 1) return fail(-1, who + ": the Gaussian table ends before distance 2 * the longest template");
+    for (int64_t g = 0; g < n_grp; g++) nclust[g] = 0;
+    if (n_pts == 0) return 0;
+    const size_t n = (size_t)n_pts, ng = (size_t)n_grp;
+    std::vector<uint32_t> r32(n), p32(ng + 1), tile_grp, tile_first;
+    std::vector<int32_t> pt_tlen(n);
+    for (int64_t k = 0; k < n_pts; k++) {
+        if (read[k] < 0 || read[k] >= U->n) return fail(-1, who + ": a point's read is out of range");
+        if (!(rp100k[k] >= 0.0) || !std::isfinite(rp100k[k])) return fail(-1, who + ": a point's RP100K is not a finite number >= 0");
+        r32[(size_t)k] = (uint32_t)read[k];
+    }
+    uint32_t n_tile[2] = {0, 0};  // NW = 4, then NW = 8
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t g = 0; g < ng; g++) {
+            p32[g + 1] = (uint32_t)grp_ptr[g + 1];
+            if ((tlen[g] > 128) != (pass == 1)) continue;
+            for (int64_t k = grp_ptr[g]; k < grp_ptr[g + 1]; k++) pt_tlen[(size_t)k] = tlen[g];
+            for (int64_t f = grp_ptr[g]; f < grp_ptr[g + 1]; f += MIRGE_BLOCK) { tile_grp.push_back((uint32_t)g); tile_first.push_back((uint32_t)f); n_tile[pass]++; }
+        }
+    p32[0] = 0;
+    const size_t nt = tile_grp.size(), ngauss = (size_t)std::min<int64_t>(n_gauss, MIRGE_TRF_CL_MAXG);
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    TrfTables t;
+    std::memset(&t, 0, sizeof(t));
+    CHECK(trf_groups(who, U, nullptr, t));
+    uint32_t *d_read = nullptr, *d_flags = nullptr, *d_ptr = nullptr, *d_tg = nullptr, *d_tf = nullptr;
+    int32_t *d_off = nullptr, *d_tlen = nullptr, *d_start = nullptr, *d_end = nullptr, *d_nn = nullptr, *d_ord = nullptr, *d_cl = nullptr, *d_cen = nullptr,
+            *d_ncl = nullptr, *d_dcen = nullptr;
+    uint64_t* d_words = nullptr;
+    double *d_rp = nullptr, *d_gauss = nullptr;
+    float *d_rho = nullptr, *d_delta = nullptr, *d_bmax = nullptr;
+    std::vector<int32_t> cen(n, -1), dcen(n);
+    std::vector<float> bmax(n);
+    TrfClusterView v;
+    auto tiles = [&](const char* name, auto launch4, auto launch8) {
+        for (int pass = 0; pass < 2; pass++) {
+            if (!n_tile[pass]) continue;
+            LaunchScope ls(c, name, (double)n_tile[pass] * MIRGE_BLOCK);
+            if (pass == 0) launch4(dim3(n_tile[0]), 0u); else launch8(dim3(n_tile[1]), n_tile[0]);
+        }
+    };
+    auto run = [&]() -> int {
+        CHECK(dalloc(c, &d_read, n)); CHECK(dalloc(c, &d_off, n)); CHECK(dalloc(c, &d_tlen, n)); CHECK(dalloc(c, &d_start, n)); CHECK(dalloc(c, &d_end, n));
+        CHECK(dalloc(c, &d_words, n * 2 * MIRGE_TRF_CL_MAXW)); CHECK(dalloc(c, &d_rp, n)); CHECK(dalloc(c, &d_gauss, ngauss)); CHECK(dalloc(c, &d_flags, 16));
+        CHECK(dalloc(c, &d_ptr, ng + 1)); CHECK(dalloc(c, &d_tg, nt)); CHECK(dalloc(c, &d_tf, nt)); CHECK(dalloc(c, &d_rho, n)); CHECK(dalloc(c, &d_delta, n));
+        CHECK(dalloc(c, &d_nn, n)); CHECK(dalloc(c, &d_ord, n)); CHECK(dalloc(c, &d_cl, n)); CHECK(dalloc(c, &d_cen, n)); CHECK(dalloc(c, &d_ncl, ng));
+        CHECK(dalloc(c, &d_bmax, n)); CHECK(dalloc(c, &d_dcen, n));
+        HIPOK(hipMemcpyAsync(d_read, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_off, off, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_tlen, pt_tlen.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_rp, rp100k, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_gauss, gauss, ngauss * 8, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_ptr, p32.data(), (ng + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_tg, tile_grp.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_tf, tile_first.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemsetAsync(d_flags, 0, 64, c->stream));
+        {
+            LaunchScope ls(c, "k_trf_cluster_pack", (double)n);
+            hipLaunchKernelGGL(k_trf_cluster_pack, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_read, (const int32_t*)d_off,
+                               (const int32_t*)d_tlen, (uint32_t)n, d_words, d_start, d_end, d_flags);
+        }
+        uint32_t flag = 0;
+        HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        if (flag & 1u) return fail(-1, who + ": a point's read is of the long class");
+        if (flag & 2u) return fail(-1, who + ": a point does not fit its template");
+        v = TrfClusterView{d_words, d_start, d_end, d_rp, d_ptr, d_tg, d_tf, d_gauss, (int32_t)ngauss, 0};
+        tiles("k_trf_density",
+              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_density<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, d_rho); },
+              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_density<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, d_rho); });
+        tiles("k_trf_nearest",
+              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_nearest<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, d_delta, d_nn, d_ord); },
+              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_nearest<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, d_delta, d_nn, d_ord); });
+        HIPOK(hipMemcpyAsync(rho, d_rho, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(delta, d_delta, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(nneigh, d_nn, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(order, d_ord, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        if (trf_cluster_assign(n_grp, grp_ptr, rho, delta, nneigh, order, cl, centre, nclust, cen.data()))
+            return fail(-1, who + ": the density order is no permutation");
+        HIPOK(hipMemcpyAsync(d_cl, cl, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_cen, cen.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_ncl, nclust, ng * 4, hipMemcpyHostToDevice, c->stream));
+        tiles("k_trf_border",
+              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_border<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, (const int32_t*)d_cl, (const int32_t*)d_cen, (const int32_t*)d_ncl, d_bmax, d_dcen); },
+              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_border<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, (const int32_t*)d_cl, (const int32_t*)d_cen, (const int32_t*)d_ncl, d_bmax, d_dcen); });
+        HIPOK(hipMemcpyAsync(bmax.data(), d_bmax, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(dcen.data(), d_dcen, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        trf_cluster_halo(n_grp, grp_ptr, rho, cl, nclust, bmax.data(), dcen.data(), halo);
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(c->stream);
+    c->drain();
+    for (void* p : {(void*)d_read, (void*)d_flags, (void*)d_ptr, (void*)d_tg, (void*)d_tf, (void*)d_off, (void*)d_tlen, (void*)d_start, (void*)d_end,
+                    (void*)d_nn, (void*)d_ord, (void*)d_cl, (void*)d_cen, (void*)d_ncl, (void*)d_dcen, (void*)d_words, (void*)d_rp, (void*)d_gauss,
+                    (void*)d_rho, (void*)d_delta, (void*)d_bmax})
+        c->release(p);
     return rc;
 }

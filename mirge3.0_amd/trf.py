@@ -1,16 +1,20 @@
 """tRNA fragment reports (``--trf-report``): the reference's ``-trf`` up to its per-sample reports -- summary.py:1060-1220 and
-``trna_deliverables`` (mirge2_tRF_a2i.py:522-744) -- without the density-peak clustering behind them.
+``trna_deliverables`` (mirge2_tRF_a2i.py:522-744) -- and, with ``--trf-clusters``, the density-peak clustering behind them (:745-947).
 
 Written into the run's directory: ``tRFs.aligned.report.tsv``, ``tRF.Counts.csv``, ``tRF.RP100K.csv``,
 ``discarded.reads.summary.assigningtRFs.csv`` and, per sample, ``tRFs.samples.tmp/<sample>.aligned_tRFs.report`` and
-``.aligned_tRFs.summary.report``.  NOT written: ``<sample>.aligned_tRFs.clusters.detail`` and ``<sample>.tRFs.report.tsv`` (the
-clustering, mirge2_tRF_a2i.py:745-947: it depends on float32 ties, on the order ``np.argsort`` leaves equals in and on the order
-doubles are summed in), nor the intermediate ``miRge3_tRNA.sam`` / ``miRge3_pre_tRNA.sam``.
+``.aligned_tRFs.summary.report``; with ``--trf-clusters`` also ``<sample>.aligned_tRFs.clusters.detail`` and
+``<sample>.tRFs.report.tsv``.  NOT written: the intermediate ``miRge3_tRNA.sam`` / ``miRge3_pre_tRNA.sam``.
 
 The sequence work runs on the device (csrc/kernels_trf.hpp): every best-stratum alignment of every tRNA read
 (``_ffi.trf_hits``: bowtie's ``-a --best --strata`` of passes 2 and 3, where the cascade keeps one alignment per read) and the
 comparison of every report row with all predefined tRFs of its tRNA (``_ffi.trf_assign``: ``assign_cluster`` / ``getDistance2``).
 The sums, the sorts and the text are host work in Python floats, so that ``'%.3f' % round(x, 3)`` rounds as the reference does.
+The clustering's pair work -- all distances between the reads stacked on one tRNA, their densities, nearest denser points and border
+densities -- runs on the device too (``_ffi.trf_cluster``); a point is a row of ``<sample>.aligned_tRFs.report`` with the RP100K the
+report prints (``report_value``), taken from memory.  The float32 densities are the reference's bit for bit: the Gaussian comes from
+a table of Python's ``math.exp`` and the double sum runs in the reference's order with product and sum rounded separately.  The
+per-cluster sums, the ``repr`` of the float lists and the text of the two files are host work (``cluster_block``, ``write_clusters``).
 
 Where the reference leaves the outcome to chance, this is the project's rule:
 
@@ -20,6 +24,12 @@ Where the reference leaves the outcome to chance, this is the project's rule:
 3. ``random.choice(candidatetRNAUniquelist)`` (mirge2_tRF_a2i.py:563-567), and the order of that list itself (a ``set`` of
    strings): here the candidates -- the hit names mapped through ``_trna_deduplicated_list.csv``, made unique -- stand in library
    order (mature before ``pre_``, then the reference index) and the first one is chosen.
+
+4. Points with equal float32 densities: ``np.argsort(-rho)`` leaves their order to NumPy's version and to the CPU; here they stand in
+   index order (the sort made stable).
+5. The reference pairs ``readInforList`` with ``tRNANameList`` by position although ``load_data_new`` skips a tRNA whose rows were all
+   dropped, so every later block carries the name before its own; here such a tRNA writes no block and the names stay with their
+   blocks.
 
 A candidate that is not itself a hit of the read raises ``KeyError`` in the reference (:583); here the row is written from the
 candidates that are hits, and ``run.log`` names the first such read.  A hit's type (``trfTypes``, summary.py:649-674) is decided by
@@ -39,6 +49,7 @@ import numpy as np
 
 TYPES = ("tRF-whole", "5'-half", "5'-tRF", "3'-half", "3'-tRF", "i-tRF", "tRF-1")  # csrc/kernels_trf.hpp: MIRGE_TRF_*
 MATURE_PASS, PRIMARY_PASS = 2, 3
+TRF_CLUSTER_MAXCOL = 256  # csrc/kernels_trf.hpp: MIRGE_TRF_CL_MAXCOL
 FILES = ("_trna.str", "_trna_aminoacid_anticodon.csv", "_trna_deduplicated_list.csv", "_tRF_infor.csv", "_tRF_merges.csv")
 _UID_ALPHABET = "BD0EF1HI2JK3LM4NO5PQ6RS7UV8WX9YZ"
 _UID_OFFSET = (0, 0, 4, 20, 84)
@@ -172,10 +183,12 @@ def hits_by_row(reads: Sequence[str], rec: dict, mature_names: Sequence[str], pr
 
 
 def write_reports(workDir, base_names: Sequence[str], reads: Sequence[str], counts, hits: List[List[tuple]], mature_sums, primary_sums,
-                  ann: Annotation, pre_seqs: Dict[str, str], lib_order: Dict[str, tuple], assign: Callable, say: Callable[[str], None]) -> dict:
+                  ann: Annotation, pre_seqs: Dict[str, str], lib_order: Dict[str, tuple], assign: Callable, say: Callable[[str], None],
+                  cluster: Optional[Callable] = None, tm: Optional[dict] = None) -> dict:
     """``trna_deliverables`` up to mirge2_tRF_a2i.py:744.  ``reads`` / ``counts`` / ``hits``: the report's rows in order (mature-tRNA
     rows of mapped.csv, then the primary-tRNA rows); ``lib_order``: name -> sort key of rule 3; ``assign(rows)`` with rows =
-    [(row index, tRNA name, 1-based start)] -> (distances, tRF indices into ``InforTables(ann.infor)`` or -1)."""
+    [(row index, tRNA name, 1-based start)] -> (distances, tRF indices into ``InforTables(ann.infor)`` or -1).  ``cluster``
+    (``--trf-clusters``): see ``write_clusters``; None: the clustering files are not written."""
     workDir = Path(workDir)
     S = len(base_names)
     counts = [[int(x) for x in row] for row in counts]
@@ -270,7 +283,8 @@ def write_reports(workDir, base_names: Sequence[str], reads: Sequence[str], coun
         for i, s in enumerate(base_names):
             if counts[k][i] > 0:
                 filled = h[1] * '-' + seq + (len(template_of(h[0])) - h[1] - len(seq)) * '-'
-                per_sample[s].setdefault(h[0], []).append((counts[k][i], h[1], seq, filled, h[3], rpm[k][i]))
+                per_sample[s].setdefault(h[0], []).append((counts[k][i], h[1], seq, filled, h[3], rpm[k][i], k))  # (k: behind what the sort looks at)
+    blocks: Dict[str, list] = {s: [] for s in base_names}   # per sample, in the report's order: (tRNA, template, its printed rows)
     for s in base_names:
         aa_list, aa_sum = [], {}
         with open(tdir / (s + '.aligned_tRFs.report'), "w") as outf:
@@ -285,6 +299,7 @@ def write_reports(workDir, base_names: Sequence[str], reads: Sequence[str], coun
                 per_sample[s][name].sort(reverse=True)
                 outf.write(name + '\t' + 'read count sum:' + str(read_sum) + '\tRP100K sum:' + '%.3f' % (round(rpm_sum, 3)) + '\n')
                 template = template_of(name)
+                blocks[s].append((name, template, [t for t in per_sample[s][name] if len(t[3]) == len(template)]))
                 for t in per_sample[s][name]:
                     if len(t[3]) == len(template):
                         outf.write(t[3] + '\t' + t[4] + '\t' + str(t[0]) + '\t' + '%.3f' % (round(t[5], 3)) + '\n')
@@ -302,7 +317,151 @@ def write_reports(workDir, base_names: Sequence[str], reads: Sequence[str], coun
             outf.write('amino acid\tCounts\tRP100K\tUnique reads\n')
             for key in aa_list:
                 outf.write('\t'.join([key, str(aa_sum[key][0]), '%.3f' % (round(aa_sum[key][1], 3)), str(aa_sum[key][2])]) + '\n')
-    return dict(rows=len(reads), printed=len(printed), discarded={s: tuple(summary[s]) for s in base_names})
+    out = dict(rows=len(reads), printed=len(printed), discarded={s: tuple(summary[s]) for s in base_names})
+    if cluster is not None:
+        out["clusters"] = write_clusters(tdir, base_names, blocks, cluster, ann, pre_seqs, tm)
+    return out
+
+
+class TemplateTooLong(ValueError):
+    """``--trf-clusters``: a tRNA (or a primary tRNA with its leader and trailer) has more columns than the clustering kernels take"""
+
+
+def report_value(x: float) -> float:
+    """an RP100K as ``load_data_new`` reads it back from <sample>.aligned_tRFs.report"""
+    return float('%.3f' % round(x, 3))
+
+
+def detect_mismatch(target: str, template: str, position: str) -> Tuple[str, str]:
+    """detectMismach (mirge2_tRF_a2i.py:215-228)"""
+    start, end = int(position.split(':')[0]) - 1, int(position.split(':')[1]) - 1
+    tmp = template[start:end + 1]
+    pos = [str(start + 1 + i) for i in range(min(len(target), len(tmp))) if target[i] != tmp[i]]
+    return ('Y' if pos else 'N'), ','.join(pos)
+
+
+def cluster_block(name: str, pts: Sequence[tuple], cl: Sequence[int], halo: Sequence[int], nclust: int, centre: Sequence[int]):
+    """one tRNA's block of <sample>.aligned_tRFs.clusters.detail (mirge2_tRF_a2i.py:840-924).  ``pts``: (dashed string, type, count,
+    RP100K) per point; ``cl`` / ``halo``: per point, 0-based lists of the 1-based cluster numbers; ``centre``: the 1-based index of
+    every cluster's centre -> (text, [(sequence, type, 'start:end', count, RP100K)] per written cluster, the block's RP100K)"""
+    n = len(pts)
+    text = [name + ':\n']
+    sum_count, sum_rp = 0, 0.0
+    core_c, halo_c, core_r, halo_r, content = [], [], [], [], []
+    number = 1
+    if nclust >= 1:
+        for i in range(1, nclust + 1):
+            c = centre[i - 1] - 1
+            nc, select, t_halo_c, t_halo_r = 0, [], 0, 0.0
+            for j in range(n):
+                if cl[j] == i:
+                    nc += 1
+                if halo[j] == i:
+                    select.append(j)
+                if cl[j] == i and halo[j] != i:
+                    t_halo_c = t_halo_c + pts[j][2]
+                    t_halo_r = t_halo_r + pts[j][3]
+            nh = len(select)
+            t_core_c, t_core_r = 0, 0.0
+            for j in select:
+                t_core_c = t_core_c + pts[j][2]
+                t_core_r = t_core_r + pts[j][3]
+            if t_core_c > 0:
+                # (the reference sorts (count, the CENTRE's string, the CENTRE's type) tuples: whichever count is largest, the
+                # sequence, the type and the coordinates are the centre's)
+                seq = pts[c][0]
+                head, tail = len(seq) - len(seq.lstrip('-')), len(seq) - len(seq.rstrip('-'))
+                text.append('Cluster: %d Total Read Count in Core: %d Total Read Count in Halo: %d Total RP100K in Core: %.2f Total RP100K in Halo: '
+                            '%.2f Center Index: %d Elements: %d Core: %d Halo: %d\n' % (number, t_core_c, t_halo_c, t_core_r, t_halo_r, c + 1, nc, nh, nc - nh))
+                text.append('Center:\n')
+                text.append('%s\t%s\t%d\t%.2f\n' % pts[c][:4])
+                a_count, a_rp = 0 + pts[c][2], 0.0 + pts[c][3]
+                for j in select:
+                    if j != c:
+                        text.append('%s\t%s\t%d\t%.2f\n' % pts[j][:4])
+                        a_count = a_count + pts[j][2]
+                        a_rp = a_rp + pts[j][3]
+                text.append('**********************************\n')
+                content.append((seq[head:len(seq) - tail], pts[c][1], ':'.join([str(head + 1), str(len(seq) - tail)]), a_count, a_rp))
+                number += 1
+            sum_count = sum_count + t_halo_c + t_core_c
+            sum_rp = sum_rp + t_halo_r
+            sum_rp = sum_rp + t_core_r
+            core_c.append(t_core_c); halo_c.append(t_halo_c); core_r.append(t_core_r); halo_r.append(t_halo_r)
+    else:
+        for j in range(n):
+            sum_count = sum_count + pts[j][2]
+            sum_rp = sum_rp + pts[j][3]
+    text.append('Summary:\nNumber of Clusters: %d\n' % (number - 1))
+    text.append('total Read Count : %d\n' % sum_count)
+    text.append('total RP100K: %.2f\n' % sum_rp)
+    text.append('total Cluster Core Read Count: %s=%d\n' % ('+'.join(str(x) for x in core_c), sum(core_c)))
+    text.append('total Cluster Core RP100K: %s=%.3f\n' % ('+'.join(str(x) for x in core_r), sum(core_r)))
+    text.append('total Cluster Halo Read Count: %s=%d\n' % ('+'.join(str(x) for x in halo_c), sum(halo_c)))
+    text.append('total Cluster Halo RP100K: %s=%.3f\n' % ('+'.join(str(x) for x in halo_r), sum(halo_r)))
+    text.append('##################################\n')
+    return ''.join(text), content, sum_rp
+
+
+def write_clusters(tdir, base_names: Sequence[str], blocks: Dict[str, list], cluster: Callable, ann: Annotation, pre_seqs: Dict[str, str],
+                   tm: Optional[dict] = None) -> dict:
+    """the rest of ``trna_deliverables`` (mirge2_tRF_a2i.py:745-947): <sample>.aligned_tRFs.clusters.detail and <sample>.tRFs.report.tsv.
+    ``blocks``: per sample (tRNA, template, rows of ``write_reports``); ``cluster(groups)`` with groups = [dict(tlen, rows, off, rp,
+    dashed)] -> the arrays of ``_ffi.trf_cluster`` over the groups' points in order."""
+    tm = tm if tm is not None else {}
+    groups, owner = [], []
+    for s in base_names:
+        for name, template, rows in blocks[s]:
+            if not rows:
+                continue  # (rule 5: a tRNA whose rows were all dropped writes no block (the reference shifts every later name by one))
+            if len(template) > TRF_CLUSTER_MAXCOL:
+                raise TemplateTooLong(f"--trf-clusters: {name} has {len(template)} columns, the clustering takes at most {TRF_CLUSTER_MAXCOL}")
+            groups.append(dict(tlen=len(template), rows=[t[6] for t in rows], off=[t[1] for t in rows], rp=[report_value(t[5]) for t in rows],
+                               dashed=[t[3] for t in rows]))
+            owner.append((s, name, [(t[3], t[4], t[0], rp) for t, rp in zip(rows, groups[-1]["rp"])]))
+    t0 = time.perf_counter()
+    res = cluster(groups) if groups else None
+    tm["trf_cluster_s"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    ptr = np.zeros(len(groups) + 1, dtype=np.int64)
+    np.cumsum([len(g["rows"]) for g in groups], out=ptr[1:])
+    at = 0
+    n_clusters = {}
+    for s in base_names:
+        selected, unified, content_of = [], [], {}
+        with open(Path(tdir) / (s + '.aligned_tRFs.clusters.detail'), "w") as o1:
+            while at < len(owner) and owner[at][0] == s:
+                _, name, pts = owner[at]
+                lo, hi = int(ptr[at]), int(ptr[at + 1])
+                nclust = int(res["nclust"][at])
+                text, content, sum_rp = cluster_block(name, pts, res["cl"][lo:hi].tolist(), res["halo"][lo:hi].tolist(), nclust,
+                                                      res["centre"][lo:lo + nclust].tolist())
+                o1.write(text)
+                content_of[name] = content
+                n_clusters[(s, name)] = len(content)
+                if sum_rp >= 10.0:
+                    selected.append(name)
+                    u = '_'.join(name.split('_')[1:-1]) if 'pre' in name else name
+                    if u not in unified:
+                        unified.append(u)
+                at += 1
+        with open(Path(tdir) / (s + '.tRFs.report.tsv'), "w") as o2:
+            o2.write('tRNA name\ttRNA sequence\ttRF sequence\ttRF mismatch\ttRF type\ttRF coordinate\tRead count\tRP100K\n')
+            for u in unified:
+                if u in selected:
+                    seq = ann.stru[u]['seq']
+                    for c in content_of[u]:
+                        o2.write(u + '\t' + seq + '\t' + c[0] + '\t' + ':'.join(detect_mismatch(c[0], seq, c[2])) + '\t' + c[1] + '\t' + c[2] + '\t' +
+                                 str(c[3]) + '\t' + '%.2f' % (round(c[4], 2)) + '\n')
+                pname = 'pre_' + u + '_trailer'
+                if pname in selected:
+                    seq = pre_seqs[pname]
+                    for c in content_of[pname]:
+                        pos = ':'.join([c[2].split(':')[0], str(int(c[2].split(':')[1]) - 3)])
+                        o2.write(u + '\t' + seq + '\t' + c[0] + '\t' + ':'.join(detect_mismatch(c[0][:-3], seq, pos)) + '\t' + c[1] + '\t' + c[2] + '\t' +
+                                 str(c[3]) + '\t' + '%.2f' % (round(c[4], 2)) + '\n')
+    tm["trf_cluster_text_s"] = time.perf_counter() - t0
+    return dict(groups=len(groups), points=int(ptr[-1]), clusters=n_clusters)
 
 
 def library_order(mature_names: Sequence[str], primary_names: Sequence[str]) -> Dict[str, tuple]:
@@ -352,8 +511,18 @@ def run(args, workDir, base_names, casc, uniq, res, order, class_sums, tm=None) 
             tm["trf_assign_s"] = time.perf_counter() - t1
             return out
 
+        def cluster(groups):
+            ptr = np.zeros(len(groups) + 1, dtype=np.int64)
+            np.cumsum([len(g["rows"]) for g in groups], out=ptr[1:])
+            return _ffi.trf_cluster(ctx, uniq, ptr, [rows[k] for g in groups for k in g["rows"]], [o for g in groups for o in g["off"]],
+                                    [x for g in groups for x in g["rp"]], [g["tlen"] for g in groups])
+
         pre_seqs = dict(zip(plib.names, plib.seqs.to_list()))
+        too_long = [nm for nm, sq in list(zip(mlib.names, mlib.seqs.to_list())) + list(pre_seqs.items()) if len(sq) > TRF_CLUSTER_MAXCOL] \
+            if getattr(args, "trf_clusters", False) else []
+        if too_long:  # (before anything is written)
+            raise TemplateTooLong(f"--trf-clusters: {too_long[0]} has more than {TRF_CLUSTER_MAXCOL} columns")
         out = write_reports(workDir, list(base_names), reads, counts, hits, class_sums[MATURE_PASS], class_sums[PRIMARY_PASS], ann, pre_seqs,
-                            library_order(mlib.names, plib.names), assign, say)
+                            library_order(mlib.names, plib.names), assign, say, cluster if getattr(args, "trf_clusters", False) else None, tm)
     tm["trf_report_s"] = time.perf_counter() - t0
     return out
