@@ -474,12 +474,21 @@ int mirge_sam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
  * chromosome indices (mirge_sam_pass.chrom_of_ref) to refIDs; -1 = no @SQ names it, an error when a kept row lies there.  Errors are
  * raised before anything is written: such a chromosome (named in the message), a position outside [0, 2^29), a QNAME beyond 254
  * characters.  *n_records_out = records, *n_stream_bytes_out = uncompressed bytes, *n_file_bytes_out = bytes of the .bam.
- * `threads` sizes the host pool of MIRGE_BAM_DEFLATE=host.  MIRGE_BAM_BLOCK_BYTES / MIRGE_BAM_CHUNK_BLOCKS / MIRGE_BAM_DEFLATE: README. */
+ * `threads` sizes the host pool of MIRGE_BAM_DEFLATE=host.  MIRGE_BAM_DEFLATE=device (the default) deflates every block on the device
+ * with the fixed Huffman code or stores it; =dynamic adds a Huffman code built per block (BTYPE 10) and takes it where its member is
+ * strictly smaller, so no member grows; =host sends the blocks through zlib on the host; any other value is an error.
+ * MIRGE_BAM_BLOCK_BYTES / MIRGE_BAM_CHUNK_BLOCKS: README. */
 int mirge_bam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
                            const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
                            const int32_t* chrom_refid, const int64_t* chrom_refid_off, int32_t n_ref, const char* bam_path,
                            const char* bai_path, const char* header, int64_t header_len, int32_t threads, int64_t* n_records_out,
                            int64_t* n_stream_bytes_out, int64_t* n_file_bytes_out);
+
+/* A test entry: the device's builder of the dynamic mode's code lengths alone (one workgroup).  counts[n_sym], 1 <= n_sym <= 288,
+ * 1 <= max_bits <= 15, 2^max_bits >= n_sym -> lengths_out[n_sym]: 0 where the count is 0, none above max_bits; two or more used
+ * symbols give a complete prefix code (of the Huffman optimum's cost whenever an optimal tree fits max_bits), one used symbol gets
+ * length 1. */
+int mirge_bam_huffman_probe(mirge_ctx* ctx, const uint32_t* counts, int32_t n_sym, int32_t max_bits, uint8_t* lengths_out);
 
 /* ---- the sequence work behind the tRNA fragment report (the reference's -trf: summary.py:1060-1220, mirge2_tRF_a2i.py:22-62)
  * mirge_trf_hits_run  every best-stratum alignment (bowtie -a --best --strata) of the tRNA reads rows[n_rows] (handle indices of `uniq`;

@@ -30,7 +30,7 @@ EXPORTS = [
     "mirge_cascade_prepare", "mirge_cascade_walks", "mirge_cascade_wg_times", "mirge_ctx_profile_only", "mirge_ctx_profile_units", "mirge_ctx_profile_reset", "mirge_ctx_profile_count", "mirge_ctx_profile_get",
     "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
-    "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device",
+    "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device", "mirge_bam_huffman_probe",
     "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
     "mirge_trf_cluster",
 ]
@@ -1005,6 +1005,15 @@ def trf_row_counts(ctx: Context, uniq: DeviceReads, rows) -> np.ndarray:
     if rows.size:
         _check(load().mirge_trf_row_counts(ctx._h, uniq._h, _p(rows), C.c_int64(rows.shape[0]), _p(out)), "mirge_trf_row_counts")
     return out
+
+
+def bam_huffman_probe(ctx: Context, counts, max_bits: int) -> np.ndarray:
+    """``mirge_bam_huffman_probe``: the code lengths (uint8 per symbol) that ``MIRGE_BAM_DEFLATE=dynamic``'s builder gives ``counts``
+    under the limit ``max_bits``"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    out = np.zeros(max(counts.shape[0], 1), dtype=np.uint8)
+    _check(load().mirge_bam_huffman_probe(ctx._h, _p(counts), C.c_int32(counts.shape[0]), C.c_int32(max_bits), _p(out)), "mirge_bam_huffman_probe")
+    return out[:counts.shape[0]]
 
 
 PILEUP_MAXREAD, PILEUP_MAXCLUSTER = 64, 128  # csrc/kernels_pileup.hpp

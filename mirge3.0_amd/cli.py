@@ -113,6 +113,10 @@ def parse_args(argv=None):
                     help="write <sample>_sorted.bam and <sample>_sorted.bai for every sample: the records of --sam-out's <sample>.sam as "
                          "BAM, coordinate-sorted, BGZF-compressed and indexed on the device (what the reference's -bam gets from samtools "
                          "view / sort / index); needs --sam-header FILE with the genome's @SQ lines; independent of --sam-out")
+    ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "host"),
+                    help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
+                         "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
+                         "its own, taken where the member gets smaller; host: zlib level 6 on host threads")
     ap.add_argument("--trf-report", dest="trf_report", action="store_true",
                     help="write the tRNA fragment reports of the reference's -trf up to its per-sample reports: tRFs.aligned.report.tsv, "
                          "tRF.Counts.csv, tRF.RP100K.csv, discarded.reads.summary.assigningtRFs.csv and tRFs.samples.tmp/<sample>."
@@ -188,6 +192,8 @@ def parse_args(argv=None):
         ap.error("--sorted-bam runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.sorted_bam and not args.sam_header:
         ap.error("--sorted-bam requires --sam-header FILE with the @SQ SN:/LN: lines of the genome the libraries were built on")
+    if args.bam_deflate and not args.sorted_bam:
+        ap.error("--bam-deflate requires --sorted-bam")
     if args.sam_out and (args.save_pkl or args.resume or args.backend == "bowtie"):
         ap.error("--sam-out runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.trf_clusters:
@@ -269,6 +275,8 @@ def collect_samples(args, runlog, loud=True):
 def main(argv=None):
     globalstart = time.perf_counter()
     args = parse_args(argv)
+    if args.bam_deflate:  # the route of this process's --sorted-bam calls, ahead of what the environment says (read per call)
+        os.environ["MIRGE_BAM_DEFLATE"] = args.bam_deflate
     # pandas writes the three small tables at the very end; importing it (0.15-0.2 s) runs beside the libraries' load and the
     # GPU work instead of in front of the first table
     import threading

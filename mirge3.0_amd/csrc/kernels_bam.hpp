@@ -17,6 +17,13 @@
 //                     - CRC-32: every thread's table CRC of its segment, times x^(8 * bytes behind the segment) mod P, XOR-ed.
 //                   and written as one BGZF member into the block's slot; k_bam_compact closes the gaps between the slots.
 //                   deflate = 0: the uncompressed block goes out instead (MIRGE_BAM_DEFLATE=host: zlib on the host).
+//                   deflate = 2 (MIRGE_BAM_DEFLATE=dynamic; on the device the kernel k_bam_blocks_dynamic): the same parse, and a
+//                   third form to choose from: a Huffman code of the
+//                   block's own (BTYPE 10).  The counting walk also adds its symbols to LDS histograms (one pair per wave) and leaves
+//                   every match at its own bytes of the still empty output words; bam_huff_lengths makes the code lengths (at most
+//                   15 bits; 7 for the code of the lengths themselves), a walk over the staged matches -- no match search -- gives
+//                   every segment its bits under that code, and the form goes out when its bytes are fewer than those of the better
+//                   of the other two: no member is larger than under deflate = 1.  k_bam_huff_probe: bam_huff_lengths alone.
 // No wave intrinsics: the same source runs on the host (tests/hostsim/bam_sim.cpp).
 #pragma once
 
@@ -191,19 +198,24 @@ struct BamBits {
 template <bool WRITE> __device__ __forceinline__ void bam_put_literal(BamBits<WRITE>& w, uint32_t b) {
     if (b < 144u) w.put(bam_bitrev(0x30u + b, 8), 8); else w.put(bam_bitrev(0x190u + (b - 144u), 9), 9);
 }
+// a match's length code 257 + idx and distance code dc with their extra bits (RFC 1951, 3.2.5)
+struct BamMatchCode { uint32_t idx, xb, xv, dc, db, dv; };
+__device__ __forceinline__ BamMatchCode bam_match_code(uint32_t len, uint32_t dist) {
+    BamMatchCode m{0u, 0u, 0u, 0u, 0u, 0u};
+    if (len <= 10u) m.idx = len - 3u;
+    else if (len == 258u) m.idx = 28u;
+    else { const uint32_t l = len - 3u; const int e = bam_log2(l) - 2; m.idx = 4u * (uint32_t)(e + 1) + ((l >> e) & 3u); m.xb = (uint32_t)e; m.xv = l & ((1u << e) - 1u); }
+    if (dist <= 4u) m.dc = dist - 1u;
+    else { const uint32_t d = dist - 1u; const int e = bam_log2(d) - 1; m.dc = 2u * (uint32_t)(e + 1) + ((d >> e) & 1u); m.db = (uint32_t)e; m.dv = d & ((1u << e) - 1u); }
+    return m;
+}
 template <bool WRITE> __device__ __forceinline__ void bam_put_match(BamBits<WRITE>& w, uint32_t len, uint32_t dist) {
-    uint32_t idx, xb = 0, xv = 0;
-    if (len <= 10u) idx = len - 3u;
-    else if (len == 258u) idx = 28u;
-    else { const uint32_t l = len - 3u; const int e = bam_log2(l) - 2; idx = 4u * (uint32_t)(e + 1) + ((l >> e) & 3u); xb = (uint32_t)e; xv = l & ((1u << e) - 1u); }
-    const uint32_t sym = 257u + idx;
+    const BamMatchCode m = bam_match_code(len, dist);
+    const uint32_t sym = 257u + m.idx;
     if (sym <= 279u) w.put(bam_bitrev(sym - 256u, 7), 7); else w.put(bam_bitrev(0xC0u + (sym - 280u), 8), 8);
-    if (xb) w.put(xv, (int)xb);
-    uint32_t dc, db = 0, dv = 0;
-    if (dist <= 4u) dc = dist - 1u;
-    else { const uint32_t d = dist - 1u; const int e = bam_log2(d) - 1; dc = 2u * (uint32_t)(e + 1) + ((d >> e) & 1u); db = (uint32_t)e; dv = d & ((1u << e) - 1u); }
-    w.put(bam_bitrev(dc, 5), 5);
-    if (db) w.put(dv, (int)db);
+    if (m.xb) w.put(m.xv, (int)m.xb);
+    w.put(bam_bitrev(m.dc, 5), 5);
+    if (m.db) w.put(m.dv, (int)m.db);
 }
 __device__ __forceinline__ uint32_t bam_ld32(const uint8_t* d, uint32_t i) {
     return (uint32_t)d[i] | ((uint32_t)d[i + 1] << 8) | ((uint32_t)d[i + 2] << 16) | ((uint32_t)d[i + 3] << 24);
@@ -211,9 +223,9 @@ __device__ __forceinline__ uint32_t bam_ld32(const uint8_t* d, uint32_t i) {
 __device__ __forceinline__ uint32_t bam_hash(uint32_t v, uint32_t i) {
     return ((i >> 15) << MIRGE_BAM_HASH_BITS) | ((v * 2654435761u) >> (32 - MIRGE_BAM_HASH_BITS));
 }
-// the greedy parse of segment [s0, s1) of the block's n bytes
-template <bool WRITE>
-__device__ __forceinline__ void bam_parse(const uint8_t* d, const uint32_t* head, uint32_t s0, uint32_t s1, BamBits<WRITE>& w) {
+// the greedy parse of segment [s0, s1) of the block's n bytes into a sink W: bam_put_literal(w, byte), bam_put_match(w, length, distance)
+template <class W>
+__device__ __forceinline__ void bam_parse(const uint8_t* d, const uint32_t* head, uint32_t s0, uint32_t s1, W& w) {
     uint32_t i = s0;
     while (i < s1) {
         uint32_t best = 0, dist = 0;
@@ -237,20 +249,251 @@ __device__ __forceinline__ void bam_parse(const uint8_t* d, const uint32_t* head
     }
 }
 
+// ---- deflate with a code of the block's own (RFC 1951, 3.2.7)
+#define MIRGE_BAM_NLL 286          // literal/length symbols
+#define MIRGE_BAM_ND 30            // distance symbols
+#define MIRGE_BAM_NCL 19           // symbols of the code that the header spells the other two codes' lengths in
+#define MIRGE_BAM_HUFF_MAX 288     // symbols bam_huff_lengths takes
+#define MIRGE_BAM_HIST_COPIES 4    // one pair of histograms per wave of 64 threads: a hot literal's atomics stay inside its wave's copy
+
+struct BamHuffWork { uint32_t a[MIRGE_BAM_HUFF_MAX]; uint32_t bl[16]; uint16_t order[MIRGE_BAM_HUFF_MAX]; };  // bam_huff_lengths' LDS
+
+// Lengths len[0 .. n) of a prefix code for the counts cnt[0 .. n), n <= MIRGE_BAM_HUFF_MAX <= 2^max_bits, max_bits <= 15: 0 where the
+// count is 0, none above max_bits, and sum count * length the Huffman optimum whenever an optimal tree fits max_bits.  Two or more used
+// symbols give a complete code (Kraft sum 1); ONE used symbol gets length 1, which inflate takes for the distance code alone.
+// cnt, len and w lie in LDS; all the workgroup's threads call, behind a barrier that made cnt visible, and leave through a barrier.
+//   - bam_huff_rank, all threads: the used symbols sorted by (count, symbol), a rank each;
+//   - bam_huff_tree, ONE thread behind a barrier: Moffat and Katajainen's in-place pass over the sorted counts (a tie takes the
+//     leaf, not the inner node: of the optimal trees the one of least depth); where that is still deeper than max_bits, the deeper leaves come up to max_bits and, as long as
+//     the Kraft sum is above 1, a leaf of the greatest length below max_bits moves one level down with a leaf of max_bits as its
+//     sibling (each step takes 2^-max_bits off the sum); the lengths go out longest first to the rarest symbols.
+// k_bam_blocks calls the two steps itself: two codes at a time, their trees on two threads of different waves.
+__device__ __forceinline__ void bam_huff_rank(const uint32_t* cnt, uint32_t n, uint8_t* len, BamHuffWork& w, uint32_t tid, uint32_t nth) {
+    for (uint32_t s = tid; s < n; s += nth) {
+        const uint32_t c = cnt[s];
+        len[s] = 0;
+        if (!c) continue;
+        uint32_t rank = 0;
+        for (uint32_t x = 0; x < n; x++) { const uint32_t cx = cnt[x]; rank += (cx != 0u && (cx < c || (cx == c && x < s))) ? 1u : 0u; }
+        w.order[rank] = (uint16_t)s; w.a[rank] = c;
+    }
+}
+__device__ __forceinline__ void bam_huff_tree(const uint32_t* cnt, uint32_t n, uint32_t max_bits, uint8_t* len, BamHuffWork& w) {
+    uint32_t* A = w.a;
+    uint32_t m = 0;
+    for (uint32_t x = 0; x < n; x++) m += cnt[x] != 0u ? 1u : 0u;
+    if (m == 1u) len[w.order[0]] = 1;
+    if (m >= 2u) {
+        A[0] += A[1];
+        uint32_t root = 0, leaf = 2;
+        for (uint32_t next = 1; next + 1 < m; next++) {  // A[root .. next): weights of inner nodes; A[.. root): their parents
+            if (leaf >= m || A[root] < A[leaf]) { A[next] = A[root]; A[root++] = next; } else A[next] = A[leaf++];
+            if (leaf >= m || (root < next && A[root] < A[leaf])) { A[next] += A[root]; A[root++] = next; } else A[next] += A[leaf++];
+        }
+        A[m - 2] = 0;
+        for (int next = (int)m - 3; next >= 0; next--) A[next] = A[A[next]] + 1u;  // depths of the inner nodes
+        int avbl = 1, used = 0, rt = (int)m - 2, nx = (int)m - 1;
+        for (uint32_t depth = 0; avbl > 0; depth++) {  // depths of the leaves: A[0] the rarest symbol's, the greatest
+            while (rt >= 0 && A[rt] == depth) { used++; rt--; }
+            while (avbl > used) { A[nx--] = depth; avbl--; }
+            avbl = 2 * used; used = 0;
+        }
+        for (uint32_t b = 0; b < 16u; b++) w.bl[b] = 0u;
+        for (uint32_t x = 0; x < m; x++) w.bl[A[x] < max_bits ? A[x] : max_bits]++;
+        if (A[0] > max_bits) {
+            uint32_t total = 0;
+            for (uint32_t b = 1; b <= max_bits; b++) total += w.bl[b] << (max_bits - b);
+            for (; total > (1u << max_bits); total--) {
+                w.bl[max_bits]--;
+                for (uint32_t b = max_bits - 1u; b >= 1u; b--)
+                    if (w.bl[b]) { w.bl[b]--; w.bl[b + 1u] += 2u; break; }
+            }
+        }
+        uint32_t x = 0;
+        for (uint32_t b = max_bits; b >= 1u; b--)
+            for (uint32_t k = w.bl[b]; k; k--) len[w.order[x++]] = (uint8_t)b;
+    }
+}
+__device__ __forceinline__ void bam_huff_lengths(const uint32_t* cnt, uint32_t n, uint32_t max_bits, uint8_t* len, BamHuffWork& w, uint32_t tid, uint32_t nth) {
+    bam_huff_rank(cnt, n, len, w, tid, nth);
+    __syncthreads();
+    if (tid == 0) bam_huff_tree(cnt, n, max_bits, len, w);
+    __syncthreads();
+}
+// two codes at once: the second one's tree is thread nth / 2's
+__device__ __forceinline__ void bam_huff_lengths2(const uint32_t* cnt0, uint32_t n0, uint8_t* len0, BamHuffWork& w0, const uint32_t* cnt1, uint32_t n1, uint8_t* len1,
+                                                  BamHuffWork& w1, uint32_t max_bits, uint32_t tid, uint32_t nth) {
+    bam_huff_rank(cnt0, n0, len0, w0, tid, nth);
+    bam_huff_rank(cnt1, n1, len1, w1, tid, nth);
+    __syncthreads();
+    if (tid == 0) bam_huff_tree(cnt0, n0, max_bits, len0, w0);
+    if (tid == nth / 2u) bam_huff_tree(cnt1, n1, max_bits, len1, w1);
+    __syncthreads();
+}
+// the canonical code of lengths len[0 .. n) (RFC 1951, 3.2.2), bit-reversed for the LSB-first stream: code[s] = bits | length << 16.
+// A symbol's code is the number of codes in front of it: 2^(L - l) per shorter code of length l, one per earlier symbol of its own length.
+__device__ __forceinline__ void bam_huff_codes(const uint8_t* len, uint32_t n, uint32_t* code, uint32_t tid, uint32_t nth) {
+    for (uint32_t s = tid; s < n; s += nth) {
+        const uint32_t L = len[s];
+        uint32_t c = 0;
+        for (uint32_t x = 0; x < n && L; x++) {
+            const uint32_t lx = len[x];
+            if (lx && lx < L) c += 1u << (L - lx);
+            else if (lx == L && x < s) c++;
+        }
+        code[s] = bam_bitrev(c, (int)L) | (L << 16);
+    }
+}
+__device__ __forceinline__ uint32_t bam_cl_order(uint32_t k) {  // 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15: five bits each
+    return (uint32_t)((k < 12u ? 0x22caa324e804a30ull >> (5u * k) : 0x3c2e1346cull >> (5u * (k - 12u))) & 31ull);
+}
+
+// the block's state of deflate == 2
+struct BamDynamic {
+    uint32_t hist_ll[MIRGE_BAM_HIST_COPIES][MIRGE_BAM_HUFF_MAX], hist_d[MIRGE_BAM_HIST_COPIES][32];  // [0]: the sums, the counts of the block
+    uint32_t code_ll[MIRGE_BAM_HUFF_MAX], code_d[32], code_cl[32];
+    uint32_t cnt_cl[2][32];            // [0]: of the header with run symbols (16, 17, 18), [1]: of the plain one
+    uint32_t seg[MIRGE_BLOCK + 1];     // the segments' bits, then bit offsets, under the block's own code
+    uint32_t hlit, hdist, hclen, n_tok, plain, header_bits;
+    BamHuffWork work[2];
+    uint16_t tok[MIRGE_BAM_NLL + MIRGE_BAM_ND + 4];  // the header with run symbols: symbol | extra bits' value << 8
+    uint8_t len_ll[MIRGE_BAM_HUFF_MAX], len_d[32], len_cl[2][32];
+};
+// length k of the HLIT + HDIST lengths the header spells, as one sequence
+__device__ __forceinline__ uint32_t bam_dyn_seq(const BamDynamic& y, uint32_t k) { return k < y.hlit ? y.len_ll[k] : y.len_d[k - y.hlit]; }
+
+// the counting walk of deflate == 2: the segment's bits under the fixed code, as BamBits<false> counts them; its symbols into the wave's
+// histograms; every match at the first three of its own bytes of tok (the output words, all zero: a zero byte is a literal), bit 7 of the
+// first one set, then length - 3 (8 bits) and distance - 1 (15 bits).  A match has MIRGE_BAM_MIN_MATCH >= 4 bytes and ends with its segment.
+struct BamCount { uint32_t at, pos; uint32_t* ll; uint32_t* dd; uint8_t* tok; };
+__device__ __forceinline__ void bam_put_literal(BamCount& w, uint32_t b) {
+    w.at += b < 144u ? 8u : 9u;
+    atomicAdd(&w.ll[b], 1u);
+    w.pos++;
+}
+__device__ __forceinline__ void bam_put_match(BamCount& w, uint32_t len, uint32_t dist) {
+    const BamMatchCode m = bam_match_code(len, dist);
+    w.at += (m.idx <= 22u ? 7u : 8u) + m.xb + 5u + m.db;
+    atomicAdd(&w.ll[257u + m.idx], 1u);
+    atomicAdd(&w.dd[m.dc], 1u);
+    const uint32_t v = (len - 3u) | ((dist - 1u) << 8);
+    w.tok[w.pos] = (uint8_t)(0x80u | (v & 0x7Fu)); w.tok[w.pos + 1u] = (uint8_t)(v >> 7); w.tok[w.pos + 2u] = (uint8_t)(v >> 15);
+    w.pos += len;
+}
+// the bits of segment [s0, s1) under the block's own code, from the staged matches
+__device__ __forceinline__ uint32_t bam_dyn_bits(const BamDynamic& y, const uint8_t* d, const uint8_t* tok, uint32_t s0, uint32_t s1) {
+    uint32_t bits = 0;
+    for (uint32_t i = s0; i < s1;) {
+        const uint32_t t0 = tok[i];
+        if (!(t0 & 0x80u)) { bits += y.len_ll[d[i]]; i++; continue; }
+        const uint32_t v = (t0 & 0x7Fu) | ((uint32_t)tok[i + 1u] << 7) | ((uint32_t)tok[i + 2u] << 15), len = (v & 255u) + 3u;
+        const BamMatchCode m = bam_match_code(len, (v >> 8) + 1u);
+        bits += y.len_ll[257u + m.idx] + m.xb + y.len_d[m.dc] + m.db;
+        i += len;
+    }
+    return bits;
+}
+// the emitting walk with the block's own code
+struct BamDynBits { BamBits<true> b; const uint32_t* ll; const uint32_t* dd; };
+__device__ __forceinline__ void bam_put_code(BamBits<true>& b, uint32_t c) { b.put(c & 0xFFFFu, (int)(c >> 16)); }
+__device__ __forceinline__ void bam_put_literal(BamDynBits& w, uint32_t b) { bam_put_code(w.b, w.ll[b]); }
+__device__ __forceinline__ void bam_put_match(BamDynBits& w, uint32_t len, uint32_t dist) {
+    const BamMatchCode m = bam_match_code(len, dist);
+    bam_put_code(w.b, w.ll[257u + m.idx]);
+    if (m.xb) w.b.put(m.xv, (int)m.xb);
+    bam_put_code(w.b, w.dd[m.dc]);
+    if (m.db) w.b.put(m.dv, (int)m.db);
+}
+
+// thread 0, the lengths of both codes known: HLIT, HDIST, and the sequence of their lengths in the symbols 0 .. 18 twice -- with the
+// run symbols (16: the length in front 3 to 6 times more, 17: 3 to 10 zeros, 18: 11 to 138 zeros; greedy, a run may cross from one code
+// into the other) into tok, and plain, a symbol per length -- and either form's counts
+__device__ __forceinline__ void bam_dyn_header_tokens(BamDynamic& y) {
+    uint32_t hlit = MIRGE_BAM_NLL, hdist = MIRGE_BAM_ND, any = 0;
+    for (uint32_t x = 0; x < MIRGE_BAM_ND; x++) any |= y.len_d[x];
+    if (!any) y.len_d[0] = 1;  // a block without a match: inflate wants one distance code, of length 1 (no walk reads it: no match)
+    while (hlit > 257u && !y.len_ll[hlit - 1u]) hlit--;
+    while (hdist > 1u && !y.len_d[hdist - 1u]) hdist--;
+    y.hlit = hlit; y.hdist = hdist;
+    for (uint32_t x = 0; x < 32u; x++) { y.cnt_cl[0][x] = 0u; y.cnt_cl[1][x] = 0u; }
+    const uint32_t N = hlit + hdist;
+    uint32_t nt = 0;
+    for (uint32_t k = 0; k < N;) {
+        const uint32_t v = bam_dyn_seq(y, k);
+        uint32_t run = 1;
+        while (k + run < N && bam_dyn_seq(y, k + run) == v) run++;
+        k += run;
+        y.cnt_cl[1][v] += run;
+        if (v) { y.tok[nt++] = (uint16_t)v; y.cnt_cl[0][v]++; run--; }
+        while (run >= (v ? 3u : 11u)) {
+            const uint32_t r = run < (v ? 6u : 138u) ? run : (v ? 6u : 138u), sym = v ? 16u : 18u;
+            y.tok[nt++] = (uint16_t)(sym | ((r - (v ? 3u : 11u)) << 8)); y.cnt_cl[0][sym]++; run -= r;
+        }
+        if (!v && run >= 3u) { y.tok[nt++] = (uint16_t)(17u | ((run - 3u) << 8)); y.cnt_cl[0][17]++; run = 0; }
+        for (; run; run--) { y.tok[nt++] = (uint16_t)v; y.cnt_cl[0][v]++; }
+    }
+    y.n_tok = nt;
+}
+// thread 0, the lengths of the code of either form known: the shorter header (a tie: the one with run symbols), HCLEN, its bits with BFINAL and BTYPE
+__device__ __forceinline__ void bam_dyn_header_choice(BamDynamic& y) {
+    uint32_t bits[2], hclen[2];
+    for (uint32_t f = 0; f < 2u; f++) {
+        uint32_t h = MIRGE_BAM_NCL, sum = 0;
+        while (h > 4u && !y.len_cl[f][bam_cl_order(h - 1u)]) h--;
+        for (uint32_t x = 0; x < MIRGE_BAM_NCL; x++) sum += y.cnt_cl[f][x] * ((uint32_t)y.len_cl[f][x] + (x == 16u ? 2u : x == 17u ? 3u : x == 18u ? 7u : 0u));
+        bits[f] = 3u + 5u + 5u + 4u + 3u * h + sum; hclen[f] = h;
+    }
+    y.plain = bits[1] < bits[0] ? 1u : 0u;
+    y.header_bits = y.plain ? bits[1] : bits[0];
+    y.hclen = y.plain ? hclen[1] : hclen[0];
+}
+// thread 0: the header into the output words
+__device__ __forceinline__ void bam_dyn_put_header(const BamDynamic& y, BamBits<true>& b) {
+    b.put(5u, 3);  // BFINAL = 1, BTYPE = 10
+    b.put(y.hlit - 257u, 5); b.put(y.hdist - 1u, 5); b.put(y.hclen - 4u, 4);
+    const uint8_t* cl = y.len_cl[y.plain];
+    for (uint32_t k = 0; k < y.hclen; k++) b.put(cl[bam_cl_order(k)], 3);
+    if (y.plain)
+        for (uint32_t k = 0; k < y.hlit + y.hdist; k++) bam_put_code(b, y.code_cl[bam_dyn_seq(y, k)]);
+    else
+        for (uint32_t k = 0; k < y.n_tok; k++) {
+            const uint32_t sym = y.tok[k] & 255u;
+            bam_put_code(b, y.code_cl[sym]);
+            if (sym >= 16u) b.put((uint32_t)y.tok[k] >> 8, sym == 16u ? 2 : sym == 17u ? 3 : 7);
+        }
+}
+
+// bam_huff_lengths alone, one workgroup (mirge_bam_huffman_probe: a payload that drives the real parse into the 15-bit limit cannot
+// be built -- bytes skewed enough always match)
+__global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_huff_probe(const uint32_t* __restrict__ counts, uint32_t n, uint32_t max_bits, uint8_t* __restrict__ lengths) {
+    __shared__ uint32_t cnt[MIRGE_BAM_HUFF_MAX];
+    __shared__ uint8_t len[MIRGE_BAM_HUFF_MAX];
+    __shared__ BamHuffWork work;
+    if (blockIdx.x != 0 || n > MIRGE_BAM_HUFF_MAX) return;
+    for (uint32_t x = threadIdx.x; x < n; x += blockDim.x) cnt[x] = counts[x];
+    __syncthreads();
+    bam_huff_lengths(cnt, n, max_bits, len, work, threadIdx.x, blockDim.x);
+    for (uint32_t x = threadIdx.x; x < n; x += blockDim.x) lengths[x] = len[x];
+}
+
 // blocks first_block .. first_block + n_blocks - 1 of the uncompressed stream (stream_bytes = header + records; row_off[n_rows + 1] =
 // exclusive scan of the sorted rows' bytes, without the header).  deflate != 0: block b -> one BGZF member at out + b * slot_stride,
-// sizes[b] = its bytes.  deflate == 0: its uncompressed bytes at out + b * block_bytes.
-__global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTables bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
-                                                            const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
-                                                            unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
-                                                            uint32_t block_bytes, int deflate, uint32_t slot_stride, uint8_t* __restrict__ out,
-                                                            uint32_t* __restrict__ sizes) {
+// sizes[b] = its bytes.  deflate == 0: its uncompressed bytes at out + b * block_bytes.  DYN: deflate != 0 is deflate == 2.
+template <bool DYN> struct BamDynSlot { BamDynamic v; };
+template <> struct BamDynSlot<false> {};
+template <bool DYN>
+__device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTables& bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
+                                                const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
+                                                unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
+                                                uint32_t block_bytes, int deflate, uint32_t slot_stride, uint8_t* __restrict__ out,
+                                                uint32_t* __restrict__ sizes) {
     __shared__ uint32_t data32[(MIRGE_BAM_MAX_BLOCK + 256) / 4];
     __shared__ uint32_t out32[(MIRGE_BAM_MAX_BLOCK + 256) / 4];
     __shared__ uint32_t head[2u << MIRGE_BAM_HASH_BITS];
     __shared__ uint32_t crc_table[256];
     __shared__ uint32_t seg_bits[MIRGE_BLOCK + 1];
     __shared__ uint32_t s_crc;
+    __shared__ BamDynSlot<DYN> slot;
     uint8_t* data = reinterpret_cast<uint8_t*>(data32);
     const unsigned long long H = bt.header_len, body = row_off[n_rows];
     const uint32_t tid = threadIdx.x, nth = blockDim.x;
@@ -307,16 +550,29 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTabl
             crc_table[x] = c;
         }
         if (tid == 0) s_crc = 0u;
+        if constexpr (DYN) {
+            BamDynamic& dyn = slot.v;
+            for (uint32_t x = tid; x < MIRGE_BAM_HIST_COPIES * MIRGE_BAM_HUFF_MAX; x += nth) (&dyn.hist_ll[0][0])[x] = 0u;
+            for (uint32_t x = tid; x < MIRGE_BAM_HIST_COPIES * 32u; x += nth) (&dyn.hist_d[0][0])[x] = 0u;
+        }
         __syncthreads();
         for (uint32_t i = tid; i + MIRGE_BAM_MIN_MATCH <= n; i += nth) atomicMin(&head[bam_hash(bam_ld32(data, i), i)], i);
         __syncthreads();
         const uint32_t seg = (n + nth - 1) / nth;
         const uint32_t s0 = tid * seg < n ? tid * seg : n, s1 = s0 + seg < n ? s0 + seg : n;
         {
-            BamBits<false> cw;
-            cw.start(nullptr, 0u);
-            bam_parse<false>(data, head, s0, s1, cw);
-            seg_bits[tid] = cw.at;
+            if constexpr (DYN) {
+                BamDynamic& dyn = slot.v;
+                const uint32_t copy = (tid >> 6) % MIRGE_BAM_HIST_COPIES;
+                BamCount cw{0u, s0, dyn.hist_ll[copy], dyn.hist_d[copy], reinterpret_cast<uint8_t*>(out32)};
+                bam_parse(data, head, s0, s1, cw);
+                seg_bits[tid] = cw.at;
+            } else {
+                BamBits<false> cw;
+                cw.start(nullptr, 0u);
+                bam_parse(data, head, s0, s1, cw);
+                seg_bits[tid] = cw.at;
+            }
             uint32_t crc = 0xFFFFFFFFu;
             for (uint32_t x = s0; x < s1; x++) crc = crc_table[(crc ^ data[x]) & 255u] ^ (crc >> 8);
             if (s1 > s0) atomicXor(&s_crc, bam_crc_mul(bam_crc_x8n(n - s1), ~crc));
@@ -329,15 +585,55 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTabl
         }
         __syncthreads();
         const uint32_t end_bit = seg_bits[nth] + 7u;  // (the end-of-block code: seven zeros)
-        const bool stored = (end_bit + 7u) / 8u >= n + 5u;
-        const uint32_t clen = stored ? n + 5u : (end_bit + 7u) / 8u;
+        bool stored = (end_bit + 7u) / 8u >= n + 5u, dynamic = false;
+        uint32_t clen = stored ? n + 5u : (end_bit + 7u) / 8u;
+        if constexpr (DYN) {  // ---- the block's own code: its lengths, the header, every segment's bits; taken when it is the shortest form
+            BamDynamic& dyn = slot.v;
+            for (uint32_t x = tid; x < MIRGE_BAM_HUFF_MAX; x += nth)
+                dyn.hist_ll[0][x] += dyn.hist_ll[1][x] + dyn.hist_ll[2][x] + dyn.hist_ll[3][x] + (x == 256u ? 1u : 0u);  // (the end-of-block code: once)
+            for (uint32_t x = tid; x < 32u; x += nth) dyn.hist_d[0][x] += dyn.hist_d[1][x] + dyn.hist_d[2][x] + dyn.hist_d[3][x];
+            __syncthreads();
+            bam_huff_lengths2(dyn.hist_ll[0], MIRGE_BAM_NLL, dyn.len_ll, dyn.work[0], dyn.hist_d[0], MIRGE_BAM_ND, dyn.len_d, dyn.work[1], 15u, tid, nth);
+            dyn.seg[tid] = bam_dyn_bits(dyn, data, reinterpret_cast<const uint8_t*>(out32), s0, s1);
+            if (tid == 0) bam_dyn_header_tokens(dyn);
+            __syncthreads();
+            bam_huff_lengths2(dyn.cnt_cl[0], MIRGE_BAM_NCL, dyn.len_cl[0], dyn.work[0], dyn.cnt_cl[1], MIRGE_BAM_NCL, dyn.len_cl[1], dyn.work[1], 7u, tid, nth);
+            if (tid == 0) {  // exclusive sum of the segments' bits behind the header's
+                bam_dyn_header_choice(dyn);
+                uint32_t run = dyn.header_bits;
+                for (uint32_t x = 0; x < nth; x++) { const uint32_t v = dyn.seg[x]; dyn.seg[x] = run; run += v; }
+                dyn.seg[nth] = run + dyn.len_ll[256];
+            }
+            __syncthreads();
+            dynamic = (dyn.seg[nth] + 7u) / 8u < clen;
+            if (dynamic) { clen = (dyn.seg[nth] + 7u) / 8u; stored = false; }
+            for (uint32_t x = tid; x < (n + 16) / 4 + 1; x += nth) out32[x] = 0u;  // (the staged matches)
+            if (dynamic) {
+                bam_huff_codes(dyn.len_ll, MIRGE_BAM_NLL, dyn.code_ll, tid, nth);
+                bam_huff_codes(dyn.len_d, MIRGE_BAM_ND, dyn.code_d, tid, nth);
+                bam_huff_codes(dyn.len_cl[dyn.plain], MIRGE_BAM_NCL, dyn.code_cl, tid, nth);
+            }
+            __syncthreads();
+        }
         uint8_t* dst = out + (size_t)b * slot_stride;
         if (!stored) {
-            BamBits<true> ew;
-            ew.start(out32, seg_bits[tid]);
-            if (tid == 0) { ew.start(out32, 0u); ew.put(3u, 3); }  // BFINAL = 1, BTYPE = 01
-            bam_parse<true>(data, head, s0, s1, ew);
-            ew.finish();
+            if constexpr (DYN) if (dynamic) {
+                BamDynamic& dyn = slot.v;
+                BamDynBits ew;
+                ew.ll = dyn.code_ll; ew.dd = dyn.code_d;
+                ew.b.start(out32, dyn.seg[tid]);
+                if (tid == 0) { ew.b.start(out32, 0u); bam_dyn_put_header(dyn, ew.b); }
+                bam_parse(data, head, s0, s1, ew);
+                if (tid == nth - 1u) bam_put_code(ew.b, dyn.code_ll[256]);  // (every segment behind the block's end is empty: the last thread ends the stream)
+                ew.b.finish();
+            }
+            if (!dynamic) {
+                BamBits<true> ew;
+                ew.start(out32, seg_bits[tid]);
+                if (tid == 0) { ew.start(out32, 0u); ew.put(3u, 3); }  // BFINAL = 1, BTYPE = 01
+                bam_parse(data, head, s0, s1, ew);
+                ew.finish();
+            }
             __syncthreads();
             const uint8_t* ob = reinterpret_cast<const uint8_t*>(out32);
             for (uint32_t x = tid; x < clen; x += nth) dst[18 + x] = ob[x];
@@ -359,6 +655,26 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTabl
         }
         __syncthreads();
     }
+}
+// deflate == 2 is an instantiation of its own, so that the code and the registers of the other two stay what they are without it: on the
+// device k_bam_blocks_dynamic is its kernel (native_bam.hpp launches it for MIRGE_BAM_DEFLATE=dynamic) and k_bam_blocks does not hold
+// it; compiled for the host (tests/hostsim/bam_sim.cpp), where nothing is allocated, k_bam_blocks takes deflate == 2 as well.
+__global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTables bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
+                                                            const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
+                                                            unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
+                                                            uint32_t block_bytes, int deflate, uint32_t slot_stride, uint8_t* __restrict__ out,
+                                                            uint32_t* __restrict__ sizes) {
+#ifndef __HIP_DEVICE_COMPILE__
+    if (deflate == 2) { bam_blocks_body<true>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, deflate, slot_stride, out, sizes); return; }
+#endif
+    bam_blocks_body<false>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, deflate, slot_stride, out, sizes);
+}
+__global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks_dynamic(SamTables t, BamTables bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
+                                                                    const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
+                                                                    unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
+                                                                    uint32_t block_bytes, uint32_t slot_stride, uint8_t* __restrict__ out,
+                                                                    uint32_t* __restrict__ sizes) {
+    bam_blocks_body<true>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, 2, slot_stride, out, sizes);
 }
 
 // member b of a chunk from its slot to its place: off[] = exclusive scan of sizes[]

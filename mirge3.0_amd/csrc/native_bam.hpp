@@ -7,7 +7,8 @@
 // uncompressed stream never exists whole, neither on the device nor on the host.  The index is built per ROW on the host from the
 // sorted rows' stream offsets and the members' file offsets.
 // MIRGE_BAM_BLOCK_BYTES (64 .. 65280, default 65280): uncompressed bytes per BGZF block; MIRGE_BAM_CHUNK_BLOCKS: blocks per chunk
-// (default: 64 MiB of stream); MIRGE_BAM_DEFLATE=host: the blocks leave the device uncompressed and zlib level 6 deflates them on
+// (default: 64 MiB of stream); MIRGE_BAM_DEFLATE=device (the default): the fixed Huffman code; =dynamic: per block also a code of its
+// own (BTYPE 10), taken where it is shorter; =host: the blocks leave the device uncompressed and zlib level 6 deflates them on
 // `threads` host threads (the A/B route).  All read per call.
 #pragma once
 
@@ -104,8 +105,9 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     const uint32_t block = (uint32_t)std::min<size_t>(MIRGE_BAM_MAX_BLOCK, std::max<size_t>(64, sam_env_bytes("MIRGE_BAM_BLOCK_BYTES", MIRGE_BAM_MAX_BLOCK)));
     const size_t chunk_blocks = std::max<size_t>(1, std::min<size_t>(sam_env_bytes("MIRGE_BAM_CHUNK_BLOCKS", std::max<size_t>(1, ((size_t)64 << 20) / block)), (size_t)1 << 20));
     const char* dv = std::getenv("MIRGE_BAM_DEFLATE");
-    const bool on_host = dv && std::strcmp(dv, "host") == 0;
-    if (dv && *dv && !on_host && std::strcmp(dv, "device") != 0) return fail(-1, "mirge_bam_write_device: MIRGE_BAM_DEFLATE is 'device' or 'host'");
+    const bool on_host = dv && std::strcmp(dv, "host") == 0, dynamic = dv && std::strcmp(dv, "dynamic") == 0;
+    if (dv && *dv && !on_host && !dynamic && std::strcmp(dv, "device") != 0)
+        return fail(-1, "mirge_bam_write_device: MIRGE_BAM_DEFLATE is 'device', 'dynamic' or 'host'");
     const int T = std::max(1, std::min(threads > 0 ? threads : 16, 256));
     const uint32_t slot_stride = (block + 5u + 26u + 15u) & ~15u;
     const unsigned long long H = (unsigned long long)header_len;
@@ -291,9 +293,13 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
             const unsigned grid = (unsigned)std::min<size_t>(nb, (size_t)1 << 20);  // one workgroup per block: the hardware balances them
             {
                 LaunchScope ls(c, "k_bam_blocks", (double)nb * block);
-                hipLaunchKernelGGL(k_bam_blocks, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, (const uint32_t*)d_sfixed,
-                                   (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, on_host ? 0 : 1, slot_stride,
-                                   on_host ? d_comp[h] : d_slots, d_sizes);
+                if (dynamic)  // deflate == 2: an instantiation of its own (kernels_bam.hpp)
+                    hipLaunchKernelGGL(k_bam_blocks_dynamic, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
+                                       (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
+                else
+                    hipLaunchKernelGGL(k_bam_blocks, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, (const uint32_t*)d_sfixed,
+                                       (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, on_host ? 0 : 1, slot_stride,
+                                       on_host ? d_comp[h] : d_slots, d_sizes);
             }
             if (on_host) {
                 const size_t nn = (size_t)(std::min<unsigned long long>(stream_bytes, (b0 + nb) * block) - b0 * block);
@@ -348,5 +354,29 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
         if (n_stream_bytes_out) *n_stream_bytes_out = (int64_t)(H + body);
         if (n_file_bytes_out) *n_file_bytes_out = n_file;
     }
+    return rc;
+}
+
+// bam_huff_lengths (kernels_bam.hpp) alone on the device: the code lengths of counts[n_sym] under the limit max_bits
+extern "C" int mirge_bam_huffman_probe(mirge_ctx* c, const uint32_t* counts, int32_t n_sym, int32_t max_bits, uint8_t* lengths_out) {
+    if (!c || !counts || !lengths_out || n_sym < 1 || n_sym > MIRGE_BAM_HUFF_MAX || max_bits < 1 || max_bits > 15 || (1 << max_bits) < n_sym)
+        return fail(-1, "mirge_bam_huffman_probe: 1 .. " + std::to_string(MIRGE_BAM_HUFF_MAX) + " symbols, max_bits 1 .. 15 with 2^max_bits >= the symbols");
+    HIPOK(hipSetDevice(c->device));
+    uint32_t* d_cnt = nullptr;
+    uint8_t* d_len = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = dalloc(c, &d_cnt, (size_t)n_sym))) break;
+        if ((rc = dalloc(c, &d_len, (size_t)n_sym + 16))) break;
+        hipError_t e = hipMemcpyAsync(d_cnt, counts, (size_t)n_sym * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_bam_huff_probe, dim3(1), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_cnt, (uint32_t)n_sym, (uint32_t)max_bits, d_len);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(lengths_out, d_len, (size_t)n_sym, hipMemcpyDeviceToHost, c->stream);
+        { const hipError_t e2 = hipStreamSynchronize(c->stream); if (e == hipSuccess) e = e2; }
+        if (e != hipSuccess) rc = fail(-2, std::string("mirge_bam_huffman_probe: ") + hipGetErrorString(e));
+    } while (0);
+    c->release(d_cnt); c->release(d_len);
     return rc;
 }
