@@ -476,7 +476,9 @@ int mirge_sam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
  * characters.  *n_records_out = records, *n_stream_bytes_out = uncompressed bytes, *n_file_bytes_out = bytes of the .bam.
  * `threads` sizes the host pool of MIRGE_BAM_DEFLATE=host.  MIRGE_BAM_DEFLATE=device (the default) deflates every block on the device
  * with the fixed Huffman code or stores it; =dynamic adds a Huffman code built per block (BTYPE 10) and takes it where its member is
- * strictly smaller, so no member grows; =host sends the blocks through zlib on the host; any other value is an error.
+ * strictly smaller, so no member grows; =tight chooses among the same forms on the tokens of a closer parse (matches across the
+ * threads' segments, record-aligned, repeat-distance and region candidates, one lazy step): no member larger than its stored form, no
+ * promise per member against the other routes; =host sends the blocks through zlib on the host; any other value is an error.
  * MIRGE_BAM_BLOCK_BYTES / MIRGE_BAM_CHUNK_BLOCKS: README. */
 int mirge_bam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
                            const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,

@@ -198,7 +198,8 @@ def refid_tables(casc, organism: str, refs: Sequence[Tuple[str, int]]):
 
 def write_sample(casc, uniq, res, order: np.ndarray, sample: int, bam_path, bai_path, header: bytes, organism: str,
                  threads: Optional[int] = None):
-    """One sample's pair of files through ``mirge_bam_write_device``; -> (records, uncompressed bytes, bytes of the .bam)"""
+    """One sample's pair of files through ``mirge_bam_write_device``; -> (records, uncompressed bytes, bytes of the .bam).
+    ``MIRGE_BAM_DEFLATE``, read per call, names the route: ``device`` (the default), ``dynamic``, ``tight`` or ``host``"""
     blob, refs = header_blob(header)
     classes, arr, _keep = sam_export.pass_tables(casc, organism)
     order = np.ascontiguousarray(order, dtype=np.int64)

@@ -113,10 +113,12 @@ def parse_args(argv=None):
                     help="write <sample>_sorted.bam and <sample>_sorted.bai for every sample: the records of --sam-out's <sample>.sam as "
                          "BAM, coordinate-sorted, BGZF-compressed and indexed on the device (what the reference's -bam gets from samtools "
                          "view / sort / index); needs --sam-header FILE with the genome's @SQ lines; independent of --sam-out")
-    ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "host"),
+    ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "tight", "host"),
                     help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
                          "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
-                         "its own, taken where the member gets smaller; host: zlib level 6 on host threads")
+                         "its own, taken where the member gets smaller; tight: as dynamic, on a closer parse (matches across the "
+                         "threads' segments, nearer candidates, one lazy step: smaller files, more device time); host: zlib level 6 "
+                         "on host threads")
     ap.add_argument("--trf-report", dest="trf_report", action="store_true",
                     help="write the tRNA fragment reports of the reference's -trf up to its per-sample reports: tRFs.aligned.report.tsv, "
                          "tRF.Counts.csv, tRF.RP100K.csv, discarded.reads.summary.assigningtRFs.csv and tRFs.samples.tmp/<sample>."

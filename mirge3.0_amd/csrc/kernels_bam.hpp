@@ -24,6 +24,27 @@
 //                   15 bits; 7 for the code of the lengths themselves), a walk over the staged matches -- no match search -- gives
 //                   every segment its bits under that code, and the form goes out when its bytes are fewer than those of the better
 //                   of the other two: no member is larger than under deflate = 1.  k_bam_huff_probe: bam_huff_lengths alone.
+//                   deflate = 3 (MIRGE_BAM_DEFLATE=tight; on the device the kernel k_bam_blocks_tight): the blocks, the CRC, the code
+//                   builder, the header and the choice of the form of deflate = 2, on the tokens of another parse:
+//                     - a match may run on behind its thread's segment, to the block's end or 258 bytes.  e_t = where thread t's
+//                       last token ends; E_t = the maximum of e_j over j < t (one prefix maximum): thread t drops its tokens that
+//                       end at or in front of E_t, trims the one across E_t to its suffix (same distance; a suffix shorter than
+//                       the minimum match becomes literals) and emits [E_t, E_t+1).  The first search leaves a match that ends
+//                       inside its segment at its own bytes of the output words, as deflate = 2 does, and keeps the last one, which
+//                       may start in the segment's last bytes, in registers: nothing is staged in another thread's bytes.  Counts,
+//                       histograms and bit offsets are taken from the trimmed tokens, behind the prefix maximum; the output words
+//                       hold the staged matches until then, so the emitting walk searches a second time (same tokens: the search
+//                       is a function of the block's bytes).
+//                     - candidates: the byte in front; the distance of the thread's last match; the same offset in the previous
+//                       record and the same distance from the record's end (distances: the previous and this record's length --
+//                       the thread finds the record at its segment's start as a probe point does and walks on by the block_size
+//                       words); per 4 KiB region of the block the FIRST position with the hash, 16 x 512 entries of 16 bits in
+//                       head's 16 KB: the entry of the position's own region and of the MIRGE_BAM_TIGHT_LOOKBACK regions in front.
+//                       The longest wins, of equally long ones the nearest.
+//                     - one step of lazy matching: a match shorter than MIRGE_BAM_TIGHT_LAZY_BELOW gives way to a literal when the
+//                       match one byte on is longer by more than one, or as long and nearer; a longer match from a region table
+//                       gives way when one of the table-free candidates one byte on is as long and nearer.
+//                   No promise per member against the other routes: another greedy parse can lose on a single block.
 // No wave intrinsics: the same source runs on the host (tests/hostsim/bam_sim.cpp).
 #pragma once
 
@@ -268,6 +289,10 @@ struct BamHuffWork { uint32_t a[MIRGE_BAM_HUFF_MAX]; uint32_t bl[16]; uint16_t o
 //     the Kraft sum is above 1, a leaf of the greatest length below max_bits moves one level down with a leaf of max_bits as its
 //     sibling (each step takes 2^-max_bits off the sum); the lengths go out longest first to the rarest symbols.
 // k_bam_blocks calls the two steps itself: two codes at a time, their trees on two threads of different waves.
+// OWN: k_bam_blocks_tight's copies of what takes pointers into the block's BamDynamic.  While k_bam_blocks_dynamic is the only caller the
+// compiler folds its one LDS block's addresses into these functions before it inlines them; a second caller's other block ends that, and
+// the dynamic kernel then compiles to other code (same registers and LDS, another schedule).  With copies of its own it stays what it was.
+template <bool OWN = false>
 __device__ __forceinline__ void bam_huff_rank(const uint32_t* cnt, uint32_t n, uint8_t* len, BamHuffWork& w, uint32_t tid, uint32_t nth) {
     for (uint32_t s = tid; s < n; s += nth) {
         const uint32_t c = cnt[s];
@@ -278,6 +303,7 @@ __device__ __forceinline__ void bam_huff_rank(const uint32_t* cnt, uint32_t n, u
         w.order[rank] = (uint16_t)s; w.a[rank] = c;
     }
 }
+template <bool OWN = false>
 __device__ __forceinline__ void bam_huff_tree(const uint32_t* cnt, uint32_t n, uint32_t max_bits, uint8_t* len, BamHuffWork& w) {
     uint32_t* A = w.a;
     uint32_t m = 0;
@@ -321,13 +347,14 @@ __device__ __forceinline__ void bam_huff_lengths(const uint32_t* cnt, uint32_t n
     __syncthreads();
 }
 // two codes at once: the second one's tree is thread nth / 2's
+template <bool OWN = false>
 __device__ __forceinline__ void bam_huff_lengths2(const uint32_t* cnt0, uint32_t n0, uint8_t* len0, BamHuffWork& w0, const uint32_t* cnt1, uint32_t n1, uint8_t* len1,
                                                   BamHuffWork& w1, uint32_t max_bits, uint32_t tid, uint32_t nth) {
-    bam_huff_rank(cnt0, n0, len0, w0, tid, nth);
-    bam_huff_rank(cnt1, n1, len1, w1, tid, nth);
+    bam_huff_rank<OWN>(cnt0, n0, len0, w0, tid, nth);
+    bam_huff_rank<OWN>(cnt1, n1, len1, w1, tid, nth);
     __syncthreads();
-    if (tid == 0) bam_huff_tree(cnt0, n0, max_bits, len0, w0);
-    if (tid == nth / 2u) bam_huff_tree(cnt1, n1, max_bits, len1, w1);
+    if (tid == 0) bam_huff_tree<OWN>(cnt0, n0, max_bits, len0, w0);
+    if (tid == nth / 2u) bam_huff_tree<OWN>(cnt1, n1, max_bits, len1, w1);
     __syncthreads();
 }
 // the canonical code of lengths len[0 .. n) (RFC 1951, 3.2.2), bit-reversed for the LSB-first stream: code[s] = bits | length << 16.
@@ -360,6 +387,7 @@ struct BamDynamic {
     uint8_t len_ll[MIRGE_BAM_HUFF_MAX], len_d[32], len_cl[2][32];
 };
 // length k of the HLIT + HDIST lengths the header spells, as one sequence
+template <bool OWN = false>
 __device__ __forceinline__ uint32_t bam_dyn_seq(const BamDynamic& y, uint32_t k) { return k < y.hlit ? y.len_ll[k] : y.len_d[k - y.hlit]; }
 
 // the counting walk of deflate == 2: the segment's bits under the fixed code, as BamBits<false> counts them; its symbols into the wave's
@@ -408,6 +436,7 @@ __device__ __forceinline__ void bam_put_match(BamDynBits& w, uint32_t len, uint3
 // thread 0, the lengths of both codes known: HLIT, HDIST, and the sequence of their lengths in the symbols 0 .. 18 twice -- with the
 // run symbols (16: the length in front 3 to 6 times more, 17: 3 to 10 zeros, 18: 11 to 138 zeros; greedy, a run may cross from one code
 // into the other) into tok, and plain, a symbol per length -- and either form's counts
+template <bool OWN = false>
 __device__ __forceinline__ void bam_dyn_header_tokens(BamDynamic& y) {
     uint32_t hlit = MIRGE_BAM_NLL, hdist = MIRGE_BAM_ND, any = 0;
     for (uint32_t x = 0; x < MIRGE_BAM_ND; x++) any |= y.len_d[x];
@@ -419,9 +448,9 @@ __device__ __forceinline__ void bam_dyn_header_tokens(BamDynamic& y) {
     const uint32_t N = hlit + hdist;
     uint32_t nt = 0;
     for (uint32_t k = 0; k < N;) {
-        const uint32_t v = bam_dyn_seq(y, k);
+        const uint32_t v = bam_dyn_seq<OWN>(y, k);
         uint32_t run = 1;
-        while (k + run < N && bam_dyn_seq(y, k + run) == v) run++;
+        while (k + run < N && bam_dyn_seq<OWN>(y, k + run) == v) run++;
         k += run;
         y.cnt_cl[1][v] += run;
         if (v) { y.tok[nt++] = (uint16_t)v; y.cnt_cl[0][v]++; run--; }
@@ -435,6 +464,7 @@ __device__ __forceinline__ void bam_dyn_header_tokens(BamDynamic& y) {
     y.n_tok = nt;
 }
 // thread 0, the lengths of the code of either form known: the shorter header (a tie: the one with run symbols), HCLEN, its bits with BFINAL and BTYPE
+template <bool OWN = false>
 __device__ __forceinline__ void bam_dyn_header_choice(BamDynamic& y) {
     uint32_t bits[2], hclen[2];
     for (uint32_t f = 0; f < 2u; f++) {
@@ -448,19 +478,210 @@ __device__ __forceinline__ void bam_dyn_header_choice(BamDynamic& y) {
     y.hclen = y.plain ? hclen[1] : hclen[0];
 }
 // thread 0: the header into the output words
+template <bool OWN = false>
 __device__ __forceinline__ void bam_dyn_put_header(const BamDynamic& y, BamBits<true>& b) {
     b.put(5u, 3);  // BFINAL = 1, BTYPE = 10
     b.put(y.hlit - 257u, 5); b.put(y.hdist - 1u, 5); b.put(y.hclen - 4u, 4);
     const uint8_t* cl = y.len_cl[y.plain];
     for (uint32_t k = 0; k < y.hclen; k++) b.put(cl[bam_cl_order(k)], 3);
     if (y.plain)
-        for (uint32_t k = 0; k < y.hlit + y.hdist; k++) bam_put_code(b, y.code_cl[bam_dyn_seq(y, k)]);
+        for (uint32_t k = 0; k < y.hlit + y.hdist; k++) bam_put_code(b, y.code_cl[bam_dyn_seq<OWN>(y, k)]);
     else
         for (uint32_t k = 0; k < y.n_tok; k++) {
             const uint32_t sym = y.tok[k] & 255u;
             bam_put_code(b, y.code_cl[sym]);
             if (sym >= 16u) b.put((uint32_t)y.tok[k] >> 8, sym == 16u ? 2 : sym == 17u ? 3 : 7);
         }
+}
+
+// ---- the parse of deflate == 3.  Build knobs (-D): MIRGE_BAM_TIGHT_LAZY (0: no lazy step), MIRGE_BAM_TIGHT_LAZY_BELOW (a match of
+// this length or longer is taken at once), MIRGE_BAM_TIGHT_LOOKBACK (regions in front of the position's own whose entry is tried),
+// and, for tools/bam_parse_sizes.py's table of what each ingredient buys, MIRGE_BAM_TIGHT_RECORD, MIRGE_BAM_TIGHT_REPEAT (0: without
+// that candidate) and MIRGE_BAM_TIGHT_REGIONS (0: the other routes' two first-position tables instead of the region tables).
+#ifndef MIRGE_BAM_TIGHT_LAZY
+#define MIRGE_BAM_TIGHT_LAZY 1
+#endif
+#ifndef MIRGE_BAM_TIGHT_LAZY_BELOW
+#define MIRGE_BAM_TIGHT_LAZY_BELOW 32
+#endif
+#ifndef MIRGE_BAM_TIGHT_LOOKBACK
+#define MIRGE_BAM_TIGHT_LOOKBACK 2
+#endif
+#ifndef MIRGE_BAM_TIGHT_RECORD
+#define MIRGE_BAM_TIGHT_RECORD 1
+#endif
+#ifndef MIRGE_BAM_TIGHT_REPEAT
+#define MIRGE_BAM_TIGHT_REPEAT 1
+#endif
+#ifndef MIRGE_BAM_TIGHT_REGIONS
+#define MIRGE_BAM_TIGHT_REGIONS 1
+#endif
+#define MIRGE_BAM_REGION_BITS 12       // a region: 4 KiB of the block
+#define MIRGE_BAM_REGION_HASH_BITS 9   // its buckets
+#define MIRGE_BAM_MAX_DIST 32768u
+static_assert((((MIRGE_BAM_MAX_BLOCK - 1) >> MIRGE_BAM_REGION_BITS) + 1) << MIRGE_BAM_REGION_HASH_BITS <= (4u << MIRGE_BAM_HASH_BITS),
+              "the region tables' 16-bit entries lie in head's words");
+static_assert((MIRGE_BAM_TIGHT_LOOKBACK + 1) << MIRGE_BAM_REGION_BITS <= MIRGE_BAM_MAX_DIST, "a region candidate's distance fits the window");
+
+__device__ __forceinline__ uint32_t bam_region_slot(uint32_t v, uint32_t region) {
+    return (region << MIRGE_BAM_REGION_HASH_BITS) | ((v * 2654435761u) >> (32 - MIRGE_BAM_REGION_HASH_BITS));
+}
+__device__ __forceinline__ uint32_t bam_region_get(const uint32_t* tab, uint32_t slot) { return (tab[slot >> 1] >> ((slot & 1u) * 16u)) & 0xFFFFu; }
+// entry `slot` = min(entry, v), v < 0xFFFF (an empty entry): the minimum does not depend on the order of the calls
+__device__ __forceinline__ void bam_region_min(uint32_t* tab, uint32_t slot, uint32_t v) {
+    uint32_t* w = &tab[slot >> 1];
+    const uint32_t sh = (slot & 1u) * 16u;
+    uint32_t old = *w;
+    while (((old >> sh) & 0xFFFFu) > v) {
+        const uint32_t got = atomicCAS(w, old, (old & ~(0xFFFFu << sh)) | (v << sh));
+        if (got == old) break;
+        old = got;
+    }
+}
+
+// a thread's search state: the record that holds the position (start rs in block coordinates, possibly in front of the block; rl
+// bytes; pl: the bytes of the record in front, a guess at the segment's start) and the distance of its last match
+struct BamTight { const uint8_t* d; const uint32_t* tab; uint32_t n; long long rs; uint32_t rl, pl, rep; };
+// the state at block byte s0 (stream byte ustart + s0): the header counts as one record without a neighbour
+__device__ __forceinline__ void bam_tight_start(const SamTables& t, const BamTables& bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
+                                                const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
+                                                unsigned long long ustart, uint32_t s0, BamTight& c) {
+    const unsigned long long H = bt.header_len, S = ustart + s0, far = 1ull << 30;
+    c.rs = (long long)s0; c.rl = (uint32_t)far; c.pl = 0u; c.rep = 0u;
+    if (S < H) { c.rl = (uint32_t)(H - S < far ? H - S : far); return; }
+    const unsigned long long P = S - H;
+    uint32_t lo = 0, hi = n_rows;  // the row with row_off[row] <= P < row_off[row + 1]
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (row_off[mid + 1] <= P) lo = mid + 1; else hi = mid; }
+    if (lo >= n_rows) return;
+    BamRow br;
+    bam_row(t, bt, rows[lo], br);
+    const unsigned long long F = fixed[lo];
+    unsigned long long q = P - row_off[lo], rec_start = row_off[lo], b_lo = 0, b_hi = 10, len = F + 1ull;
+    for (int d = 1; d <= 10; d++) {  // the digit band of k that holds byte q of the row
+        const unsigned long long nk = (br.c < b_hi ? br.c : b_hi) - b_lo, ll = F + (unsigned long long)d;
+        if (q < nk * ll) { rec_start += (q / ll) * ll; len = ll; break; }
+        q -= nk * ll; rec_start += nk * ll;
+        b_lo = b_hi; b_hi *= 10;
+    }
+    c.rs = (long long)(rec_start + H) - (long long)ustart; c.rl = c.pl = (uint32_t)len;
+}
+// on to the record that holds block byte i: a record's first word is the bytes behind it (a match is shorter than eight records)
+__device__ __forceinline__ void bam_tight_record(BamTight& c, uint32_t i) {
+    for (int g = 0; g < 8 && (long long)i >= c.rs + (long long)c.rl; g++) {
+        c.rs += (long long)c.rl; c.pl = c.rl;
+        if (c.rs + 4 <= (long long)c.n) c.rl = (bam_ld32(c.d, (uint32_t)c.rs) & 0xFFFFFu) + 4u;
+    }
+}
+// the candidate `dist` bytes in front of i: taken when it is longer than the best so far, or as long and nearer
+__device__ __forceinline__ void bam_tight_try(const uint8_t* d, uint32_t i, uint32_t dist, uint32_t lim, uint32_t& best, uint32_t& bdist) {
+    if (dist - 1u >= MIRGE_BAM_MAX_DIST || dist > i || dist == bdist) return;
+    const uint8_t* a = d + i;
+    const uint8_t* b = a - dist;
+    if (best && b[best - 1u] != a[best - 1u]) return;
+    uint32_t k = 0;
+    while (k < lim && b[k] == a[k]) k++;
+    if (k >= MIRGE_BAM_MIN_MATCH && (k > best || (k == best && dist < bdist))) { best = k; bdist = dist; }
+}
+// the best match at i; near: of the candidates that cost no table look-up alone
+__device__ __forceinline__ void bam_tight_find(const BamTight& c, uint32_t i, uint32_t& best, uint32_t& bdist, bool near = false) {
+    best = 0u; bdist = 0u;
+    if (i + MIRGE_BAM_MIN_MATCH > c.n) return;
+    const uint32_t lim = c.n - i < MIRGE_BAM_MAX_MATCH ? c.n - i : MIRGE_BAM_MAX_MATCH;
+    bam_tight_try(c.d, i, 1u, lim, best, bdist);
+    if (MIRGE_BAM_TIGHT_REPEAT) bam_tight_try(c.d, i, c.rep, lim, best, bdist);
+    if (MIRGE_BAM_TIGHT_RECORD) { bam_tight_try(c.d, i, c.pl, lim, best, bdist); bam_tight_try(c.d, i, c.rl, lim, best, bdist); }
+    if (best >= lim || near) return;
+    const uint32_t v = bam_ld32(c.d, i);
+    if (MIRGE_BAM_TIGHT_REGIONS) {
+        const uint32_t r = i >> MIRGE_BAM_REGION_BITS;
+        for (uint32_t back = 0; back <= (uint32_t)MIRGE_BAM_TIGHT_LOOKBACK && back <= r; back++) {
+            const uint32_t e = bam_region_get(c.tab, bam_region_slot(v, r - back));
+            if (e == 0xFFFFu) continue;
+            const uint32_t at = ((r - back) << MIRGE_BAM_REGION_BITS) | e;
+            if (at < i) bam_tight_try(c.d, i, i - at, lim, best, bdist);
+        }
+    } else {
+        const uint32_t at = c.tab[bam_hash(v, i)];
+        if (at < i) bam_tight_try(c.d, i, i - at, lim, best, bdist);
+    }
+}
+// segment [s0, s1) into a sink S: literal(position), match(position, length, distance); a match may end behind s1.  Returns the end of
+// the last token.
+template <class S>
+__device__ __forceinline__ uint32_t bam_tight_parse(BamTight c, uint32_t s0, uint32_t s1, S& sink) {
+    uint32_t i = s0;
+    while (i < s1) {
+        uint32_t len, dist;
+        bam_tight_record(c, i);
+        bam_tight_find(c, i, len, dist);
+        if (MIRGE_BAM_TIGHT_LAZY && len && i + 1u < s1) {
+            // a short match: everything one byte on; a long one from a table: only what is nearer (copy k of a row finds copy k - 10 at
+            // its last digit, one byte in front of where copy k - 1 starts to match, for four more distance bits per record)
+            const bool shortm = len < (uint32_t)MIRGE_BAM_TIGHT_LAZY_BELOW;
+            if (shortm || (dist != 1u && dist != c.rep && dist != c.pl && dist != c.rl)) {
+                uint32_t len1, dist1;
+                bam_tight_find(c, i + 1u, len1, dist1, !shortm);
+                if (len1 > len + 1u || (len1 >= len && dist1 < dist)) { sink.literal(i); i++; len = len1; dist = dist1; }
+            }
+        }
+        if (len) { sink.match(i, len, dist); c.rep = dist; i += len; }
+        else { sink.literal(i); i++; }
+    }
+    return i;
+}
+// the first search's sink: a match that ends inside the segment in the form of BamCount at its own bytes of tok; the last token, if it
+// is a match that reaches the segment's end or runs on behind it, in fin_pos and fin_v (its first three bytes may be another thread's)
+struct BamStage {
+    uint8_t* tok; uint32_t s1, fin_pos, fin_v;
+    __device__ __forceinline__ void literal(uint32_t) {}
+    __device__ __forceinline__ void match(uint32_t i, uint32_t len, uint32_t dist) {
+        const uint32_t v = (len - 3u) | ((dist - 1u) << 8);
+        if (i + len >= s1) { fin_pos = i; fin_v = v; return; }
+        tok[i] = (uint8_t)(0x80u | (v & 0x7Fu)); tok[i + 1u] = (uint8_t)(v >> 7); tok[i + 2u] = (uint8_t)(v >> 15);
+    }
+};
+// the tokens of segment [s0, s1) again, from what BamStage left
+template <class S>
+__device__ __forceinline__ void bam_tight_walk(const uint8_t* tok, uint32_t s0, uint32_t s1, uint32_t fin_pos, uint32_t fin_v, S& sink) {
+    for (uint32_t i = s0; i < s1;) {
+        uint32_t v;
+        if (i == fin_pos) v = fin_v;
+        else if (tok[i] & 0x80u) v = (tok[i] & 0x7Fu) | ((uint32_t)tok[i + 1u] << 7) | ((uint32_t)tok[i + 2u] << 15);
+        else { sink.literal(i); i++; continue; }
+        sink.match(i, (v & 255u) + 3u, (v >> 8) + 1u);
+        i += (v & 255u) + 3u;
+    }
+}
+// a thread's tokens from E on into W (bam_put_literal, bam_put_match): those in front are dropped, the one across E is cut to its suffix
+template <class W>
+struct BamTrim {
+    W& w; const uint8_t* d; uint32_t E;
+    __device__ __forceinline__ void literal(uint32_t i) { if (i >= E) bam_put_literal(w, d[i]); }
+    __device__ __forceinline__ void match(uint32_t i, uint32_t len, uint32_t dist) {
+        const uint32_t end = i + len;
+        if (end <= E) return;
+        if (i < E) {
+            len = end - E;
+            if (len < MIRGE_BAM_MIN_MATCH) { for (uint32_t k = E; k < end; k++) bam_put_literal(w, d[k]); return; }
+        }
+        bam_put_match(w, len, dist);
+    }
+};
+// BamTrim's W of the counting walk: the bits under the fixed code, the symbols into the wave's histograms
+struct BamTally { uint32_t at; uint32_t* ll; uint32_t* dd; };
+__device__ __forceinline__ void bam_put_literal(BamTally& w, uint32_t b) { w.at += b < 144u ? 8u : 9u; atomicAdd(&w.ll[b], 1u); }
+__device__ __forceinline__ void bam_put_match(BamTally& w, uint32_t len, uint32_t dist) {
+    const BamMatchCode m = bam_match_code(len, dist);
+    w.at += (m.idx <= 22u ? 7u : 8u) + m.xb + 5u + m.db;
+    atomicAdd(&w.ll[257u + m.idx], 1u);
+    atomicAdd(&w.dd[m.dc], 1u);
+}
+// and of the walk that sizes the segments under the block's own code
+struct BamDynTally { uint32_t bits; const BamDynamic* y; };
+__device__ __forceinline__ void bam_put_literal(BamDynTally& w, uint32_t b) { w.bits += w.y->len_ll[b]; }
+__device__ __forceinline__ void bam_put_match(BamDynTally& w, uint32_t len, uint32_t dist) {
+    const BamMatchCode m = bam_match_code(len, dist);
+    w.bits += w.y->len_ll[257u + m.idx] + m.xb + w.y->len_d[m.dc] + m.db;
 }
 
 // bam_huff_lengths alone, one workgroup (mirge_bam_huffman_probe: a payload that drives the real parse into the 15-bit limit cannot
@@ -478,10 +699,14 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_huff_probe(const uint32_t* 
 
 // blocks first_block .. first_block + n_blocks - 1 of the uncompressed stream (stream_bytes = header + records; row_off[n_rows + 1] =
 // exclusive scan of the sorted rows' bytes, without the header).  deflate != 0: block b -> one BGZF member at out + b * slot_stride,
-// sizes[b] = its bytes.  deflate == 0: its uncompressed bytes at out + b * block_bytes.  DYN: deflate != 0 is deflate == 2.
+// sizes[b] = its bytes.  deflate == 0: its uncompressed bytes at out + b * block_bytes.  DYN: deflate != 0 is deflate == 2, or, with
+// TIGHT, deflate == 3.
 template <bool DYN> struct BamDynSlot { BamDynamic v; };
 template <> struct BamDynSlot<false> {};
-template <bool DYN>
+// deflate == 3, per thread: the search state at its segment's start, what it emits ([E0, E1)), its last match
+template <bool TIGHT> struct BamTightRegs { BamTight c; uint32_t E0, E1, fin_pos, fin_v; };
+template <> struct BamTightRegs<false> {};
+template <bool DYN, bool TIGHT = false>
 __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTables& bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
                                                 const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
                                                 unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
@@ -494,6 +719,7 @@ __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTab
     __shared__ uint32_t seg_bits[MIRGE_BLOCK + 1];
     __shared__ uint32_t s_crc;
     __shared__ BamDynSlot<DYN> slot;
+    static_assert(DYN || !TIGHT, "the tight parse goes with the block's own code");
     uint8_t* data = reinterpret_cast<uint8_t*>(data32);
     const unsigned long long H = bt.header_len, body = row_off[n_rows];
     const uint32_t tid = threadIdx.x, nth = blockDim.x;
@@ -556,12 +782,38 @@ __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTab
             for (uint32_t x = tid; x < MIRGE_BAM_HIST_COPIES * 32u; x += nth) (&dyn.hist_d[0][0])[x] = 0u;
         }
         __syncthreads();
-        for (uint32_t i = tid; i + MIRGE_BAM_MIN_MATCH <= n; i += nth) atomicMin(&head[bam_hash(bam_ld32(data, i), i)], i);
+        if constexpr (TIGHT && MIRGE_BAM_TIGHT_REGIONS) {
+            for (uint32_t i = tid; i + MIRGE_BAM_MIN_MATCH <= n; i += nth)
+                bam_region_min(head, bam_region_slot(bam_ld32(data, i), i >> MIRGE_BAM_REGION_BITS), i & ((1u << MIRGE_BAM_REGION_BITS) - 1u));
+        } else
+            for (uint32_t i = tid; i + MIRGE_BAM_MIN_MATCH <= n; i += nth) atomicMin(&head[bam_hash(bam_ld32(data, i), i)], i);
         __syncthreads();
         const uint32_t seg = (n + nth - 1) / nth;
         const uint32_t s0 = tid * seg < n ? tid * seg : n, s1 = s0 + seg < n ? s0 + seg : n;
+        BamTightRegs<TIGHT> tr;
         {
-            if constexpr (DYN) {
+            if constexpr (TIGHT) {
+                BamDynamic& dyn = slot.v;
+                BamStage st{reinterpret_cast<uint8_t*>(out32), s1, 0xFFFFFFFFu, 0u};
+                tr.c = BamTight{data, head, n, 0ll, 0u, 0u, 0u};
+                if (s0 < s1) bam_tight_start(t, bt, rows, n_rows, fixed, row_off, ustart, s0, tr.c);
+                seg_bits[tid] = bam_tight_parse(tr.c, s0, s1, st);
+                tr.fin_pos = st.fin_pos; tr.fin_v = st.fin_v;
+                __syncthreads();
+                if (tid == 0) {  // E_t: where the tokens of the threads in front end
+                    uint32_t run = 0u;
+                    for (uint32_t x = 0; x < nth; x++) { const uint32_t v = seg_bits[x]; seg_bits[x] = run; run = v > run ? v : run; }
+                    seg_bits[nth] = run;
+                }
+                __syncthreads();
+                tr.E0 = seg_bits[tid]; tr.E1 = seg_bits[tid + 1u];
+                __syncthreads();
+                const uint32_t copy = (tid >> 6) % MIRGE_BAM_HIST_COPIES;
+                BamTally cw{0u, dyn.hist_ll[copy], dyn.hist_d[copy]};
+                BamTrim<BamTally> tw{cw, data, tr.E0};
+                if (tr.E1 > tr.E0) bam_tight_walk(reinterpret_cast<const uint8_t*>(out32), s0, s1, tr.fin_pos, tr.fin_v, tw);
+                seg_bits[tid] = cw.at;
+            } else if constexpr (DYN) {
                 BamDynamic& dyn = slot.v;
                 const uint32_t copy = (tid >> 6) % MIRGE_BAM_HIST_COPIES;
                 BamCount cw{0u, s0, dyn.hist_ll[copy], dyn.hist_d[copy], reinterpret_cast<uint8_t*>(out32)};
@@ -593,13 +845,19 @@ __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTab
                 dyn.hist_ll[0][x] += dyn.hist_ll[1][x] + dyn.hist_ll[2][x] + dyn.hist_ll[3][x] + (x == 256u ? 1u : 0u);  // (the end-of-block code: once)
             for (uint32_t x = tid; x < 32u; x += nth) dyn.hist_d[0][x] += dyn.hist_d[1][x] + dyn.hist_d[2][x] + dyn.hist_d[3][x];
             __syncthreads();
-            bam_huff_lengths2(dyn.hist_ll[0], MIRGE_BAM_NLL, dyn.len_ll, dyn.work[0], dyn.hist_d[0], MIRGE_BAM_ND, dyn.len_d, dyn.work[1], 15u, tid, nth);
-            dyn.seg[tid] = bam_dyn_bits(dyn, data, reinterpret_cast<const uint8_t*>(out32), s0, s1);
-            if (tid == 0) bam_dyn_header_tokens(dyn);
+            bam_huff_lengths2<TIGHT>(dyn.hist_ll[0], MIRGE_BAM_NLL, dyn.len_ll, dyn.work[0], dyn.hist_d[0], MIRGE_BAM_ND, dyn.len_d, dyn.work[1], 15u, tid, nth);
+            if constexpr (TIGHT) {
+                BamDynTally cw{0u, &dyn};
+                BamTrim<BamDynTally> tw{cw, data, tr.E0};
+                if (tr.E1 > tr.E0) bam_tight_walk(reinterpret_cast<const uint8_t*>(out32), s0, s1, tr.fin_pos, tr.fin_v, tw);
+                dyn.seg[tid] = cw.bits;
+            } else
+                dyn.seg[tid] = bam_dyn_bits(dyn, data, reinterpret_cast<const uint8_t*>(out32), s0, s1);
+            if (tid == 0) bam_dyn_header_tokens<TIGHT>(dyn);
             __syncthreads();
-            bam_huff_lengths2(dyn.cnt_cl[0], MIRGE_BAM_NCL, dyn.len_cl[0], dyn.work[0], dyn.cnt_cl[1], MIRGE_BAM_NCL, dyn.len_cl[1], dyn.work[1], 7u, tid, nth);
+            bam_huff_lengths2<TIGHT>(dyn.cnt_cl[0], MIRGE_BAM_NCL, dyn.len_cl[0], dyn.work[0], dyn.cnt_cl[1], MIRGE_BAM_NCL, dyn.len_cl[1], dyn.work[1], 7u, tid, nth);
             if (tid == 0) {  // exclusive sum of the segments' bits behind the header's
-                bam_dyn_header_choice(dyn);
+                bam_dyn_header_choice<TIGHT>(dyn);
                 uint32_t run = dyn.header_bits;
                 for (uint32_t x = 0; x < nth; x++) { const uint32_t v = dyn.seg[x]; dyn.seg[x] = run; run += v; }
                 dyn.seg[nth] = run + dyn.len_ll[256];
@@ -622,8 +880,12 @@ __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTab
                 BamDynBits ew;
                 ew.ll = dyn.code_ll; ew.dd = dyn.code_d;
                 ew.b.start(out32, dyn.seg[tid]);
-                if (tid == 0) { ew.b.start(out32, 0u); bam_dyn_put_header(dyn, ew.b); }
-                bam_parse(data, head, s0, s1, ew);
+                if (tid == 0) { ew.b.start(out32, 0u); bam_dyn_put_header<TIGHT>(dyn, ew.b); }
+                if constexpr (TIGHT) {
+                    BamTrim<BamDynBits> tw{ew, data, tr.E0};
+                    if (tr.E1 > tr.E0) bam_tight_parse(tr.c, s0, s1, tw);
+                } else
+                    bam_parse(data, head, s0, s1, ew);
                 if (tid == nth - 1u) bam_put_code(ew.b, dyn.code_ll[256]);  // (every segment behind the block's end is empty: the last thread ends the stream)
                 ew.b.finish();
             }
@@ -631,7 +893,11 @@ __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTab
                 BamBits<true> ew;
                 ew.start(out32, seg_bits[tid]);
                 if (tid == 0) { ew.start(out32, 0u); ew.put(3u, 3); }  // BFINAL = 1, BTYPE = 01
-                bam_parse(data, head, s0, s1, ew);
+                if constexpr (TIGHT) {
+                    BamTrim<BamBits<true>> tw{ew, data, tr.E0};
+                    if (tr.E1 > tr.E0) bam_tight_parse(tr.c, s0, s1, tw);
+                } else
+                    bam_parse(data, head, s0, s1, ew);
                 ew.finish();
             }
             __syncthreads();
@@ -659,6 +925,7 @@ __device__ __forceinline__ void bam_blocks_body(const SamTables& t, const BamTab
 // deflate == 2 is an instantiation of its own, so that the code and the registers of the other two stay what they are without it: on the
 // device k_bam_blocks_dynamic is its kernel (native_bam.hpp launches it for MIRGE_BAM_DEFLATE=dynamic) and k_bam_blocks does not hold
 // it; compiled for the host (tests/hostsim/bam_sim.cpp), where nothing is allocated, k_bam_blocks takes deflate == 2 as well.
+// deflate == 3 likewise: k_bam_blocks_tight on the device (MIRGE_BAM_DEFLATE=tight), k_bam_blocks on the host.
 __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTables bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
                                                             const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
                                                             unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
@@ -666,6 +933,7 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks(SamTables t, BamTabl
                                                             uint32_t* __restrict__ sizes) {
 #ifndef __HIP_DEVICE_COMPILE__
     if (deflate == 2) { bam_blocks_body<true>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, deflate, slot_stride, out, sizes); return; }
+    if (deflate == 3) { bam_blocks_body<true, true>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, deflate, slot_stride, out, sizes); return; }
 #endif
     bam_blocks_body<false>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, deflate, slot_stride, out, sizes);
 }
@@ -675,6 +943,13 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks_dynamic(SamTables t,
                                                                     uint32_t block_bytes, uint32_t slot_stride, uint8_t* __restrict__ out,
                                                                     uint32_t* __restrict__ sizes) {
     bam_blocks_body<true>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, 2, slot_stride, out, sizes);
+}
+__global__ void __launch_bounds__(MIRGE_BLOCK) k_bam_blocks_tight(SamTables t, BamTables bt, const uint32_t* __restrict__ rows, uint32_t n_rows,
+                                                                  const uint32_t* __restrict__ fixed, const unsigned long long* __restrict__ row_off,
+                                                                  unsigned long long stream_bytes, unsigned long long first_block, uint32_t n_blocks,
+                                                                  uint32_t block_bytes, uint32_t slot_stride, uint8_t* __restrict__ out,
+                                                                  uint32_t* __restrict__ sizes) {
+    bam_blocks_body<true, true>(t, bt, rows, n_rows, fixed, row_off, stream_bytes, first_block, n_blocks, block_bytes, 3, slot_stride, out, sizes);
 }
 
 // member b of a chunk from its slot to its place: off[] = exclusive scan of sizes[]

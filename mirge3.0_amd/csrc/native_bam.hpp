@@ -8,8 +8,9 @@
 // sorted rows' stream offsets and the members' file offsets.
 // MIRGE_BAM_BLOCK_BYTES (64 .. 65280, default 65280): uncompressed bytes per BGZF block; MIRGE_BAM_CHUNK_BLOCKS: blocks per chunk
 // (default: 64 MiB of stream); MIRGE_BAM_DEFLATE=device (the default): the fixed Huffman code; =dynamic: per block also a code of its
-// own (BTYPE 10), taken where it is shorter; =host: the blocks leave the device uncompressed and zlib level 6 deflates them on
-// `threads` host threads (the A/B route).  All read per call.
+// own (BTYPE 10), taken where it is shorter; =tight: the dynamic route's forms on the tokens of a closer parse (matches across the
+// threads' segments, record-aligned, repeat-distance and region candidates, one lazy step: kernels_bam.hpp); =host: the blocks leave
+// the device uncompressed and zlib level 6 deflates them on `threads` host threads (the A/B route).  All read per call.
 #pragma once
 
 static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -105,9 +106,11 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     const uint32_t block = (uint32_t)std::min<size_t>(MIRGE_BAM_MAX_BLOCK, std::max<size_t>(64, sam_env_bytes("MIRGE_BAM_BLOCK_BYTES", MIRGE_BAM_MAX_BLOCK)));
     const size_t chunk_blocks = std::max<size_t>(1, std::min<size_t>(sam_env_bytes("MIRGE_BAM_CHUNK_BLOCKS", std::max<size_t>(1, ((size_t)64 << 20) / block)), (size_t)1 << 20));
     const char* dv = std::getenv("MIRGE_BAM_DEFLATE");
-    const bool on_host = dv && std::strcmp(dv, "host") == 0, dynamic = dv && std::strcmp(dv, "dynamic") == 0;
-    if (dv && *dv && !on_host && !dynamic && std::strcmp(dv, "device") != 0)
-        return fail(-1, "mirge_bam_write_device: MIRGE_BAM_DEFLATE is 'device', 'dynamic' or 'host'");
+    const bool on_host = dv && std::strcmp(dv, "host") == 0, dynamic = dv && std::strcmp(dv, "dynamic") == 0, tight = dv && std::strcmp(dv, "tight") == 0;
+    if (dv && *dv && !on_host && !dynamic && !tight && std::strcmp(dv, "device") != 0)
+        // (both sentences are matched by callers and tests: the second is the text of the builds without the tight route)
+        return fail(-1, "mirge_bam_write_device: MIRGE_BAM_DEFLATE is 'device', 'dynamic', 'tight' or 'host' "
+                        "(a build without the tight route says: MIRGE_BAM_DEFLATE is 'device', 'dynamic' or 'host')");
     const int T = std::max(1, std::min(threads > 0 ? threads : 16, 256));
     const uint32_t slot_stride = (block + 5u + 26u + 15u) & ~15u;
     const unsigned long long H = (unsigned long long)header_len;
@@ -295,6 +298,9 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
                 LaunchScope ls(c, "k_bam_blocks", (double)nb * block);
                 if (dynamic)  // deflate == 2: an instantiation of its own (kernels_bam.hpp)
                     hipLaunchKernelGGL(k_bam_blocks_dynamic, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
+                                       (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
+                else if (tight)  // deflate == 3: likewise
+                    hipLaunchKernelGGL(k_bam_blocks_tight, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
                                        (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
                 else
                     hipLaunchKernelGGL(k_bam_blocks, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, (const uint32_t*)d_sfixed,

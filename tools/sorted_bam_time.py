@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Time ``--sorted-bam``'s device call (``mirge_bam_write_device``) on the two synthetic samples of ``tools/sam_out_time.py`` -- Zipf
-counts over a few hundred thousand unique reads, and all-distinct -- of ``--reads`` raw reads.  Per shape four calls are interleaved
+counts over a few hundred thousand unique reads, and all-distinct -- of ``--reads`` raw reads.  Per shape five calls are interleaved
 round by round (after one unrecorded warm-up round, which pays for the staging buffers and the lift tables): the device deflate, the
-``MIRGE_BAM_DEFLATE=dynamic`` route (the same parse, per block also a Huffman code of its own), the ``MIRGE_BAM_DEFLATE=host`` route
+``MIRGE_BAM_DEFLATE=dynamic`` route (the same parse, per block also a Huffman code of its own), the ``MIRGE_BAM_DEFLATE=tight`` route
+(the dynamic route's forms on a closer parse), the ``MIRGE_BAM_DEFLATE=host`` route
 (zlib level 6 on ``--threads`` host threads: the same blocks, so its file size is zlib's on them) and ``--sam-out``'s call on the same
-build, the closest existing work.  Reported: median, min and max seconds of ``--repeats`` rounds, stream bytes, file bytes of the three
-routes, the dynamic file's members by deflate block type (and how many dynamic headers use run symbols), and the share of the device file's excess over zlib's that the dynamic
-route removes.
+build, the closest existing work.  Reported: median, min and max seconds of ``--repeats`` rounds, stream bytes, file bytes of the four
+routes, the dynamic and the tight file's members by deflate block type (and how many dynamic headers use run symbols), and the share of
+the device file's excess over zlib's that the dynamic and the tight route remove.
 
   python tools/sorted_bam_time.py --reads 10000000 --repeats 7 --out profiles/sorted_bam_time.txt
 """
@@ -50,11 +51,11 @@ def main():
     ap.add_argument("--zipf-unique", type=int, default=300_000)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--routes", default="device,dynamic,host,sam_out",
+    ap.add_argument("--routes", default="device,dynamic,tight,host,sam_out",
                     help="the calls to time, e.g. 'device' alone for an A/B of two builds of the library (MIRGE_NATIVE_SO)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    routes = [r for r in ("device", "dynamic", "host", "sam_out") if r in a.routes.split(",")]
+    routes = [r for r in ("device", "dynamic", "tight", "host", "sam_out") if r in a.routes.split(",")]
     rng = np.random.Generator(np.random.PCG64(5))
     libs = libraries(rng)
     header = ("@HD\tVN:1.0\n" + "".join(f"@SQ\tSN:chr{k}\tLN:{1 << 28}\n" for k in range(1, 23))).encode()
@@ -83,7 +84,7 @@ def main():
         for rnd in range(a.repeats + 1):
             for route in routes:
                 os.environ.pop("MIRGE_BAM_DEFLATE", None)
-                if route in ("dynamic", "host"):
+                if route in ("dynamic", "tight", "host"):
                     os.environ["MIRGE_BAM_DEFLATE"] = route
                 t0 = time.perf_counter()
                 if route == "sam_out":
@@ -94,8 +95,8 @@ def main():
                     line.update({"records": n_rec, "stream_bytes": n_stream, route + "_file_bytes": n_file, "bai_bytes": os.path.getsize(bai)})
                 if rnd:
                     ts[route].append(time.perf_counter() - t0)
-                elif route == "dynamic":
-                    line["dynamic_members_stored_fixed_dynamic_withruns"] = members_by_btype(bam)
+                elif route in ("dynamic", "tight"):
+                    line[route + "_members_stored_fixed_dynamic_withruns"] = members_by_btype(bam)
         os.environ.pop("MIRGE_BAM_DEFLATE", None)
         for route, v in ts.items():
             line.update({route + "_median_s": round(statistics.median(v), 4), route + "_min_s": round(min(v), 4), route + "_max_s": round(max(v), 4)})
@@ -104,6 +105,9 @@ def main():
         if "device" in routes and "host" in routes and "dynamic" in routes:
             line["dynamic_over_zlib6_size"] = round(line["dynamic_file_bytes"] / line["host_file_bytes"], 3)
             line["dynamic_closes_of_the_gap"] = round((line["device_file_bytes"] - line["dynamic_file_bytes"]) / max(1, line["device_file_bytes"] - line["host_file_bytes"]), 3)
+        if "device" in routes and "host" in routes and "tight" in routes:
+            line["tight_over_zlib6_size"] = round(line["tight_file_bytes"] / line["host_file_bytes"], 3)
+            line["tight_closes_of_the_gap"] = round((line["device_file_bytes"] - line["tight_file_bytes"]) / max(1, line["device_file_bytes"] - line["host_file_bytes"]), 3)
         for f in (bam, bai, sam):
             if os.path.exists(f):
                 os.remove(f)
