@@ -36,6 +36,9 @@
 #ifndef MIRGE_LDS_PLAN
 #define MIRGE_LDS_PLAN 1
 #endif
+#ifndef MIRGE_NP_EARLY_OUT
+#define MIRGE_NP_EARLY_OUT 1  // align_hybrid: a wave none of whose reads has a probe (all longer than the library's longest window) leaves at once
+#endif
 
 // pointers that came out of memory or a v_readlane have lost their address space; these casts keep
 // the loads global_load_* (not flat_load_*, which also ties up lgkmcnt)
@@ -359,6 +362,11 @@ __device__ __forceinline__ void align_hybrid(const MirgeLibView& lib, const Mirg
     return;
 #endif
     const int np = active ? (int)(LDS ? ps.l->np[r.len] : ps.g->np[r.len]) : 0;
+#if MIRGE_NP_EARLY_OUT
+    // no lane holds a probe -- reads trimmed to more than the library's longest window (the plan gives them np = 0), lanes without a
+    // read: the npmax trips below would look nothing up and verify nothing.  Wave-uniform: every lane leaves or none does.
+    if (!__any(np > 0)) return;
+#endif
     // wave-uniform bound on the probe count: (mm+1) plain segments or (mm+1)^2 recursive probes
     const int npmax = (pol.mm >= 1 && pol.mm <= 2) ? (pol.mm + 1) * (pol.mm + 1) : pol.mm + 1;
     // (round 6) pol.reserved > 0: a read that meets a bucket of more windows than that is not aligned by this wave -- one such list
@@ -1010,7 +1018,8 @@ k_cascade_bulk(const BulkWalks* __restrict__ walks, GroupView<W> g, uint32_t* __
 // 45 -> 49-53 us.  7.6 M wave-level VALU instructions per launch, most of them the 16-way pointer select, 73 MB moved.)
 // Nothing in a step's tail waits for the bulk group's launch of this kernel: the count join resolves the positions of the miRNA
 // reads -- the only references its tables need -- itself, with resolve_entry on the two miRNA libraries' rows (kernels_join.hpp),
-// and queues this kernel behind the event the host waits for; every other consumer finds it launched first (join_pending_now).
+// and leaves this kernel pending; whoever reads res_ref / res_off finds it launched first (join_pending_now), and a result that is
+// closed unread never runs it (mirge_result_destroy).
 __global__ void k_resolve(ResolveTable tb, const int8_t* __restrict__ res_pass, const uint32_t* __restrict__ res_pos,
                           uint32_t n, int32_t* __restrict__ res_ref, int32_t* __restrict__ res_off,
                           const uint32_t* __restrict__ n_dev) {

@@ -433,9 +433,11 @@ struct MirgePlanTable {
     uint8_t np[MIRGE_MAX_READ_LEN + 1];
     MirgeProbe pr[MIRGE_MAX_READ_LEN + 1][MIRGE_MAX_PROBES];
 };
-static inline void mirge_plan_table_fill(const MirgePolicy& p, int K, uint64_t npos, MirgePlanTable& t) {
+// max_window: the longest window the library holds (MirgeHostLib::max_run).  A read trimmed to more has no valid window
+// anywhere, whatever its probes find: it gets no probe (np = 0), so the kernels spend no lookup on it.  The default bounds nothing.
+static inline void mirge_plan_table_fill(const MirgePolicy& p, int K, uint64_t npos, MirgePlanTable& t, int max_window = MIRGE_MAX_READ_LEN) {
     for (int L = 0; L <= MIRGE_MAX_READ_LEN; L++) {
-        const bool ok = L >= 1 && L > p.mm;
+        const bool ok = L >= 1 && L > p.mm && L <= max_window;
         const int n = ok ? mirge_probe_count(p, L, K, npos) : 0;
         t.np[L] = (uint8_t)n;
         for (int q = 0; q < MIRGE_MAX_PROBES; q++) {

@@ -20,6 +20,9 @@ struct MirgeHostLib {
     std::vector<uint64_t> T;    // (total+31)/32 + 8 words, zero padded
     std::vector<uint64_t> inv;  // (total+63)/64 + 4 words, padding = ones
     std::vector<uint32_t> ref_start;  // n_refs + 1
+    // the longest run of valid bases (mirge_longest_valid_run): no window longer than this lies inside one reference, free of N
+    // -- a read trimmed to more can have no hit, and the probe plans give it no probe (mirge_plan_table_fill)
+    uint32_t max_run = 0;
 };
 
 static inline int mirge_base_code(char ch) {
@@ -31,6 +34,24 @@ static inline int mirge_base_code(char ch) {
         case 'U': return 3;
         default: return -1;  // N and every other IUPAC code: no window over it is a valid hit
     }
+}
+
+// longest run of zero bits among the first `total` of an invalid bitmap: the longest window a library can hold.  Whole words
+// of valid bases (the inside of a long reference) go 64 at a time.
+static inline uint32_t mirge_longest_valid_run(const uint64_t* inv, uint64_t total) {
+    uint64_t best = 0, run = 0;
+    for (uint64_t g = 0; g < total;) {
+        const uint64_t w = inv[g >> 6];
+        if ((g & 63) == 0 && g + 64 <= total && (w == 0ull || w == ~0ull)) {
+            run = w ? 0 : run + 64;
+            g += 64;
+        } else {
+            run = ((w >> (g & 63)) & 1ull) ? 0 : run + 1;
+            g++;
+        }
+        if (run > best) best = run;
+    }
+    return (uint32_t)std::min<uint64_t>(best, 0xFFFFFFFFull);
 }
 
 static inline int mirge_hostlib_build(MirgeHostLib& L, const char* seq, const int64_t* off, int64_t n_refs,
@@ -94,6 +115,7 @@ static inline int mirge_hostlib_build(MirgeHostLib& L, const char* seq, const in
     int k = 8;
     while (k < MIRGE_KMAX && (1ull << (2 * k)) < (uint64_t)MIRGE_K_OVERSAMPLE * std::max<uint64_t>(L.valid_positions, 1)) k++;
     L.kmax = k;
+    L.max_run = mirge_longest_valid_run(L.inv.data(), total);
     return 0;
 }
 

@@ -27,7 +27,18 @@ struct mirge_result {
 
 extern "C" void mirge_result_destroy(mirge_result* r) {
     if (!r) return;
-    (void)join_pending_now(r->ctx);  // the side streams may still be writing what goes back to the pool here
+    mirge_ctx* const c = r->ctx;
+    // a k_resolve still pending for this result: nobody has read its references and nobody will -- dropped, not launched
+    // (MIRGE_LAZY_RESOLVE=0: launched, as every other entry point does); the clocks of a profiled launch go to the host all the same
+    mirge_ctx::PendingResolve& pr = c->resolve_pending;
+    bool mine = false;
+    for (auto& g : r->g) mine |= pr.set && g.ref && g.ref == pr.ref;
+    if (mine && lazy_resolve_on()) {
+        pr.set = false;
+        (void)wg_copy_pending(c);
+        (void)join_side_now(c);
+    } else
+    (void)join_pending_now(c);  // the side streams may still be writing what goes back to the pool here
     for (auto& g : r->g) {
         r->ctx->release(g.pass); r->ctx->release(g.pos); r->ctx->release(g.mm);
         r->ctx->release(g.ref); r->ctx->release(g.off);
@@ -61,6 +72,7 @@ static int prepare_tables(mirge_lib* lib, const mirge_policy& pol, const int32_t
     std::memcpy(&p, &pol, sizeof(p));
     std::vector<ShapeJob> wanted;
     std::vector<bool> seen(MIRGE_SHAPE_SLOTS, false);
+    const int max_window = lib->plan_window;  // (a length beyond it has no probes in the plan: no table for its shapes)
     // L = MIRGE_MAX_READ_LEN + 1 stands for the long class (k_cascade_long): a read of 256 nt or more is probed with the plan of
     // its first 31 bases -- of its whole head when a T run is stripped down to less -- so lengths 31 + trims (any below with -ttail)
     for (int L = 1; L <= MIRGE_MAX_READ_LEN + 1; L++) {
@@ -75,7 +87,7 @@ static int prepare_tables(mirge_lib* lib, const mirge_policy& pol, const int32_t
         if (p.ttail) { lo = 1; hi = (lng ? 31 + p.trim5 + p.trim3 : L - 3); }  // any head length once the T run is gone
         for (int l0 = lo; l0 <= hi; l0++) {
             const int l = l0 - p.trim5 - p.trim3;
-            if (l < 1 || l <= p.mm) continue;
+            if (l < 1 || l <= p.mm || l > max_window) continue;
             const int np = mirge_probe_count(p, l, lib->kmax, lib->h.total);
             for (int q = 0; q < np; q++) {
                 MirgeProbe pr;
@@ -120,7 +132,7 @@ static int cascade_group(mirge_ctx* c, const ReadGroup& rg, ResGroup& out, const
                          const mirge_policy* pol, const ResolveTable& rt, const char* gtag,
                          const uint32_t* n_dev = nullptr, uint32_t n_cap = 0, const BulkWalks* dwalks = nullptr, bool defer_resolve = false) {
     // defer_resolve (the bulk group, on the main stream): k_resolve is not launched here but left with the ctx (PendingResolve) for the
-    // count join to queue BEHIND its tables, or for whichever entry point comes first (join_pending_now).  Only with libraries of
+    // first entry point that reads the references or queues new work (join_pending_now), or for nobody.  Only with libraries of
     // this context's own (casc_libs_own): mirge_lib_destroy launches the pending kernel of the library's context and no other's
     defer_resolve = defer_resolve && c->casc_libs_own;
     // n_dev != nullptr: the group's read count is not on the host yet (see k_pass); everything is sized for
@@ -410,7 +422,7 @@ static int cascade_prepare(mirge_ctx* c, const mirge_lib* const* libs, const mir
             if (e.uid == st.lib->uid && std::memcmp(&e.pol, &mp, sizeof(mp)) == 0) { dp = e.dplan; break; }
         if (!dp) {
             auto h = std::make_unique<MirgePlanTable>();
-            mirge_plan_table_fill(mp, st.lib->kmax, st.lib->h.total, *h);
+            mirge_plan_table_fill(mp, st.lib->kmax, st.lib->h.total, *h, st.lib->plan_window);
             MirgePlanTable* d = nullptr;
             HIPOK(hipMalloc((void**)&d, sizeof(MirgePlanTable)));
             HIPOK(hipMemcpy(d, h.get(), sizeof(MirgePlanTable), hipMemcpyHostToDevice));
@@ -770,6 +782,7 @@ extern "C" int mirge_collapse_cascade(mirge_ctx* c, const mirge_reads* raw, cons
         for (int k = 0; k < MIRGE_N_XAUX; k++) (void)hipStreamSynchronize(c->xaux[k]);
         c->overlap_mode = false;
         c->resolve_pending.set = false;  // (its buffers go back to the pool below)
+        c->resolve_pending.wg_src = nullptr;
         c->join_pending = false;  // (everything has drained: nothing is left to join)
         c->xaux_used = false;
         c->x0_gathered = c->aux_drained = false;

@@ -121,17 +121,21 @@ struct mirge_ctx {
     const BulkWalks* casc_dwalks[2] = {nullptr, nullptr};  // [0] the one-word group's list (exact steps ride along), [1] wider groups
     size_t prof_used = 0;
     std::vector<ProfUnits> prof_pending;
-    // The bulk group's k_resolve, not launched yet (cascade_group): the count join finds a miRNA read's reference from its position and
-    // needs none of what k_resolve writes, so the launch waits until the join has queued its kernels and the event the host waits
-    // for -- or until any other entry point touches the ctx (join_pending_now, mirge_lib_destroy): resolution at the first consumer.
-    // The main stream's order then puts res_ref / res_off in front of whatever reads them, as before.  `rt` is a copy: the ctx's table may be reconfigured before the launch.
+    // The bulk group's k_resolve, not launched yet (cascade_group): resolution at the first use.  The count join finds a miRNA read's
+    // reference from its position and needs none of what k_resolve writes, so it leaves the kernel pending; a caller that takes the
+    // count tables and closes the result never pays for it (mirge_result_destroy drops it).  Whoever reads res_ref / res_off, frees
+    // what the kernel reads (mirge_lib_destroy) or queues new work while the result lives launches it first (join_pending_now,
+    // resolve_pending_now): the main stream's order then puts res_ref / res_off in front of whatever reads them, as before.
+    // MIRGE_LAZY_RESOLVE=0: launched by the count join behind the event the host waits for, and by mirge_result_destroy (A/B, tests).
+    // `rt` is a copy: the ctx's table may be reconfigured before the launch.
     struct PendingResolve {
         bool set = false;
         ResolveTable rt;
         const int8_t* pass = nullptr; const uint32_t* pos = nullptr; uint32_t n = 0;
         int32_t* ref = nullptr; int32_t* off = nullptr; const uint32_t* n_dev = nullptr;
         char name[32] = {0};
-        // the workgroups' clocks of a profiled k_cascade_bulk launch go to the host behind k_resolve instead of in front of it
+        // the workgroups' clocks of a profiled k_cascade_bulk launch go to the host behind the count join's event, or with k_resolve
+        // (wg_copy_pending), instead of between the bulk kernel and the join
         const uint32_t* wg_src = nullptr; uint32_t wg_grid = 0;
     } resolve_pending;
 
@@ -281,6 +285,22 @@ static int stream_join(mirge_ctx* c) {
     return 0;
 }
 static inline int grid_for(const mirge_ctx* c, size_t n, int per_block = MIRGE_BLOCK);
+// (read at every call, twice a step: a test compares both settings in one process)
+static bool lazy_resolve_on() {
+    const char* const e = std::getenv("MIRGE_LAZY_RESOLVE");
+    return !(e && std::atoi(e) == 0);
+}
+// the clocks of the profiled bulk launch a pending k_resolve belongs to, to the host now (main stream): they wait for no kernel
+// that may never run.  mirge_cascade_wg_times synchronises before it reads them.
+static int wg_copy_pending(mirge_ctx* c) {
+    mirge_ctx::PendingResolve& r = c->resolve_pending;
+    if (!r.wg_src) return 0;
+    const uint32_t* const src = r.wg_src;
+    r.wg_src = nullptr;
+    HIPOK(hipMemcpyAsync(c->wg_pinned, src, 2 * (size_t)r.wg_grid * 4, hipMemcpyDeviceToHost, c->stream));
+    c->wg_grid = r.wg_grid;
+    return 0;
+}
 // the bulk group's deferred k_resolve (mirge_ctx::PendingResolve), on the main stream, now
 static int resolve_pending_now(mirge_ctx* c) {
     mirge_ctx::PendingResolve& r = c->resolve_pending;
@@ -293,20 +313,21 @@ static int resolve_pending_now(mirge_ctx* c) {
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(c, r.n)), dim3(MIRGE_BLOCK), 0, c->stream, r.rt, r.pass, r.pos, r.n, r.ref, r.off, r.n_dev);
     }
     c->cur = cur;
-    if (r.wg_src) {
-        HIPOK(hipMemcpyAsync(c->wg_pinned, r.wg_src, 2 * (size_t)r.wg_grid * 4, hipMemcpyDeviceToHost, c->stream));
-        c->wg_grid = r.wg_grid;
-    }
-    return 0;
+    return wg_copy_pending(c);
 }
 // mirge_cascade_run / mirge_collapse_cascade leave their side streams unjoined; every entry point that enqueues on the main
 // stream, hands buffers back to the pool or synchronises joins them first.  mirge_count_join uses the slack: the bulk
 // group's part of the join runs before the wait, beside the small groups' cascades.
-static int join_pending_now(mirge_ctx* c) {
-    CHECK(resolve_pending_now(c));  // (in front of the wait: it runs beside what is left of the side streams' work)
+static int join_side_now(mirge_ctx* c) {
     if (!c->join_pending) return 0;
     c->join_pending = false;
     return stream_join(c);
+}
+// ... and launches a pending k_resolve: the result it belongs to is alive (mirge_result_destroy drops it otherwise), and what this
+// entry point reads or queues may depend on res_ref / res_off
+static int join_pending_now(mirge_ctx* c) {
+    CHECK(resolve_pending_now(c));  // (in front of the wait: it runs beside what is left of the side streams' work)
+    return join_side_now(c);
 }
 static int largest_group(const struct mirge_reads* R);
 

@@ -42,9 +42,10 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
     // behind the wait for them.  Otherwise: everything in one launch with atomics (k_join_multi).
     // Neither needs the bulk group's k_resolve: a miRNA read's reference comes from its position (JoinGroups::from_pos).  The
     // main stream reads k_cascade_bulk, k_join_rows (bulk), the wait for the side streams, k_join_rows (small groups),
-    // k_join_reduce, the event the host waits for, k_resolve (bulk): its 40 us for 4.2 M reads run while the host takes the
-    // tables.  (In front of the wait they outlasted it: the small groups are ready ~10 us behind the bulk rows,
-    // profiles/tail_join_from_positions.md.)  Stream order still puts res_ref / res_off in front of every later reader.
+    // k_join_reduce, the event the host waits for.  k_resolve stays pending (mirge_ctx::PendingResolve): the first reader of
+    // res_ref / res_off launches it, in front of itself in stream order, and a result closed unread never runs it
+    // (profiles/lazy_resolve_reflen.md).  MIRGE_LAZY_RESOLVE=0: queued behind the event, where its 40 us for 4.2 M reads ran
+    // while the host took the tables and headed the next step's main stream (profiles/tail_join_from_positions.md).
     static const bool rows_off = std::getenv("MIRGE_JOIN_ROWS") && std::atoi(std::getenv("MIRGE_JOIN_ROWS")) == 0;  // A/B
     // `join_pending` stays set until stream_join has actually been issued: an early return below (argument check, out of
     // memory) then leaves the side streams to the next entry point's join_pending_now instead of unjoined for good
@@ -62,6 +63,14 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
     // positions and granule tables are this context's own cascade's, and no library has been destroyed since it ran; any other result
     // is joined from the references it holds (resolved by then: k_resolve goes first)
     const bool from_pos = res->ctx == c && res->lib_epoch == g_lib_epoch.load();
+    // joined from the references the result holds: a k_resolve still pending for them goes first -- this context's own in the main
+    // stream's order; another context's (a result joined here that was made there) is launched there and waited for
+    auto resolve_first = [&]() -> int {
+        if (res->ctx == c) return resolve_pending_now(c);
+        CHECK(join_pending_now(res->ctx));
+        HIPOK(hipStreamSynchronize(res->ctx->stream));
+        return 0;
+    };
     auto group_list = [&](bool bulk, JoinGroups& gs) -> uint64_t {
         std::memset(&gs, 0, sizeof(gs));
         gs.from_pos = from_pos ? 1 : 0;
@@ -90,7 +99,7 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         const uint32_t rows_b = n_bulk ? (uint32_t)std::min<uint64_t>((uint64_t)c->n_cu, (n_bulk + 4095) / 4096) : 0u;
         const uint32_t rows_s = n_small ? (uint32_t)std::min<uint64_t>((uint64_t)c->n_cu, (n_small + 4095) / 4096) : 0u;
         CHECK(dalloc(c, &partial, (size_t)(rows_b + rows_s) * words));
-        if (!from_pos) CHECK(resolve_pending_now(c));
+        if (!from_pos) CHECK(resolve_first());
         if (rows_b) {
             LaunchScope ls(c, "k_join", (double)n_bulk);
             hipLaunchKernelGGL(k_join_rows, dim3(rows_b), dim3(MIRGE_JOIN_ROWS_THREADS), words * 8, c->stream, gb, S, P, exact_pass, iso_pass,
@@ -107,7 +116,7 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         hipLaunchKernelGGL(k_join_reduce, dim3((unsigned)((words + 63) / 64)), dim3(1024), 0, c->stream, partial, rows_b + rows_s, (uint32_t)words, d,
                            c->join_pinned);
     } else {
-        if (!from_pos) CHECK(resolve_pending_now(c));
+        if (!from_pos) CHECK(resolve_first());
         CHECK(join_side_streams());
         for (JoinGroups* gs : {&gb, &gsm}) {
             const uint64_t total = gs == &gb ? n_bulk : n_small;
@@ -123,8 +132,10 @@ extern "C" int mirge_count_join(mirge_ctx* c, const mirge_reads* U, const mirge_
         HIPOK(hipMemcpyAsync(c->join_pinned, d, words * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPOK(hipEventRecord(c->ev_meta, c->stream));
-    // the bulk group's k_resolve: behind the event the host waits for, in front of whatever the main stream is given next
-    CHECK(resolve_pending_now(c));
+    // the clocks of a profiled bulk launch: behind the event the host waits for, on their own; the bulk group's k_resolve only with
+    // MIRGE_LAZY_RESOLVE=0 (otherwise it stays pending for the first reader of the references)
+    if (lazy_resolve_on()) CHECK(wg_copy_pending(c));
+    else CHECK(resolve_pending_now(c));
     // cleared for the next call now, behind the copy: the host waits for the copy only
     if (!by_rows) cleared = hipMemsetAsync(d, 0, c->join_dev_words * 8, c->stream) == hipSuccess;
     hc.lap("enqueue");

@@ -23,6 +23,10 @@ struct mirge_lib {
     std::mutex mu;
     int64_t n_refs = 0;
     int kmax = 8;
+    // The longest window the probe plans of this library admit (mirge_plan_table_fill): its longest run of valid bases -- a read trimmed
+    // to more gets no probe and no shape table.  MIRGE_PLAN_REFLEN=0: no bound, every length probed (A/B, tests).  Fixed when the
+    // library is made, so that the plan kept for it and every later prepare_tables agree on which lengths are probed.
+    int plan_window = MIRGE_MAX_READ_LEN;
     uint32_t max_bucket = 0;  // windows in the fullest bucket of any probe table built so far (k_table_heavy_list): > casc_big_t = reads may be deferred
     // whole-read tables of the exact passes (kernels_cascade.hpp, ExactStep), by the set of lengths they hold (bit l of the key)
     struct ExactTab { uint64_t* slots = nullptr; uint32_t mask = 0; uint64_t windows = 0; };
@@ -67,6 +71,7 @@ extern "C" int mirge_lib_create_packed(mirge_ctx* c, const uint64_t* T, int64_t 
     L->h.T.assign(T, T + n_T);
     L->h.inv.assign(inv, inv + n_inv);
     L->h.ref_start.assign(ref_start, ref_start + n_refs + 1);
+    L->h.max_run = mirge_longest_valid_run(L->h.inv.data(), total);
     return lib_upload(c, L, n_refs, out);
 }
 // sizes[4] = {words of T, words of inv, total, valid positions}; then the arrays themselves (caller-allocated)
@@ -87,6 +92,10 @@ extern "C" int mirge_lib_packed_copy(const mirge_lib* L, uint64_t* T, uint64_t* 
 static int lib_upload(mirge_ctx* c, std::unique_ptr<mirge_lib>& L, int64_t n_refs, mirge_lib** out) {
     L->n_refs = n_refs;
     L->kmax = L->h.kmax;
+    {
+        const char* const e = std::getenv("MIRGE_PLAN_REFLEN");
+        if (!(e && std::atoi(e) == 0)) L->plan_window = (int)std::min<uint32_t>(L->h.max_run, MIRGE_MAX_READ_LEN);
+    }
     L->htables.assign(MIRGE_SHAPE_SLOTS, MirgeKTable{nullptr, nullptr, nullptr});
     const size_t nT = L->h.T.size() * 8, nI = L->h.inv.size() * 8, nR = ((size_t)n_refs + 1) * 4;
     HIPOK(hipMalloc((void**)&L->dT, nT));

@@ -38,8 +38,9 @@ for r in range(rounds):
                               "--two-in-flight", "0", "--cli-path", "0", "--read-sets", "0"] + extra, env=env, capture_output=True, text=True)
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not lines:
-            print(name, "FAILED", out.stderr[-400:], flush=True)
-            continue
+            # a run that died may have left the GPU in a bad state: nothing more is started on it
+            print(name, "FAILED", f"(exit status {out.returncode})", out.stderr[-400:], flush=True)
+            raise SystemExit(1)
         d = json.loads(lines[-1])
         res[name].append(d["ms_per_step"])
         ks = {k: round(d["kernels"][k]["avg_ms"], 4) for k in KEYS if k in d.get("kernels", {})}
