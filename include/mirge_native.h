@@ -319,7 +319,11 @@ int mirge_annotation_csv_device_at(mirge_ctx* ctx, const mirge_reads* uniq, cons
  * out: fam_tables[5][n_fam][S] = n_seqs, seq_true, count_true, canon, kept_exact;
  *      census[n_fam][32][16][3][S] (position, target base * 4 + read base, variant raw / accepted / accepted+retained),
  *      read base != target base and position < len - 5 only;  A=0 C=1 G=2 T=3;
- *      diag_out/state_out[n reads] (may be NULL): diagonal of the alignment; 1 accepted, 0 rejected, -1 not a member. */
+ *      diag_out/state_out[n reads] (may be NULL): diagonal of the alignment; 1 accepted, 0 rejected, -1 not a member.
+ * Members of up to 64 nt are tallied (the isomiR policy annotates reads of up to 3 nt more than their miRNA: 35 nt for a
+ * canonical sequence of 32).  Errors: -6 a canonical sequence of more than 32 nt, or a member of more than 64 nt (only a
+ * policy that trims more can annotate one; nothing is left out of the tables in silence); -7 a canonical sequence with a
+ * character other than A/C/G/T/U. */
 #define MIRGE_TALLY_POSITIONS 32
 int mirge_variant_tally(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, int32_t exact_pass,
                         int32_t iso_pass, const int32_t* fam_of_ref, int64_t n_mirna, const char* target_ascii,

@@ -774,7 +774,9 @@ def variant_tally(ctx: Context, uniq: DeviceReads, res: CascadeResult, exact_pas
                   fam_of_ref: np.ndarray, targets: FlatSeqs, retained: Optional[np.ndarray], freq: np.ndarray,
                   per_read: bool = True):
     """``mirge_variant_tally`` (config 5 / rows a16, N1) -> dict: n_seqs, seq_true, count_true, canon, kept_exact
-    [n_fam, S]; census [n_fam, 32, 4, 4, 3, S]; diag, state [n reads] (handle order) when ``per_read``."""
+    [n_fam, S]; census [n_fam, 32, 4, 4, 3, S]; diag, state [n reads] (handle order) when ``per_read``.
+    Canonical sequences of up to 32 nt (A/C/G/T/U), member reads of up to 64 nt: a longer canonical sequence, one with another
+    character, or a read of more than 64 nt that is a member of a family's list raises ``RuntimeError`` -- nothing is dropped."""
     n_fam, S, n = len(targets), uniq.n_samples, len(uniq)
     fam_of_ref = np.ascontiguousarray(fam_of_ref, dtype=np.int32)
     tdata = np.ascontiguousarray(targets.data, dtype=np.uint8)

@@ -253,14 +253,24 @@ extern "C" int mirge_variant_tally(mirge_ctx* c, const mirge_reads* U, const mir
     if (n_mirna) HIPOK(hipMemcpyAsync(dfam, fam_of_ref, (size_t)n_mirna * 4, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemcpyAsync(dfreq, freq, (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
     if (retained && U->n) HIPOK(hipMemcpyAsync(dret, retained, (size_t)U->n, hipMemcpyHostToDevice, c->stream));
-    HIPOK(hipMemsetAsync(dstate, 0xFF, n, c->stream));  // reads of the wide groups are never members
+    HIPOK(hipMemsetAsync(dstate, 0xFF, n, c->stream));  // -1: not a member
     HIPOK(hipMemsetAsync(ddiag, 0, n, c->stream));
     TallyOut o;
     o.n_seqs = d; o.seq_true = d + n_fs; o.count_true = d + 2 * n_fs; o.canon = d + 3 * n_fs; o.kept_exact = d + 4 * n_fs;
     o.census = d + 5 * n_fs; o.diag = ddiag; o.state = dstate;
     std::vector<uint32_t*> lists;  // member lists of the groups, released behind the synchronisation below
+    // The isomiR policy annotates reads of up to 3 nt more than their miRNA, and a canonical sequence has up to 32: members sit
+    // in the one- and the two-word groups (<= 31 and 32..64 nt), which k_tally counts.  The wider groups are asked the same
+    // member question and must answer "none" (a policy that trims more could put a member there): their counts come back
+    // with the tables and a member among them fails the call -- no read is left out of the tables without a word.
+    std::vector<uint32_t> wide_counts;
+    std::vector<std::pair<size_t, int>> wide_at;  // (first count in wide_counts, group)
+    for (int gi = 0; gi < MIRGE_NGROUPS; gi++)
+        if (res->g[gi].n && kGroupW[gi] != 1 && kGroupW[gi] != 2) {
+            wide_at.push_back({wide_counts.size(), gi});
+            wide_counts.resize(wide_counts.size() + (size_t)grid_for(c, res->g[gi].n), 0u);
+        }
     for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
-        if (kGroupW[gi] != 1) continue;  // a read annotated to a miRNA is at most 3 nt longer than it: the <= 31-nt groups
         const ResGroup& g = res->g[gi];
         const ReadGroup& rg = U->g[gi];
         if (!g.n) continue;
@@ -271,17 +281,27 @@ extern "C" int mirge_variant_tally(mirge_ctx* c, const mirge_reads* U, const mir
         uint32_t* dlist = nullptr;
         CHECK(dalloc(c, &dlist, (size_t)tgrid * chunk + tgrid));
         uint32_t* dnlist = dlist + (size_t)tgrid * chunk;
+        lists.push_back(dlist);
         {
             LaunchScope ls(c, "k_member_list", g.n);
             const TallyMember pred{g.pass, g.ref, rg.counts, S, exact_pass, iso_pass, dfam, dfreq};
             hipLaunchKernelGGL((k_member_list<TallyMember, MIRGE_BLOCK>), dim3(tgrid), dim3(MIRGE_BLOCK), 0, c->stream, (uint32_t)g.n, chunk,
                                pred, dlist, dnlist);
         }
+        if (kGroupW[gi] != 1 && kGroupW[gi] != 2) {
+            for (auto& w : wide_at)
+                if (w.second == gi) HIPOK(hipMemcpyAsync(wide_counts.data() + w.first, dnlist, (size_t)tgrid * 4, hipMemcpyDeviceToHost, c->stream));
+            continue;
+        }
         LaunchScope ls(c, "k_tally", g.n);
-        hipLaunchKernelGGL(k_tally, dim3(tgrid), dim3(MIRGE_BLOCK), 0, c->stream, view_of<1>(rg), rg.base,
-                           (const uint32_t*)rg.orig, g.pass, g.ref, rg.counts, S, exact_pass, iso_pass, dfam, dtb, dtl,
-                           (const uint8_t*)dret, dfreq, o, (const uint32_t*)dlist, (const uint32_t*)dnlist, chunk);
-        lists.push_back(dlist);
+        if (kGroupW[gi] == 1)
+            hipLaunchKernelGGL(k_tally<1>, dim3(tgrid), dim3(MIRGE_BLOCK), 0, c->stream, view_of<1>(rg), rg.base,
+                               (const uint32_t*)rg.orig, g.pass, g.ref, rg.counts, S, exact_pass, iso_pass, dfam, dtb, dtl,
+                               (const uint8_t*)dret, dfreq, o, (const uint32_t*)dlist, (const uint32_t*)dnlist, chunk);
+        else
+            hipLaunchKernelGGL(k_tally<2>, dim3(tgrid), dim3(MIRGE_BLOCK), 0, c->stream, view_of<2>(rg), rg.base,
+                               (const uint32_t*)rg.orig, g.pass, g.ref, rg.counts, S, exact_pass, iso_pass, dfam, dtb, dtl,
+                               (const uint8_t*)dret, dfreq, o, (const uint32_t*)dlist, (const uint32_t*)dnlist, chunk);
     }
     // straight into the caller's arrays (the census alone is 12 KiB per family and sample: no staging copy of it)
     for (int t = 0; t < 5 && n_fam; t++)  // the device block is sized for max(n_fam, 1)
@@ -294,5 +314,10 @@ extern "C" int mirge_variant_tally(mirge_ctx* c, const mirge_reads* U, const mir
     c->release(d); c->release(dtb); c->release(dtl); c->release(dfam); c->release(dret); c->release(dfreq);
     c->release(ddiag); c->release(dstate);
     for (uint32_t* l : lists) c->release(l);
+    unsigned long long wide_members = 0;
+    for (uint32_t m : wide_counts) wide_members += m;
+    if (wide_members)
+        return fail(-6, "mirge_variant_tally: " + std::to_string(wide_members) + " read(s) of more than 64 nt are members of a miRNA family's list; "
+                        "the tally aligns reads of up to 64 nt");
     return 0;
 }

@@ -35,6 +35,40 @@ def test_a2i_restatement_equals_the_reference_functions(case_name):
     assert n_true > 50 and n_pos >= 5
 
 
+def test_a2i_restatement_equals_the_reference_functions_at_long_lengths():
+    """Canonical sequences of 26..32 nt and reads of up to 35 nt (tests/golden/a2i_long_direct.json, made by
+    make_golden_a2i_long.py from the reference's own functions): the lengths at which the tally kernel's packed words
+    are full, which the two cases above (targets of 18..25 nt) do not reach."""
+    d = json.load(open(os.path.join(GOLDEN, "a2i_long_direct.json")))
+    assert len(d["groups"]) >= 50
+    n_long = {True: 0, False: 0}
+    positions = []
+    for g in d["groups"]:
+        o = oracle.a2i_group(g["target"], g["reads"], g["counts"], set(g["retained"]))
+        assert o["frame"] == g["aligned"], (g["target"], o["frame"], g["aligned"])
+        assert o["states"] == g["states"]
+        a = g["a2i"]
+        assert o["kept"] == a["kept"] and o["positions"] == a["positions"]
+        assert {str(k): v for k, v in o["count"].items()} == a["count"]
+        assert o["countSumTrue"] == a["countSumTrue"] and o["seqCountTrue"] == a["seqCountTrue"]
+        assert o["canonicalSeqCount"] == a["canonicalSeqCount"]
+        for k, v in a["ratio"].items():
+            assert o["ratio"][int(k)] == v
+        for k, v in a["pvalue"].items():
+            assert o["pvalue"][int(k)] == pytest.approx(v, rel=1e-12, abs=1e-300)
+        assert o["census"] == g["mismatch_census"]
+        for r, s in zip(g["reads"], g["states"]):
+            assert len(g["target"]) - 4 <= len(r) <= len(g["target"]) + 3
+            if len(r) >= 32:
+                n_long[bool(s)] += 1
+        positions += a["positions"]
+    # what the file is for
+    per_length = {L: sum(len(g["target"]) == L for g in d["groups"]) for L in range(26, 33)}
+    assert min(per_length.values()) >= 6 and sum(per_length.values()) == len(d["groups"]), per_length
+    assert n_long[True] + n_long[False] >= 40 and n_long[True] and n_long[False], n_long
+    assert max(positions) - 1 >= 22  # an A -> G at target base 22 or beyond (positions are 1-based)
+
+
 def _case4_gff_tables(case_name="case4_gff_a2i"):
     """name -> canonical sequence / precursor name -> precursor sequence, read the way summarize() reads them
     (summary.py:801-837): the mature FASTA, the GFF3 annotation, and `bowtie-inspect` of the hairpin index -- whose
