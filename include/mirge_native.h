@@ -155,7 +155,7 @@ int mirge_reads_parse_trim(mirge_ctx* ctx, const char* text, int64_t nbytes, int
  *   qiagen       --qiagenumi (:334-352): the dictionary key is the trimmed read + the `back` bases that follow the 3'
  *                adapter in the untrimmed line (`currentSeq.split(trimmed)[1][:len(adapter)+b][-b:]`, first occurrence,
  *                "" when the trimmed read is empty); counted once, after the last modifier; needs trim->adapter (3')
- *   dedup        -udd (:183-205): a count is a number of distinct UMI-tagged reads
+ *   dedup        -udd (:183-205): a count is a number of distinct UMI-tagged reads; 2: -udd with directional clustering (below)
  * The worker's length test applies to the insert (`len(pureSeq) >= min_len`, :360), with qiagen to the trimmed read (:349),
  * and baking's to the insert again (:173,192).
  * *out: RAW inserts in file order -- without dedup one per counted read; with dedup one per DISTINCT tagged read whose
@@ -172,6 +172,20 @@ typedef struct mirge_umi {
 int mirge_reads_parse_umi(mirge_ctx* ctx, const char* text, int64_t nbytes, int32_t format, int32_t min_len,
                           const mirge_trim* trim, const mirge_umi* umi, mirge_reads** out, int64_t* n_records,
                           mirge_reads** tagged_out);
+/* Error-tolerant UMI deduplication (--umi-cluster directional): the "directional" network method of UMI-tools (Smith, Heger &
+ * Sudbery 2017) on the distinct tagged reads of one sample.  `tagged`: any collapse result with ONE count column (*tagged_out above,
+ * or mirge_collapse[_weighted] of packed reads); the UMI is a read's first `front` and last `back` letters, 1 <= front + back <= 32.
+ * A read is eligible iff it holds no N, has at most 256 nt and at least front + back; two eligible reads of one length that differ in
+ * exactly one letter, inside the UMI, are neighbours; edge a -> v iff count(a) >= 2 count(v) - 1 (64-bit).  founder_out (host,
+ * [mirge_reads_count(tagged)], handle order) = 1 for every ineligible read, every read of count >= 2 without an edge into it, and the
+ * earliest member (smallest first index) of every connected component of count-1 reads none of whose members has a neighbour of count
+ * >= 2: as many founders among an insert's eligible reads as UMI-tools' searches.  *n_founders = the ones in founder_out.
+ * mirge_umi.dedup == 2 makes mirge_reads_parse_umi call the same routine: *out then holds the inserts of the founders only, in the order
+ * the founders first appeared; *tagged_out is what dedup == 1 gives.
+ * mirge_umi_cluster_stats: out[0..4] = tagged reads, eligible reads, count-1 reads with a count-1 neighbour, rounds of the label
+ * propagation and slots of the lookup table of this thread's last clustering. */
+int mirge_umi_cluster(mirge_ctx* ctx, const mirge_reads* tagged, int32_t front, int32_t back, uint8_t* founder_out, int64_t* n_founders);
+int mirge_umi_cluster_stats(int64_t* out);
 /* Several raw read sets as one, in the order given (the samples of a run, one file each, before the joint collapse
  * that replaces the per-file dicts and their outer join, digest.py:133-163,243).  The parts stay valid. */
 int mirge_reads_concat(mirge_ctx* ctx, const mirge_reads* const* parts, int32_t n_parts, mirge_reads** out);

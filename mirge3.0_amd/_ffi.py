@@ -32,7 +32,7 @@ EXPORTS = [
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
     "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device", "mirge_bam_huffman_probe",
     "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
-    "mirge_trf_cluster",
+    "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats",
 ]
 
 
@@ -89,10 +89,22 @@ class MirgeUmi(C.Structure):
     _fields_ = [("front", C.c_int32), ("back", C.c_int32), ("qiagen", C.c_int32), ("dedup", C.c_int32)]
 
     @staticmethod
-    def make(front: int, back: int, qiagen: bool = False, dedup: bool = False) -> "MirgeUmi":
+    def make(front: int, back: int, qiagen: bool = False, dedup: bool = False, cluster: Optional[str] = None) -> "MirgeUmi":
+        """``cluster="directional"`` (with ``dedup``): ``--umi-cluster directional``, ``dedup == 2`` in the struct"""
+        if cluster not in (None, "none", "directional"):
+            raise ValueError(f"cluster={cluster!r}: None or 'directional'")
+        directional = cluster == "directional"
+        if directional and not dedup:
+            raise ValueError("cluster='directional' needs dedup (-udd)")
+        if directional and not 1 <= int(front) + int(back) <= 32:
+            raise ValueError("cluster='directional' takes UMIs of 1 to 32 letters (front + back)")
         u = MirgeUmi()
-        u.front, u.back, u.qiagen, u.dedup = int(front), int(back), 1 if qiagen else 0, 1 if dedup else 0
+        u.front, u.back, u.qiagen, u.dedup = int(front), int(back), 1 if qiagen else 0, (2 if directional else 1) if dedup else 0
         return u
+
+    @property
+    def cluster(self) -> Optional[str]:
+        return "directional" if self.dedup == 2 else None
 
 
 _lib = None
@@ -597,6 +609,18 @@ class DeviceReads:
         _check(load().mirge_collapse_fetch(self.ctx._h, self._h, _p(cnt), _p(first)), "mirge_collapse_fetch")
         return cnt, first
 
+    def umi_cluster(self, front: int, back: int) -> np.ndarray:
+        """``mirge_umi_cluster`` on a one-column collapse result (distinct UMI-tagged reads with their counts) -> uint8 [U], handle
+        order: 1 = the read founds a molecule under the directional method (UMI = first ``front`` + last ``back`` letters)"""
+        n = len(self)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        nf = C.c_int64()
+        _check(load().mirge_umi_cluster(self.ctx._h, self._h, C.c_int32(int(front)), C.c_int32(int(back)), _p(out), C.byref(nf)), "mirge_umi_cluster")
+        out = out[:n]
+        if int(out.sum()) != nf.value:
+            raise RuntimeError("mirge_umi_cluster: the founder count and the flags differ")
+        return out
+
     def first_appearance_order(self) -> np.ndarray:
         """Indices of the unique reads in the order their first copy appeared in the raw reads (``mirge_collapse_order``)."""
         order = np.zeros(len(self), dtype=np.int64)
@@ -652,6 +676,13 @@ class DeviceReads:
             self.close()
         except Exception:
             pass
+
+
+def umi_cluster_stats() -> dict:
+    """``mirge_umi_cluster_stats``: what this thread's last directional clustering saw"""
+    out = np.zeros(5, dtype=np.int64)
+    _check(load().mirge_umi_cluster_stats(_p(out)), "mirge_umi_cluster_stats")
+    return dict(zip(("tagged", "eligible", "linked", "rounds", "slots"), (int(x) for x in out)))
 
 
 class CascadeResult:

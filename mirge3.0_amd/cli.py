@@ -7,7 +7,8 @@ Same flag names as the reference (``mirge/libs/parse.py``) for what is implement
 scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignored.  Writes the reference's files:
 ``run.log``, ``mapped.csv``, ``unmapped.csv``, ``miR.Counts.csv``, ``miR.RPM.csv``, ``annotation.report.csv/html``
 (+ ``isomirs.csv`` / ``isomirs.samples.csv`` with ``-ie``, ``sample_miRge3.gff`` with ``-gff``, the three
-``a2IEditing.*`` files with ``-ai``, ``<sample>_umiCounts.csv`` with ``-udd``, ``unmapped_tmp/`` with ``--unmapped-clusters``
+``a2IEditing.*`` files with ``-ai``, ``<sample>_umiCounts.csv`` with ``-udd`` (and ``<sample>_umiClusters.csv`` with this project's
+``--umi-cluster directional``), ``unmapped_tmp/`` with ``--unmapped-clusters``
 (FASTA files, the genome SAM and ``<sample>_clusters.tsv``) and ``--unmapped-align`` (the cluster filter's two files, the
 cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences) and ``--unmapped-features``
 (``<sample>_features.tsv``, ``_cluster.txt``, ``_precursor.fa``), the tRNA fragment reports with ``--trf-report`` and the two
@@ -53,6 +54,9 @@ def parse_args(argv=None):
                     help="f,b: drop f bases at the 5' end and b at the 3' end of every read before collapsing")
     ap.add_argument("-udd", "--umiDedup", dest="umiDedup", action="store_true",
                     help="with -umi: count distinct UMI-tagged reads per insert (writes <sample>_umiCounts.csv)")
+    ap.add_argument("--umi-cluster", dest="umi_cluster", default="none", choices=("none", "directional"),
+                    help="with -udd: 'directional' absorbs sequencing errors inside UMIs (UMI-tools' directional network method, Hamming "
+                         "distance 1): a count is a number of founder UMIs; also writes <sample>_umiClusters.csv")
     ap.add_argument("-tcf", "--tcf-out", dest="tcf_out", action="store_true",
                     help="write <sample>.trim.collapse.fa")
     ap.add_argument("-ie", "--isoform-entropy", dest="isoform_entropy", action="store_true",
@@ -167,6 +171,15 @@ def parse_args(argv=None):
         ap.error("--action mask / lowercase change a read's letters, not its bounds: not part of the MI355X path; -n must be >= 1")
     if (args.umiDedup or args.qiagenumi) and not args.uniq_mol_ids:
         ap.error("-udd / --qiagenumi require -umi f,b")
+    if args.umi_cluster != "none":
+        if not args.umiDedup:
+            ap.error("--umi-cluster directional requires -udd (and -umi f,b)")
+        try:
+            tag = [int(x) for x in str(args.uniq_mol_ids).split(",")]
+        except ValueError:
+            tag = []
+        if len(tag) != 2 or min(tag) < 0 or not 1 <= sum(tag) <= 32:
+            ap.error("--umi-cluster directional takes -umi f,b with 1 <= f + b <= 32")
     if args.qiagenumi and not (args.adapters and args.adapters[0][0] == "back"):
         ap.error("--qiagenumi reads the UMI behind the 3' adapter: give it with -a (first)")
     args.bowtieVersion = "True"

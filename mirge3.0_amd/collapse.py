@@ -16,6 +16,8 @@ UMI handling (digest.py:164-205,305-315,334-365) is part of
 (counts add up); with ``-udd`` the UMI-tagged reads are collapsed first, ``<sample>_umiCounts.csv`` is written from that
 result and ONE insert per distinct tagged read goes on, so a count is a number of molecules; ``--qiagenumi`` takes the
 UMI from behind the 3' adapter of the untrimmed read (the reference's ``currentSeq.split(trimmed)[1]`` string rule).
+``--umi-cluster directional`` (with ``-udd``; not in the reference) lets only the founders of UMI-tools' directional networks go on
+(``mirge_umi_cluster``) and writes ``<sample>_umiClusters.csv``.
 Both command lines of the reference's quick start (``docs/source/quick_start.md:282-314``) run this way.
 ``-tcf`` writes ``<sample>.trim.collapse.fa`` (digest.py:219-229).
 """
@@ -766,7 +768,8 @@ def umi_from_args(args):
         f, b = (int(x) for x in str(umi).split(","))
     except ValueError:
         raise SystemExit("-umi expects two comma separated integers, e.g. 4,4 or 0,12")
-    return _ffi.MirgeUmi.make(f, b, qiagen=qia, dedup=bool(getattr(args, "umiDedup", False)))
+    cluster = getattr(args, "umi_cluster", None)
+    return _ffi.MirgeUmi.make(f, b, qiagen=qia, dedup=bool(getattr(args, "umiDedup", False)), cluster=None if cluster in (None, "none") else cluster)
 
 
 def write_umi_counts(path, tagged: "_ffi.DeviceReads", front: int, back: int, min_len: int) -> int:
@@ -784,6 +787,27 @@ def write_umi_counts(path, tagged: "_ffi.DeviceReads", front: int, back: int, mi
         fh.write(b"UMISeq,transcriptSeq,UMICounts\n")
         fh.write(FlatSeqs.join_columns([tag, pure, digits], b",,\n"))
     return int(keep.shape[0])
+
+
+def write_umi_clusters(path, tagged: "_ffi.DeviceReads", front: int, back: int, min_len: int):
+    """``<sample>_umiClusters.csv`` (``--umi-cluster directional``): the lines of ``<sample>_umiCounts.csv`` in the same order with a fourth
+    column, 1 where the tagged read founds a molecule (``mirge_umi_cluster``).  Returns (tagged reads, eligible ones, founders)."""
+    founder = tagged.umi_cluster(front, back)
+    stats = _ffi.umi_cluster_stats()
+    order = tagged.first_appearance_order()
+    counts, _ = tagged.counts()
+    full = tagged.unpack().take(order)
+    c = counts[order, 0] if len(tagged) else np.zeros(0, np.uint32)
+    fo = founder[order] if len(tagged) else np.zeros(0, np.uint8)
+    pure, tag = full.umi_split(front, back)
+    keep = np.flatnonzero(pure.lengths >= int(min_len))
+    pure, tag, c, fo = pure.take(keep), tag.take(keep), c[keep], fo[keep]
+    digits = FlatSeqs.from_fixed(np.char.mod("%d", c.astype(np.int64)).astype("S")) if len(c) else FlatSeqs.from_list([])
+    flag = FlatSeqs.from_fixed(np.char.mod("%d", fo.astype(np.int64)).astype("S")) if len(c) else FlatSeqs.from_list([])
+    with open(path, "ab") as fh:
+        fh.write(b"UMISeq,transcriptSeq,UMICounts,Founder\n")
+        fh.write(FlatSeqs.join_columns([tag, pure, digits, flag], b",,,\n"))
+    return len(tagged), stats["eligible"], int(founder.sum())
 
 
 def write_tcf(path, raw: "_ffi.DeviceReads") -> None:
@@ -819,6 +843,10 @@ def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None,
     if tagged is not None:
         if workDir is not None:
             write_umi_counts(Path(workDir) / (str(name) + "_umiCounts.csv"), tagged, umi.front, umi.back, min_len)
+            if umi.dedup == 2:  # (the flags once more, for the file: milliseconds beside the text built here, profiles/umi_cluster.md)
+                n_tag, n_elig, n_found = write_umi_clusters(Path(workDir) / (str(name) + "_umiClusters.csv"), tagged, umi.front, umi.back, min_len)
+                with open(Path(workDir) / "run.log", "a") as lf:
+                    lf.write(f"{name}: --umi-cluster directional: {n_tag} distinct UMI-tagged reads, {n_elig} eligible, {n_found} founders\n")
         tagged.close()
     return raw, n_rec
 

@@ -51,3 +51,4 @@ __device__ __forceinline__ void load_read(const GroupView<W>& g, uint32_t i, Mir
 #include "kernels_sam.hpp"
 #include "kernels_bam.hpp"
 #include "kernels_trf.hpp"
+#include "kernels_umi.hpp"

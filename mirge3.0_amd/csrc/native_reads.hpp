@@ -575,6 +575,8 @@ static void reads_clear_groups(mirge_reads* r) {
 }
 
 extern "C" int mirge_collapse(mirge_ctx* c, const mirge_reads* raw, const int32_t* sample_ids, int32_t S, mirge_reads** uniq, int64_t* n_uniq);
+static int umi_check_layout(const std::string& who, int32_t front, int32_t back);  // native_umi.hpp
+static int umi_cluster_device(mirge_ctx* c, const mirge_reads* T, int32_t front, int32_t back, uint8_t* d_founder, int64_t* n_founders);
 
 extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len,
                                      const mirge_trim* trim, const mirge_umi* umi, mirge_reads** out, int64_t* n_records,
@@ -584,6 +586,8 @@ extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nby
     if (tagged_out) *tagged_out = nullptr;
     if (umi && (umi->front < 0 || umi->back < 0 || umi->front > MIRGE_MAX_READ_LEN || umi->back > MIRGE_MAX_READ_LEN))
         return fail(-1, "mirge_reads_parse_umi: -umi f,b out of range");
+    const bool cluster = umi && umi->dedup == 2;  // -udd with --umi-cluster directional: only founders go on (native_umi.hpp)
+    if (cluster) CHECK(umi_check_layout("mirge_reads_parse_umi", umi->front, umi->back));
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     if (format == 0) format = nbytes == 0 ? 3 : (text[0] == '@' ? 1 : (text[0] == '>' ? 2 : 3));
     TrimOpts topt;
@@ -639,6 +643,7 @@ extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nby
     // ... then ONE read per distinct tagged read, its insert, in the order the tagged reads first appeared: the second
     // collapse (the caller's) counts molecules, and its first indices are ranks in the reference's dictionary order
     uint32_t *keys = nullptr, *keys2 = nullptr;
+    uint8_t* founder = nullptr;
     int64_t *st2 = nullptr, *en2 = nullptr, *s2s2 = nullptr;
     int32_t* s2l2 = nullptr;
     void* stmp = nullptr;
@@ -654,10 +659,21 @@ extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nby
             const ReadGroup& g = T->g[gi];
             if (g.n) e = hipMemcpyAsync(keys + g.base, g.first, (size_t)g.n * 4, hipMemcpyDeviceToDevice, c->stream);
         }
+        if (cluster) {
+            // the reads that found no molecule leave the list: their keys sort behind every founder's, and U ends in front of them
+            if (e != hipSuccess) { rc = fail(-2, std::string("mirge_reads_parse_umi: ") + hipGetErrorString(e)); break; }
+            if ((rc = dalloc(c, &founder, (size_t)U))) break;
+            const int64_t U_all = U;
+            if ((rc = umi_cluster_device(c, T, f, b, founder, &U))) break;
+            hipLaunchKernelGGL(k_umi_mask_keys, dim3(grid_for(c, (size_t)U_all)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint8_t*)founder,
+                               (uint32_t)U_all, keys);
+            if (!U) break;
+        }
         size_t sb = 0;
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(nullptr, sb, keys, keys2, (int)U, 0, 32, c->stream);
+        const int n_sort = (int)(cluster ? T->n : U);
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(nullptr, sb, keys, keys2, n_sort, 0, 32, c->stream);
         if (e == hipSuccess && (rc = dalloc(c, (uint8_t**)&stmp, std::max<size_t>(sb, 16)))) break;
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(stmp, sb, keys, keys2, (int)U, 0, 32, c->stream);
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(stmp, sb, keys, keys2, n_sort, 0, 32, c->stream);
         if (e != hipSuccess) { rc = fail(-2, std::string("mirge_reads_parse_umi: ") + hipGetErrorString(e)); break; }
         if ((rc = dalloc(c, &st2, (size_t)U))) break;
         if ((rc = dalloc(c, &en2, (size_t)U))) break;
@@ -671,7 +687,7 @@ extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nby
         rc = parse_pack(J, st2, en2, s2s2, s2l2, (uint32_t)U, so, R.get(), nullptr);
     } while (0);
     (void)hipStreamSynchronize(c->stream);
-    c->release(rec_of_kept); c->release(keys); c->release(keys2); c->release(stmp);
+    c->release(rec_of_kept); c->release(keys); c->release(keys2); c->release(stmp); c->release(founder);
     c->release(st2); c->release(en2); c->release(s2s2); c->release(s2l2);
     if (rc) { mirge_reads_destroy(R.release()); return rc; }
     if (tagged_out) *tagged_out = Tg.release();
