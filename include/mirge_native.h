@@ -510,6 +510,33 @@ int mirge_bam_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_
  * length 1. */
 int mirge_bam_huffman_probe(mirge_ctx* ctx, const uint32_t* counts, int32_t n_sym, int32_t max_bits, uint8_t* lengths_out);
 
+/* ---- per-sample genome coverage as bedGraph (`--coverage`): depth per base from weighted intervals, as maximal runs of constant depth > 0.
+ * mirge_coverage_runs          n intervals from host arrays: chrom_rank (0 .. 2^24 - 1), 0-based start, len >= 1, weight >= 1, minus;
+ *                              depth(x) = the summed weight of the intervals that hold x, per strand when stranded != 0 (otherwise
+ *                              every run has strand 0).  The runs (chromosome rank, [start, end), depth; abutting runs of equal depth are
+ *                              one) arrive in file order -- plus strand first, then rank, then start -- in the caller's arrays of capacity
+ *                              2 n; *n_runs_out = how many.  An interval outside the contract (end <= 2^31 - 1 included) fails the call;
+ *                              2 n must stay below 2^31 - 16.
+ * mirge_coverage_write_device  one sample's intervals are the rows of mirge_sam_write_device's file (same arguments up to n_pass): a row
+ *                              with START, SEQ and count c is [START - 1, START - 1 + len(SEQ)) of weight c, minus iff FLAG 16.
+ *                              chrom_rank + chrom_rank_off[p] .. [p + 1] maps pass p's chromosome indices to ranks 0 .. n_rank-1 (-1: the
+ *                              caller's order does not hold the name, an error when a kept row lies there); rank_names /
+ *                              rank_name_off[n_rank + 1] are the names in rank order.  The lines `chrom \t start \t end \t depth \n` go
+ *                              to `path` (stranded == 0) or to `path` (plus) and `path_minus`.  Errors are raised before a file is
+ *                              opened -- a chromosome without rank (named in the message), START < 1 or an end beyond 2^31 - 1 -- and
+ *                              err_out[0..3] = kind (1 chromosome, 2 range), handle index of the unique read, pass, reference of the
+ *                              first such row of the file; any failure leaves no file.  Outputs: intervals, their summed weight, lines
+ *                              and bytes (both files together).  MIRGE_COV_CHUNK_BYTES / MIRGE_COV_TILE_BYTES: README. */
+int mirge_coverage_runs(mirge_ctx* ctx, int64_t n, const int32_t* chrom_rank, const int64_t* start, const int32_t* len,
+                        const uint32_t* weight, const uint8_t* minus, int32_t stranded, uint8_t* run_strand, int32_t* run_chrom,
+                        int64_t* run_start, int64_t* run_end, int64_t* run_depth, int64_t* n_runs_out);
+int mirge_coverage_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
+                                const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                                const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
+                                int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
+                                int64_t* err_out);
+
 /* ---- the sequence work behind the tRNA fragment report (the reference's -trf: summary.py:1060-1220, mirge2_tRF_a2i.py:22-62)
  * mirge_trf_hits_run  every best-stratum alignment (bowtie -a --best --strata) of the tRNA reads rows[n_rows] (handle indices of `uniq`;
  *                     a record's row is the index INTO rows).  A read the cascade gave to mature_pass: every forward window of

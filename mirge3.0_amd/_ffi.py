@@ -32,7 +32,7 @@ EXPORTS = [
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
     "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device", "mirge_bam_huffman_probe",
     "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
-    "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats",
+    "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats", "mirge_coverage_runs", "mirge_coverage_write_device",
 ]
 
 

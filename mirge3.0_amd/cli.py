@@ -12,7 +12,8 @@ scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignor
 (FASTA files, the genome SAM and ``<sample>_clusters.tsv``) and ``--unmapped-align`` (the cluster filter's two files, the
 cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences) and ``--unmapped-features``
 (``<sample>_features.tsv``, ``_cluster.txt``, ``_precursor.fa``), the tRNA fragment reports with ``--trf-report`` and the two
-clustering files per sample behind them with ``--trf-clusters``).
+clustering files per sample behind them with ``--trf-clusters``, ``<sample>.bedgraph`` or ``<sample>.plus.bedgraph`` /
+``<sample>.minus.bedgraph`` with this project's ``--coverage``).
 
 One process: all samples on one GPU, byte-compatible outputs.  Under ``torch.distributed.run`` with N
 ranks: samples are sharded one per GPU (multigpu.py); rank 0 gathers each sample's count columns and its
@@ -112,11 +113,17 @@ def parse_args(argv=None):
                          "the device (the text the reference's -bam hands to samtools; --sorted-bam writes the sorted, indexed BAM)")
     ap.add_argument("--sam-header", dest="sam_header", default=None, metavar="FILE",
                     help="with --sam-out: FILE is copied verbatim to the top of every <sample>.sam (default: '@HD VN:1.0 SO:unsorted'); "
-                         "with --sorted-bam (required there): its @SQ SN:/LN: lines are the BAM's reference list, in that order")
+                         "with --sorted-bam (required there): its @SQ SN:/LN: lines are the BAM's reference list, in that order; "
+                         "with --coverage: its @SQ lines, if it has any, are the chromosome order of the bedGraph files")
     ap.add_argument("--sorted-bam", dest="sorted_bam", action="store_true",
                     help="write <sample>_sorted.bam and <sample>_sorted.bai for every sample: the records of --sam-out's <sample>.sam as "
                          "BAM, coordinate-sorted, BGZF-compressed and indexed on the device (what the reference's -bam gets from samtools "
                          "view / sort / index); needs --sam-header FILE with the genome's @SQ lines; independent of --sam-out")
+    ap.add_argument("--coverage", dest="coverage", nargs="?", const="unstranded", default=None, choices=("unstranded", "stranded"),
+                    help="write the depth per genome base of --sam-out's rows as bedGraph, computed and formatted on the device: "
+                         "<sample>.bedgraph (unstranded, the default) or <sample>.plus.bedgraph and <sample>.minus.bedgraph (stranded); "
+                         "a row counts with its read count; chromosomes in the @SQ order of --sam-header FILE, else in byte order; "
+                         "independent of --sam-out and --sorted-bam")
     ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "tight", "host"),
                     help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
                          "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
@@ -201,8 +208,10 @@ def parse_args(argv=None):
             ap.error("-sl is bowtie's -l: at least 5")
         if args.ignored_maxl is not None and int(args.ignored_maxl) > 64:
             ap.error("-maxl above 64: the genome scan on the device takes reads of at most 64 nt")
-    if args.sam_header and not (args.sam_out or args.sorted_bam):
-        ap.error("--sam-header requires --sam-out or --sorted-bam")
+    if args.sam_header and not (args.sam_out or args.sorted_bam or args.coverage):
+        ap.error("--sam-header requires --sam-out, --sorted-bam or --coverage")
+    if args.coverage and (args.save_pkl or args.resume or args.backend == "bowtie"):
+        ap.error("--coverage runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.sorted_bam and (args.save_pkl or args.resume or args.backend == "bowtie"):
         ap.error("--sorted-bam runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.sorted_bam and not args.sam_header:
@@ -223,6 +232,13 @@ def parse_args(argv=None):
         try:
             with open(args.sam_header, "rb") as fh:
                 parse_sq(fh.read())
+        except ValueError as e:
+            ap.error(str(e))
+    if args.coverage and args.sam_header:  # (a header without @SQ lines is fine here: byte order)
+        from .coverage import sq_order
+        try:
+            with open(args.sam_header, "rb") as fh:
+                sq_order(fh.read())
         except ValueError as e:
             ap.error(str(e))
     if args.genome_filter == "gpu" and args.genome_retained:
@@ -319,6 +335,8 @@ def main(argv=None):
         sys.exit("--sam-out is a single-process option")
     if world > 1 and args.sorted_bam:
         sys.exit("--sorted-bam is a single-process option")
+    if world > 1 and args.coverage:
+        sys.exit("--coverage is a single-process option")
     if world > 1 and args.trf_report:
         sys.exit("--trf-report / --trf-clusters are single-process options")
     if not (Path(args.libraries_path) / args.organism_name / "index.Libs").exists():

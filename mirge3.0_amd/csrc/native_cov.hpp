@@ -1,0 +1,357 @@
+// native_cov.hpp -- part of mirge_native.hip (one translation unit): `<sample>.bedgraph` of `--coverage` (kernels_cov.hpp).  CovDev is
+// everything behind the interval list -- events, radix sort, inclusive sum, three compactions, the runs, their text -- and serves both
+// exports: mirge_coverage_runs (intervals from the host, runs back to the host: tests and other callers) and
+// mirge_coverage_write_device (intervals from the resident run through SamPrep, the rows of `--sam-out`; text to one or two files, chunk
+// by chunk through the page-locked halves `--sam-out` uses).  MIRGE_COV_CHUNK_BYTES / MIRGE_COV_TILE_BYTES (read per call): the chunk
+// and the workgroup's tile; tests make them small so that their boundaries fall inside numbers and names.
+#pragma once
+
+struct CovDev {
+    unsigned long long *kA = nullptr, *kB = nullptr, *d_sum = nullptr, *d_bytes = nullptr, *d_off = nullptr;
+    long long *vA = nullptr, *vB = nullptr;
+    uint32_t *flag = nullptr, *pos = nullptr, *words = nullptr, *d_name_off = nullptr;
+    uint8_t* d_name_data = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    CovRuns r{nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t n_runs = 0, n_plus = 0;
+    unsigned long long weight = 0, body = 0, split = 0;  // split: the bytes of the plus strand's lines
+
+    int need_tmp(mirge_ctx* c, size_t bytes) {
+        if (bytes <= tmp_bytes) return 0;
+        c->release(tmp); tmp = nullptr; tmp_bytes = 0;
+        CHECK(c->alloc(&tmp, bytes));
+        tmp_bytes = bytes;
+        return 0;
+    }
+    // flag[0 .. m) is queued: pos = its exclusive sum, *count = the flags set (synchronises the stream)
+    int count_flags(mirge_ctx* c, size_t m, uint32_t* count) {
+        size_t tb = 0;
+        HIPOK(hipMemsetAsync(flag + m, 0, 4, c->stream));
+        HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, pos, (int)(m + 1), c->stream));
+        CHECK(need_tmp(c, tb));
+        HIPOK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, pos, (int)(m + 1), c->stream));
+        HIPOK(hipMemcpyAsync(count, pos + m, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    // the runs of n intervals (device arrays) over n_rank chromosome ranks, in file order
+    int runs(mirge_ctx* c, const std::string& who, const CovIntervals& iv, size_t n, uint32_t n_rank, bool stranded) {
+        n_runs = n_plus = 0; weight = 0;
+        if (n == 0) return 0;
+        if (2 * (unsigned long long)n >= 0x7FFFFFF0ull) return fail(-5, who + ": too many intervals for one call (two events each must fit 32-bit indices)");
+        if (n_rank < 1 || n_rank > (1u << 24)) return fail(-1, who + ": 1 to 2^24 chromosome ranks");
+        int rbits = 0;
+        while ((1ull << rbits) < (unsigned long long)n_rank) rbits++;
+        const int strand_shift = MIRGE_COV_POS_BITS + rbits, end_bit = strand_shift + (stranded ? 1 : 0);
+        const size_t m = 2 * n;
+        CHECK(dalloc(c, &kA, m)); CHECK(dalloc(c, &kB, m)); CHECK(dalloc(c, &vA, m)); CHECK(dalloc(c, &vB, m));
+        CHECK(dalloc(c, &flag, m + 1)); CHECK(dalloc(c, &pos, m + 1)); CHECK(dalloc(c, &words, (size_t)4)); CHECK(dalloc(c, &d_sum, (size_t)1));
+        HIPOK(hipMemsetAsync(words, 0, 16, c->stream));
+        HIPOK(hipMemsetAsync(d_sum, 0, 8, c->stream));
+        size_t tb_sort = 0, tb_sum = 0;
+        HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, kA, kB, vA, vB, (int)m, 0, end_bit, c->stream));
+        HIPOK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_sum, vB, vA, (int)m, c->stream));
+        CHECK(need_tmp(c, std::max(tb_sort, tb_sum)));
+        const dim3 block(MIRGE_BLOCK);
+        { LaunchScope ls(c, "k_cov_events", (double)n);
+          hipLaunchKernelGGL(k_cov_events, dim3(grid_for(c, n)), block, 0, c->stream, iv, (uint32_t)n, n_rank, stranded ? 1 : 0, strand_shift, kA, vA, words, d_sum); }
+        HIPOK(hipcub::DeviceRadixSort::SortPairs(tmp, tb_sort, kA, kB, vA, vB, (int)m, 0, end_bit, c->stream));
+        HIPOK(hipcub::DeviceScan::InclusiveSum(tmp, tb_sum, vB, vA, (int)m, c->stream));
+        // ---- the last event of every key with its sum: (kB, vA) -> (kA, vB)
+        uint32_t n1 = 0, n2 = 0, n3 = 0, hw[4] = {0, 0, 0, 0};
+        { LaunchScope ls(c, "k_cov_last", (double)m);
+          hipLaunchKernelGGL(k_cov_last, dim3(grid_for(c, m)), block, 0, c->stream, (const unsigned long long*)kB, (uint32_t)m, flag); }
+        HIPOK(hipMemcpyAsync(hw, words, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(&weight, d_sum, 8, hipMemcpyDeviceToHost, c->stream));
+        CHECK(count_flags(c, m, &n1));
+        if (hw[0] & 1u)
+            return fail(-1, who + ": an interval outside the contract (rank in [0, ranks), start >= 0, length >= 1, weight >= 1, end <= 2^31 - 1)");
+        { LaunchScope ls(c, "k_cov_scatter", (double)m);
+          hipLaunchKernelGGL(k_cov_scatter, dim3(grid_for(c, m)), block, 0, c->stream, (const unsigned long long*)kB, (const long long*)vA,
+                             (const uint32_t*)flag, (const uint32_t*)pos, (uint32_t)m, kA, vB); }
+        // ---- of those, the entries where the sum changes: (kA, vB) -> (kB, vA)
+        { LaunchScope ls(c, "k_cov_change", (double)n1);
+          hipLaunchKernelGGL(k_cov_change, dim3(grid_for(c, n1)), block, 0, c->stream, (const long long*)vB, n1, flag); }
+        CHECK(count_flags(c, n1, &n2));
+        { LaunchScope ls(c, "k_cov_scatter", (double)n1);
+          hipLaunchKernelGGL(k_cov_scatter, dim3(grid_for(c, n1)), block, 0, c->stream, (const unsigned long long*)kA, (const long long*)vB,
+                             (const uint32_t*)flag, (const uint32_t*)pos, n1, kB, vA); }
+        // ---- of those, the entries with a sum: the runs
+        if (n2 == 0) return 0;
+        { LaunchScope ls(c, "k_cov_nonzero", (double)n2);
+          hipLaunchKernelGGL(k_cov_nonzero, dim3(grid_for(c, n2)), block, 0, c->stream, (const long long*)vA, n2, flag, words); }
+        HIPOK(hipMemcpyAsync(hw, words, 16, hipMemcpyDeviceToHost, c->stream));
+        CHECK(count_flags(c, n2, &n3));
+        if (hw[0] & 2u) return fail(-3, who + ": the depth fell below 0 or did not return to 0");
+        CHECK(dalloc(c, &r.strand, std::max<size_t>(n3, 1))); CHECK(dalloc(c, &r.chrom, std::max<size_t>(n3, 1)));
+        CHECK(dalloc(c, &r.start, std::max<size_t>(n3, 1))); CHECK(dalloc(c, &r.end, std::max<size_t>(n3, 1)));
+        CHECK(dalloc(c, &r.depth, std::max<size_t>(n3, 1)));
+        { LaunchScope ls(c, "k_cov_runs", (double)n2);
+          hipLaunchKernelGGL(k_cov_runs, dim3(grid_for(c, n2)), block, 0, c->stream, (const unsigned long long*)kB, (const long long*)vA,
+                             (const uint32_t*)flag, (const uint32_t*)pos, n2, strand_shift, r, words + 1); }
+        HIPOK(hipMemcpyAsync(hw, words, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        HIPOK(hipGetLastError());
+        n_runs = n3; n_plus = hw[1];
+        return 0;
+    }
+    // the lines' offsets: name_off[n_rank + 1] into name_data (host), the chromosome names in rank order
+    int measure(mirge_ctx* c, const char* name_data, const int64_t* name_off, uint32_t n_rank) {
+        body = split = 0;
+        if (n_runs == 0) return 0;
+        std::vector<uint32_t> off32((size_t)n_rank + 1);
+        for (uint32_t k = 0; k <= n_rank; k++) off32[k] = (uint32_t)(name_off[k] - name_off[0]);
+        const size_t nb = off32[n_rank];
+        CHECK(dalloc(c, &d_name_off, (size_t)n_rank + 1)); CHECK(dalloc(c, &d_name_data, std::max<size_t>(nb, 1)));
+        CHECK(dalloc(c, &d_bytes, n_runs + 1)); CHECK(dalloc(c, &d_off, n_runs + 1));
+        hipError_t e = hipMemcpyAsync(d_name_off, off32.data(), ((size_t)n_rank + 1) * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && nb) e = hipMemcpyAsync(d_name_data, name_data + name_off[0], nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_bytes + n_runs, 0, 8, c->stream);
+        if (e == hipSuccess) {
+            LaunchScope ls(c, "k_cov_measure", (double)n_runs);
+            hipLaunchKernelGGL(k_cov_measure, dim3(grid_for(c, n_runs)), dim3(MIRGE_BLOCK), 0, c->stream, r, (uint32_t)n_runs, (const uint32_t*)d_name_off, d_bytes);
+        }
+        size_t tb = 0;
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_bytes, d_off, (int)(n_runs + 1), c->stream);
+        int rc = 0;
+        if (e == hipSuccess && (rc = need_tmp(c, tb))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, d_bytes, d_off, (int)(n_runs + 1), c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&body, d_off + n_runs, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&split, d_off + n_plus, 8, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // (also when a call failed: off32 leaves scope)
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return fail(-2, std::string("coverage: ") + hipGetErrorString(e));
+        return 0;
+    }
+    void release(mirge_ctx* c) {
+        for (void* p : {(void*)kA, (void*)kB, (void*)d_sum, (void*)d_bytes, (void*)d_off, (void*)vA, (void*)vB, (void*)flag, (void*)pos, (void*)words,
+                        (void*)d_name_off, (void*)d_name_data, tmp, (void*)r.strand, (void*)r.chrom, (void*)r.start, (void*)r.end, (void*)r.depth})
+            c->release(p);
+    }
+};
+
+extern "C" int mirge_coverage_runs(mirge_ctx* c, int64_t n, const int32_t* chrom_rank, const int64_t* start, const int32_t* len, const uint32_t* weight,
+                                   const uint8_t* minus, int32_t stranded, uint8_t* run_strand, int32_t* run_chrom, int64_t* run_start,
+                                   int64_t* run_end, int64_t* run_depth, int64_t* n_runs_out) {
+    const std::string who = "mirge_coverage_runs";
+    if (!c || n < 0 || !n_runs_out || (n && (!chrom_rank || !start || !len || !weight || !minus || !run_strand || !run_chrom || !run_start || !run_end || !run_depth)))
+        return fail(-1, who + ": bad argument");
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    *n_runs_out = 0;
+    if (n == 0) return 0;
+    if (2 * (unsigned long long)n >= 0x7FFFFFF0ull) return fail(-5, who + ": too many intervals for one call (two events each must fit 32-bit indices)");
+    int32_t top = 0;  // (the sort covers the rank bits that are used)
+    for (int64_t i = 0; i < n; i++) top = std::max(top, chrom_rank[i]);
+    if (top >= (1 << 24)) return fail(-1, who + ": a chromosome rank beyond 2^24");
+    const size_t sn = (size_t)n;
+    int32_t *d_rank = nullptr, *d_len = nullptr;
+    long long* d_start = nullptr;
+    uint32_t* d_w = nullptr;
+    uint8_t* d_minus = nullptr;
+    CovDev dev;
+    auto run = [&]() -> int {
+        CHECK(dalloc(c, &d_rank, sn)); CHECK(dalloc(c, &d_len, sn)); CHECK(dalloc(c, &d_start, sn)); CHECK(dalloc(c, &d_w, sn)); CHECK(dalloc(c, &d_minus, sn));
+        HIPOK(hipMemcpyAsync(d_rank, chrom_rank, sn * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_start, start, sn * 8, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_len, len, sn * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_w, weight, sn * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_minus, minus, sn, hipMemcpyHostToDevice, c->stream));
+        CHECK(dev.runs(c, who, CovIntervals{d_rank, d_start, d_len, d_w, d_minus}, sn, (uint32_t)top + 1u, stranded != 0));
+        if (dev.n_runs > 2 * sn) return fail(-3, who + ": more runs than events");
+        if (dev.n_runs) {
+            HIPOK(hipMemcpyAsync(run_strand, dev.r.strand, dev.n_runs, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(hipMemcpyAsync(run_chrom, dev.r.chrom, dev.n_runs * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(hipMemcpyAsync(run_start, dev.r.start, dev.n_runs * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(hipMemcpyAsync(run_end, dev.r.end, dev.n_runs * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(hipMemcpyAsync(run_depth, dev.r.depth, dev.n_runs * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(hipStreamSynchronize(c->stream));
+        }
+        return 0;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(c->stream);
+    c->drain();
+    dev.release(c);
+    c->release(d_rank); c->release(d_len); c->release(d_start); c->release(d_w); c->release(d_minus);
+    if (rc == 0) *n_runs_out = (int64_t)dev.n_runs;
+    return rc;
+}
+
+extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                                           const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                           const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                                           const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
+                                           int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
+                                           int64_t* err_out) {
+    const std::string who = "mirge_coverage_write_device";
+    if (!c || !path || (stranded && !path_minus) || !chrom_rank || !chrom_rank_off || n_rank < 0 || n_rank > (1 << 24) || !rank_name_off ||
+        (n_rank && !rank_names) || n_pass < 1 || n_pass > MIRGE_MAX_PASSES || !passes)
+        return fail(-1, who + ": bad argument");
+    if (err_out) for (int k = 0; k < 4; k++) err_out[k] = 0;
+    for (int32_t k = 0; k < n_rank; k++)
+        if (rank_name_off[k + 1] < rank_name_off[k] || rank_name_off[k + 1] - rank_name_off[0] >= 0x7FFFFFF0ll) return fail(-1, who + ": malformed chromosome names");
+    HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
+    HostClock hc("coverage_write_device");
+    size_t tile = sam_env_bytes("MIRGE_COV_TILE_BYTES", 8160);
+    tile = std::min<size_t>(MIRGE_COV_MAX_TILE, std::max<size_t>(64, tile)) & ~size_t(15);
+    size_t chunk = sam_env_bytes("MIRGE_COV_CHUNK_BYTES", (size_t)32 << 20);
+    chunk = std::min<size_t>((size_t)1 << 30, std::max(chunk, tile)) / tile * tile;
+
+    SamPrep prep;
+    CovDev dev;
+    int32_t *d_map = nullptr, *d_rank = nullptr, *d_len = nullptr, *d_desc = nullptr;
+    long long* d_start = nullptr;
+    uint32_t *d_w = nullptr, *d_err = nullptr;
+    uint8_t *d_minus = nullptr, *d_text[2] = {nullptr, nullptr};
+    int rc = 0, fd[2] = {-1, -1};
+    const char* paths[2] = {path, stranded ? path_minus : nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    size_t n_rows = 0;
+    do {
+        if ((rc = prep.build(c, who, U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
+        n_rows = prep.n_rows;
+        hc.lap("rows chosen");
+        // ---- every named pass's chromosome index -> global rank
+        CovRankMap rm;
+        std::memset(&rm, 0, sizeof(rm));
+        for (int p = 0; p < n_pass && rc == 0; p++) {
+            const int64_t nn = chrom_rank_off[p + 1] - chrom_rank_off[p];
+            bool named = false;
+            for (int k = 0; k < n_class; k++) named = named || class_pass[k] == p;
+            if (chrom_rank_off[p] < 0 || chrom_rank_off[p] >= 0x7FFFFFF0ll || nn < 0 || (named && nn != passes[p].n_chrom))
+                rc = fail(-1, who + ": the rank table of pass " + std::to_string(p) + " does not fit its chromosomes");
+            for (int64_t k = 0; k < nn && rc == 0; k++)
+                if (chrom_rank[chrom_rank_off[p] + k] >= n_rank) rc = fail(-1, who + ": a chromosome rank beyond the names given");
+            rm.rank_off[p] = (uint32_t)chrom_rank_off[p];
+        }
+        if (rc) break;
+        const size_t n_map = (size_t)chrom_rank_off[n_pass];
+        if ((rc = dalloc(c, &d_map, std::max<size_t>(n_map, 1)))) break;
+        if ((rc = dalloc(c, &d_err, (size_t)2))) break;
+        if ((rc = dalloc(c, &d_desc, (size_t)4))) break;
+        const size_t cap = std::max<size_t>(n_rows, 1);
+        if ((rc = dalloc(c, &d_rank, cap)) || (rc = dalloc(c, &d_len, cap)) || (rc = dalloc(c, &d_start, cap)) || (rc = dalloc(c, &d_w, cap)) ||
+            (rc = dalloc(c, &d_minus, cap))) break;
+        rm.rank_of = d_map;
+        uint32_t herr[2] = {MIRGE_COV_NONE, MIRGE_COV_NONE};
+        hipError_t e = hipSuccess;
+        if (n_map) e = hipMemcpyAsync(d_map, chrom_rank, n_map * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_err, 0xFF, 8, c->stream);
+        if (e == hipSuccess && n_rows) {
+            LaunchScope ls(c, "k_cov_intervals", (double)n_rows);
+            hipLaunchKernelGGL(k_cov_intervals, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, prep.t, (const uint32_t*)prep.d_rows, (uint32_t)n_rows, rm,
+                               d_rank, d_start, d_len, d_w, d_minus, d_err);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(herr, d_err, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { rc = fail(-2, who + ": " + hipGetErrorString(e)); break; }
+        if (herr[0] != MIRGE_COV_NONE || herr[1] != MIRGE_COV_NONE) {  // name the first offending row of the file
+            const bool range = herr[0] == MIRGE_COV_NONE || (herr[1] != MIRGE_COV_NONE && herr[1] < herr[0]);
+            int32_t d[4] = {0, 0, 0, 0};
+            hipLaunchKernelGGL(k_cov_describe, dim3(1), dim3(64), 0, c->stream, prep.t, (const uint32_t*)prep.d_rows, range ? herr[1] : herr[0], d_desc);
+            e = hipMemcpyAsync(d, d_desc, 16, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { rc = fail(-2, who + ": " + hipGetErrorString(e)); break; }
+            if (err_out) { err_out[0] = range ? 2 : 1; err_out[1] = d[0]; err_out[2] = d[1]; err_out[3] = d[2]; }
+            if (range) {
+                rc = fail(-1, who + ": a read lies outside [1, 2^31 - 1] of its chromosome (unique read " + std::to_string(d[0]) + ", pass " +
+                                  std::to_string(d[1]) + ", reference " + std::to_string(d[2]) + ")");
+            } else {
+                std::string name = "?";
+                if (d[1] >= 0 && d[1] < n_pass && d[3] >= 0 && (int64_t)d[3] < passes[d[1]].n_chrom) {
+                    const mirge_sam_pass& in = passes[d[1]];
+                    name.assign(in.chrom_data + in.chrom_off[d[3]], in.chrom_data + in.chrom_off[d[3] + 1]);
+                }
+                rc = fail(-1, who + ": reads lie on '" + name + "', which no @SQ line of the header names");
+            }
+            break;
+        }
+        hc.lap("intervals");
+        if ((rc = dev.runs(c, who, CovIntervals{d_rank, d_start, d_len, d_w, d_minus}, n_rows, (uint32_t)std::max(n_rank, 1), stranded != 0))) break;
+        hc.lap("runs");
+        if ((rc = dev.measure(c, rank_names, rank_name_off, (uint32_t)n_rank))) break;
+        hc.lap("measured");
+        // ---- the file or files: every error of the data has been raised by now
+        const unsigned long long body = dev.body, split = stranded ? dev.split : dev.body;
+        for (int f = 0; f < 2 && rc == 0; f++) {
+            if (!paths[f]) continue;
+            fd[f] = ::open(paths[f], O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (fd[f] < 0) rc = fail(-8, std::string("cannot write ") + paths[f]);
+        }
+        if (rc) break;
+        if (body) {
+            const size_t buf = (size_t)std::min<unsigned long long>(chunk, body);
+            if (2 * buf > c->sam_pinned_bytes) {  // page-locked staging of two chunks, kept between samples (shared with --sam-out)
+                if (c->sam_pinned) (void)hipHostFree(c->sam_pinned);
+                c->sam_pinned = nullptr; c->sam_pinned_bytes = 0;
+                if (hipHostMalloc((void**)&c->sam_pinned, 2 * buf, hipHostMallocDefault) != hipSuccess) {
+                    rc = fail(-3, who + ": cannot page-lock " + std::to_string(2 * buf) + " bytes"); break;
+                }
+                c->sam_pinned_bytes = 2 * buf;
+            }
+            if ((rc = dalloc(c, &d_text[0], buf + 16))) break;
+            if (body > buf && (rc = dalloc(c, &d_text[1], buf + 16))) break;
+            ev[0] = c->get_evt(); ev[1] = c->get_evt();
+            const unsigned long long n_chunks = (body + chunk - 1) / chunk;
+            auto put_part = [&](int f, const uint8_t* src, size_t nn, unsigned long long at) -> int {
+                size_t done = 0;
+                while (done < nn) {
+                    const ssize_t wr = ::pwrite(fd[f], src + done, nn - done, (off_t)(at + done));
+                    if (wr <= 0) return fail(-8, who + ": write error on " + paths[f]);
+                    done += (size_t)wr;
+                }
+                return 0;
+            };
+            auto put = [&](unsigned long long ci) -> int {  // chunk ci has been queued: wait for its copy; the plus strand's bytes end at `split`
+                if (hipEventSynchronize(ev[ci & 1]) != hipSuccess) return fail(-2, who + ": the copy of a chunk failed");
+                const unsigned long long at0 = ci * chunk, at1 = at0 + std::min<unsigned long long>(chunk, body - at0);
+                const uint8_t* src = c->sam_pinned + (ci & 1) * buf;
+                if (at0 < split) CHECK(put_part(0, src, (size_t)(std::min(at1, split) - at0), at0));
+                if (at1 > split) { const unsigned long long b0 = std::max(at0, split); CHECK(put_part(1, src + (b0 - at0), (size_t)(at1 - b0), b0 - split)); }
+                return 0;
+            };
+            for (unsigned long long ci = 0; ci < n_chunks && rc == 0; ci++) {
+                const unsigned long long at0 = ci * chunk;
+                const uint32_t nn = (uint32_t)std::min<unsigned long long>(chunk, body - at0);
+                const size_t tiles = ((size_t)nn + tile - 1) / tile;
+                {
+                    LaunchScope ls(c, "k_cov_write", (double)nn);
+                    hipLaunchKernelGGL(k_cov_write, dim3((unsigned)std::min<size_t>(tiles, (size_t)c->n_cu * 32)), dim3(MIRGE_BLOCK), 0, c->stream, dev.r,
+                                       (uint32_t)dev.n_runs, (const uint32_t*)dev.d_name_off, (const uint8_t*)dev.d_name_data,
+                                       (const unsigned long long*)dev.d_off, at0, nn, (uint32_t)tile, d_text[ci & 1]);
+                }
+                e = hipMemcpyAsync(c->sam_pinned + (ci & 1) * buf, d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream);
+                if (e == hipSuccess) e = hipEventRecord(ev[ci & 1], c->stream);
+                if (e != hipSuccess) { rc = fail(-2, who + ": " + hipGetErrorString(e)); break; }
+                if (ci) rc = put(ci - 1);  // (chunk ci - 1's half of the staging is free again before chunk ci + 1 is queued)
+            }
+            if (rc == 0) rc = put(n_chunks - 1);
+        }
+        if (rc) break;
+        hc.lap("formatted + written");
+    } while (0);
+    (void)hipStreamSynchronize(c->stream);
+    c->drain();
+    for (int f = 0; f < 2; f++) {
+        if (fd[f] < 0) continue;
+        struct stat st;
+        const bool regular = ::fstat(fd[f], &st) == 0 && S_ISREG(st.st_mode);
+        if (::close(fd[f]) != 0 && rc == 0) rc = fail(-8, who + ": cannot close " + paths[f]);
+        fd[f] = regular ? -2 : -1;
+    }
+    if (rc != 0)  // never a partial file that looks like a result
+        for (int f = 0; f < 2; f++) if (fd[f] == -2) (void)::unlink(paths[f]);
+    for (auto& x : ev) if (x) c->evt_pool.push_back(x);
+    prep.release(c);
+    dev.release(c);
+    for (void* p : {(void*)d_map, (void*)d_rank, (void*)d_len, (void*)d_desc, (void*)d_start, (void*)d_w, (void*)d_err, (void*)d_minus, (void*)d_text[0], (void*)d_text[1]})
+        c->release(p);
+    if (rc == 0) {
+        if (n_intervals_out) *n_intervals_out = (int64_t)n_rows;
+        if (weight_out) *weight_out = (int64_t)dev.weight;
+        if (n_lines_out) *n_lines_out = (int64_t)dev.n_runs;
+        if (n_bytes_out) *n_bytes_out = (int64_t)dev.body;
+    }
+    return rc;
+}

@@ -323,6 +323,11 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
             raise RuntimeError("--sorted-bam needs the cascade's result on the device (a single-process run)")
         from . import bam_export as _bam_export
         out["sorted_bam"] = _bam_export.run(args, workDir, base_names, casc, uniq, res, order, tm)
+    if getattr(args, "coverage", None):  # --coverage: <sample>.bedgraph, the depth of the same rows per base (and strand)
+        if ann is not None or res is None:
+            raise RuntimeError("--coverage needs the cascade's result on the device (a single-process run)")
+        from . import coverage as _coverage
+        out["coverage"] = _coverage.run(args, workDir, base_names, casc, uniq, res, order, tm)
     if getattr(args, "trf_report", False):  # --trf-report: the reference's -trf up to its per-sample reports (summary.py:1060-1220)
         if ann is not None or res is None:
             raise RuntimeError("--trf-report needs the cascade's result on the device (a single-process run)")
