@@ -537,6 +537,26 @@ int mirge_coverage_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const m
                                 int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
                                 int64_t* err_out);
 
+/* ---- the runs of `--coverage` as bigWig (`--coverage-bigwig`; the format: mirge3_amd/bigwig.py): one file per strand, written to
+ * `<path>.tmp` and renamed when every file of the call is whole; any failure leaves no file.
+ * mirge_bigwig_from_intervals  host intervals as in mirge_coverage_runs.  rank_names / rank_name_off[n_rank + 1]: ALL chromosome names
+ *                              in rank order (n_rank >= 1), chrom_size[rank] <= 2^32 - 1, chrom_id[rank] = the name's position among
+ *                              the names sorted by bytes (checked).  stats_out[16 f + ..] of file f: sections, items, zoom levels,
+ *                              bytes, the largest depth, then the records of every kept level.  A run that ends beyond its
+ *                              chromosome's size fails the call with err_out = {3, rank, end, size}.
+ * mirge_bigwig_write_device    the resident run: the arguments of mirge_coverage_write_device up to rank_name_off, then the sizes and
+ *                              ids as above; err_out kinds 1 and 2 as there, 3 as above.
+ * MIRGE_BW_SECTION_ITEMS (1 .. 1024), MIRGE_BW_ZOOM_BASE (default 64), MIRGE_BW_DEFLATE (device | none), MIRGE_BW_CHUNK_BYTES: README. */
+int mirge_bigwig_from_intervals(mirge_ctx* ctx, int64_t n, const int32_t* chrom_rank, const int64_t* start, const int32_t* len,
+                                const uint32_t* weight, const uint8_t* minus, int32_t stranded, int32_t n_rank, const char* rank_names,
+                                const int64_t* rank_name_off, const int64_t* chrom_size, const int32_t* chrom_id, const char* path,
+                                const char* path_minus, int64_t* stats_out, int64_t* err_out);
+int mirge_bigwig_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
+                              const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                              const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                              const int64_t* rank_name_off, const int64_t* chrom_size, const int32_t* chrom_id, int32_t stranded,
+                              const char* path, const char* path_minus, int64_t* stats_out, int64_t* err_out);
+
 /* ---- the sequence work behind the tRNA fragment report (the reference's -trf: summary.py:1060-1220, mirge2_tRF_a2i.py:22-62)
  * mirge_trf_hits_run  every best-stratum alignment (bowtie -a --best --strata) of the tRNA reads rows[n_rows] (handle indices of `uniq`;
  *                     a record's row is the index INTO rows).  A read the cascade gave to mature_pass: every forward window of

@@ -33,6 +33,7 @@ EXPORTS = [
     "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device", "mirge_bam_huffman_probe",
     "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
     "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats", "mirge_coverage_runs", "mirge_coverage_write_device",
+    "mirge_bigwig_from_intervals", "mirge_bigwig_write_device",
 ]
 
 

@@ -124,6 +124,10 @@ def parse_args(argv=None):
                          "<sample>.bedgraph (unstranded, the default) or <sample>.plus.bedgraph and <sample>.minus.bedgraph (stranded); "
                          "a row counts with its read count; chromosomes in the @SQ order of --sam-header FILE, else in byte order; "
                          "independent of --sam-out and --sorted-bam")
+    ap.add_argument("--coverage-bigwig", dest="coverage_bigwig", action="store_true",
+                    help="with --coverage: also write the same runs as bigWig, sections, zoom levels and their deflate computed on the "
+                         "device: <sample>.bw, or <sample>.plus.bw and <sample>.minus.bw when stranded; needs --sam-header FILE whose "
+                         "@SQ SN:/LN: lines give the chromosome sizes (all of them are listed, in byte order)")
     ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "tight", "host"),
                     help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
                          "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
@@ -208,6 +212,8 @@ def parse_args(argv=None):
             ap.error("-sl is bowtie's -l: at least 5")
         if args.ignored_maxl is not None and int(args.ignored_maxl) > 64:
             ap.error("-maxl above 64: the genome scan on the device takes reads of at most 64 nt")
+    if args.coverage_bigwig and not args.coverage:
+        ap.error("--coverage-bigwig requires --coverage")
     if args.sam_header and not (args.sam_out or args.sorted_bam or args.coverage):
         ap.error("--sam-header requires --sam-out, --sorted-bam or --coverage")
     if args.coverage and (args.save_pkl or args.resume or args.backend == "bowtie"):
@@ -232,6 +238,13 @@ def parse_args(argv=None):
         try:
             with open(args.sam_header, "rb") as fh:
                 parse_sq(fh.read())
+        except ValueError as e:
+            ap.error(str(e))
+    if args.coverage_bigwig:
+        from .bigwig import parse_sizes
+        try:
+            with open(args.sam_header, "rb") if args.sam_header else open(os.devnull, "rb") as fh:
+                parse_sizes(fh.read())
         except ValueError as e:
             ap.error(str(e))
     if args.coverage and args.sam_header:  # (a header without @SQ lines is fine here: byte order)

@@ -225,14 +225,19 @@ def run(args, workDir, base_names, casc, uniq, res, order, tm: Optional[dict] = 
         with open(hfile, "rb") as fh:
             header = fh.read()
     sq_names = sq_order(header)
-    files = {}
+    files, files_bw = {}, {}
     with open(workDir / "run.log", "a+") as log:
         for s, name in enumerate(base_names):
+            if getattr(args, "coverage_bigwig", False):  # first: a data error then leaves no file of this sample
+                from . import bigwig
+                files_bw.update(bigwig.run(args, workDir, base_names, casc, uniq, res, order, tm, sample=s))
             paths = sample_paths(workDir, str(name), stranded)
             st = write_sample(casc, uniq, res, order, s, paths, stranded, args.organism_name, sq_names)
             files[str(name)] = dict(paths=[str(p) for p in paths], **st)
             log.write(f"coverage ({'stranded' if stranded else 'unstranded'}, chromosomes in {'@SQ' if sq_names is not None else 'byte'} order) "
                       f"{name}: {st['intervals']} intervals, summed weight {st['weight']}, {st['lines']} lines, {st['bytes']} bytes\n")
     if tm is not None:
-        tm["coverage_s"] = time.perf_counter() - t0
+        tm["coverage_s"] = time.perf_counter() - t0 - tm.get("coverage_bigwig_s", 0.0)
+    for name, v in files_bw.items():
+        files[name]["bigwig"] = v
     return files

@@ -178,6 +178,87 @@ extern "C" int mirge_coverage_runs(mirge_ctx* c, int64_t n, const int32_t* chrom
     return rc;
 }
 
+// the intervals of one sample's rows from the resident run (SamPrep, the rows of `--sam-out`): what mirge_coverage_write_device and
+// mirge_bigwig_write_device hand to CovDev::runs.  A row on a chromosome without rank or outside [1, 2^31 - 1] fails the call, named.
+struct CovInput {
+    SamPrep prep;
+    int32_t *d_map = nullptr, *d_rank = nullptr, *d_len = nullptr, *d_desc = nullptr;
+    long long* d_start = nullptr;
+    uint32_t *d_w = nullptr, *d_err = nullptr;
+    uint8_t* d_minus = nullptr;
+    size_t n_rows = 0;
+    CovIntervals intervals() const { return CovIntervals{d_rank, d_start, d_len, d_w, d_minus}; }
+    int build(mirge_ctx* c, const std::string& who, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+              const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass, const int32_t* chrom_rank,
+              const int64_t* chrom_rank_off, int32_t n_rank, int64_t* err_out, HostClock& hc) {
+        int rc = 0;
+        if ((rc = prep.build(c, who, U, res, order, sample, class_pass, n_class, passes, n_pass))) return rc;
+        n_rows = prep.n_rows;
+        hc.lap("rows chosen");
+        // ---- every named pass's chromosome index -> global rank
+        CovRankMap rm;
+        std::memset(&rm, 0, sizeof(rm));
+        for (int p = 0; p < n_pass && rc == 0; p++) {
+            const int64_t nn = chrom_rank_off[p + 1] - chrom_rank_off[p];
+            bool named = false;
+            for (int k = 0; k < n_class; k++) named = named || class_pass[k] == p;
+            if (chrom_rank_off[p] < 0 || chrom_rank_off[p] >= 0x7FFFFFF0ll || nn < 0 || (named && nn != passes[p].n_chrom))
+                rc = fail(-1, who + ": the rank table of pass " + std::to_string(p) + " does not fit its chromosomes");
+            for (int64_t k = 0; k < nn && rc == 0; k++)
+                if (chrom_rank[chrom_rank_off[p] + k] >= n_rank) rc = fail(-1, who + ": a chromosome rank beyond the names given");
+            rm.rank_off[p] = (uint32_t)chrom_rank_off[p];
+        }
+        if (rc) return rc;
+        const size_t n_map = (size_t)chrom_rank_off[n_pass];
+        CHECK(dalloc(c, &d_map, std::max<size_t>(n_map, 1)));
+        CHECK(dalloc(c, &d_err, (size_t)2));
+        CHECK(dalloc(c, &d_desc, (size_t)4));
+        const size_t cap = std::max<size_t>(n_rows, 1);
+        CHECK(dalloc(c, &d_rank, cap)); CHECK(dalloc(c, &d_len, cap)); CHECK(dalloc(c, &d_start, cap)); CHECK(dalloc(c, &d_w, cap));
+        CHECK(dalloc(c, &d_minus, cap));
+        rm.rank_of = d_map;
+        uint32_t herr[2] = {MIRGE_COV_NONE, MIRGE_COV_NONE};
+        hipError_t e = hipSuccess;
+        if (n_map) e = hipMemcpyAsync(d_map, chrom_rank, n_map * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_err, 0xFF, 8, c->stream);
+        if (e == hipSuccess && n_rows) {
+            LaunchScope ls(c, "k_cov_intervals", (double)n_rows);
+            hipLaunchKernelGGL(k_cov_intervals, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, prep.t, (const uint32_t*)prep.d_rows, (uint32_t)n_rows, rm,
+                               d_rank, d_start, d_len, d_w, d_minus, d_err);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(herr, d_err, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return fail(-2, who + ": " + hipGetErrorString(e));
+        if (herr[0] != MIRGE_COV_NONE || herr[1] != MIRGE_COV_NONE) {  // name the first offending row of the file
+            const bool range = herr[0] == MIRGE_COV_NONE || (herr[1] != MIRGE_COV_NONE && herr[1] < herr[0]);
+            int32_t d[4] = {0, 0, 0, 0};
+            hipLaunchKernelGGL(k_cov_describe, dim3(1), dim3(64), 0, c->stream, prep.t, (const uint32_t*)prep.d_rows, range ? herr[1] : herr[0], d_desc);
+            e = hipMemcpyAsync(d, d_desc, 16, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) return fail(-2, who + ": " + hipGetErrorString(e));
+            if (err_out) { err_out[0] = range ? 2 : 1; err_out[1] = d[0]; err_out[2] = d[1]; err_out[3] = d[2]; }
+            if (range) {
+                rc = fail(-1, who + ": a read lies outside [1, 2^31 - 1] of its chromosome (unique read " + std::to_string(d[0]) + ", pass " +
+                                  std::to_string(d[1]) + ", reference " + std::to_string(d[2]) + ")");
+            } else {
+                std::string name = "?";
+                if (d[1] >= 0 && d[1] < n_pass && d[3] >= 0 && (int64_t)d[3] < passes[d[1]].n_chrom) {
+                    const mirge_sam_pass& in = passes[d[1]];
+                    name.assign(in.chrom_data + in.chrom_off[d[3]], in.chrom_data + in.chrom_off[d[3] + 1]);
+                }
+                rc = fail(-1, who + ": reads lie on '" + name + "', which no @SQ line of the header names");
+            }
+            return rc;
+        }
+        hc.lap("intervals");
+        return 0;
+    }
+    void release(mirge_ctx* c) {
+        prep.release(c);
+        for (void* p : {(void*)d_map, (void*)d_rank, (void*)d_len, (void*)d_desc, (void*)d_start, (void*)d_w, (void*)d_err, (void*)d_minus}) c->release(p);
+    }
+};
+
 extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
                                            const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
                                            const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
@@ -198,77 +279,18 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
     size_t chunk = sam_env_bytes("MIRGE_COV_CHUNK_BYTES", (size_t)32 << 20);
     chunk = std::min<size_t>((size_t)1 << 30, std::max(chunk, tile)) / tile * tile;
 
-    SamPrep prep;
+    CovInput in;
     CovDev dev;
-    int32_t *d_map = nullptr, *d_rank = nullptr, *d_len = nullptr, *d_desc = nullptr;
-    long long* d_start = nullptr;
-    uint32_t *d_w = nullptr, *d_err = nullptr;
-    uint8_t *d_minus = nullptr, *d_text[2] = {nullptr, nullptr};
+    uint8_t* d_text[2] = {nullptr, nullptr};
     int rc = 0, fd[2] = {-1, -1};
     const char* paths[2] = {path, stranded ? path_minus : nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
     size_t n_rows = 0;
+    hipError_t e = hipSuccess;
     do {
-        if ((rc = prep.build(c, who, U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
-        n_rows = prep.n_rows;
-        hc.lap("rows chosen");
-        // ---- every named pass's chromosome index -> global rank
-        CovRankMap rm;
-        std::memset(&rm, 0, sizeof(rm));
-        for (int p = 0; p < n_pass && rc == 0; p++) {
-            const int64_t nn = chrom_rank_off[p + 1] - chrom_rank_off[p];
-            bool named = false;
-            for (int k = 0; k < n_class; k++) named = named || class_pass[k] == p;
-            if (chrom_rank_off[p] < 0 || chrom_rank_off[p] >= 0x7FFFFFF0ll || nn < 0 || (named && nn != passes[p].n_chrom))
-                rc = fail(-1, who + ": the rank table of pass " + std::to_string(p) + " does not fit its chromosomes");
-            for (int64_t k = 0; k < nn && rc == 0; k++)
-                if (chrom_rank[chrom_rank_off[p] + k] >= n_rank) rc = fail(-1, who + ": a chromosome rank beyond the names given");
-            rm.rank_off[p] = (uint32_t)chrom_rank_off[p];
-        }
-        if (rc) break;
-        const size_t n_map = (size_t)chrom_rank_off[n_pass];
-        if ((rc = dalloc(c, &d_map, std::max<size_t>(n_map, 1)))) break;
-        if ((rc = dalloc(c, &d_err, (size_t)2))) break;
-        if ((rc = dalloc(c, &d_desc, (size_t)4))) break;
-        const size_t cap = std::max<size_t>(n_rows, 1);
-        if ((rc = dalloc(c, &d_rank, cap)) || (rc = dalloc(c, &d_len, cap)) || (rc = dalloc(c, &d_start, cap)) || (rc = dalloc(c, &d_w, cap)) ||
-            (rc = dalloc(c, &d_minus, cap))) break;
-        rm.rank_of = d_map;
-        uint32_t herr[2] = {MIRGE_COV_NONE, MIRGE_COV_NONE};
-        hipError_t e = hipSuccess;
-        if (n_map) e = hipMemcpyAsync(d_map, chrom_rank, n_map * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_err, 0xFF, 8, c->stream);
-        if (e == hipSuccess && n_rows) {
-            LaunchScope ls(c, "k_cov_intervals", (double)n_rows);
-            hipLaunchKernelGGL(k_cov_intervals, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, prep.t, (const uint32_t*)prep.d_rows, (uint32_t)n_rows, rm,
-                               d_rank, d_start, d_len, d_w, d_minus, d_err);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(herr, d_err, 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = fail(-2, who + ": " + hipGetErrorString(e)); break; }
-        if (herr[0] != MIRGE_COV_NONE || herr[1] != MIRGE_COV_NONE) {  // name the first offending row of the file
-            const bool range = herr[0] == MIRGE_COV_NONE || (herr[1] != MIRGE_COV_NONE && herr[1] < herr[0]);
-            int32_t d[4] = {0, 0, 0, 0};
-            hipLaunchKernelGGL(k_cov_describe, dim3(1), dim3(64), 0, c->stream, prep.t, (const uint32_t*)prep.d_rows, range ? herr[1] : herr[0], d_desc);
-            e = hipMemcpyAsync(d, d_desc, 16, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { rc = fail(-2, who + ": " + hipGetErrorString(e)); break; }
-            if (err_out) { err_out[0] = range ? 2 : 1; err_out[1] = d[0]; err_out[2] = d[1]; err_out[3] = d[2]; }
-            if (range) {
-                rc = fail(-1, who + ": a read lies outside [1, 2^31 - 1] of its chromosome (unique read " + std::to_string(d[0]) + ", pass " +
-                                  std::to_string(d[1]) + ", reference " + std::to_string(d[2]) + ")");
-            } else {
-                std::string name = "?";
-                if (d[1] >= 0 && d[1] < n_pass && d[3] >= 0 && (int64_t)d[3] < passes[d[1]].n_chrom) {
-                    const mirge_sam_pass& in = passes[d[1]];
-                    name.assign(in.chrom_data + in.chrom_off[d[3]], in.chrom_data + in.chrom_off[d[3] + 1]);
-                }
-                rc = fail(-1, who + ": reads lie on '" + name + "', which no @SQ line of the header names");
-            }
-            break;
-        }
-        hc.lap("intervals");
-        if ((rc = dev.runs(c, who, CovIntervals{d_rank, d_start, d_len, d_w, d_minus}, n_rows, (uint32_t)std::max(n_rank, 1), stranded != 0))) break;
+        if ((rc = in.build(c, who, U, res, order, sample, class_pass, n_class, passes, n_pass, chrom_rank, chrom_rank_off, n_rank, err_out, hc))) break;
+        n_rows = in.n_rows;
+        if ((rc = dev.runs(c, who, in.intervals(), n_rows, (uint32_t)std::max(n_rank, 1), stranded != 0))) break;
         hc.lap("runs");
         if ((rc = dev.measure(c, rank_names, rank_name_off, (uint32_t)n_rank))) break;
         hc.lap("measured");
@@ -343,10 +365,9 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
     if (rc != 0)  // never a partial file that looks like a result
         for (int f = 0; f < 2; f++) if (fd[f] == -2) (void)::unlink(paths[f]);
     for (auto& x : ev) if (x) c->evt_pool.push_back(x);
-    prep.release(c);
+    in.release(c);
     dev.release(c);
-    for (void* p : {(void*)d_map, (void*)d_rank, (void*)d_len, (void*)d_desc, (void*)d_start, (void*)d_w, (void*)d_err, (void*)d_minus, (void*)d_text[0], (void*)d_text[1]})
-        c->release(p);
+    c->release(d_text[0]); c->release(d_text[1]);
     if (rc == 0) {
         if (n_intervals_out) *n_intervals_out = (int64_t)n_rows;
         if (weight_out) *weight_out = (int64_t)dev.weight;

@@ -323,7 +323,9 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
             raise RuntimeError("--sorted-bam needs the cascade's result on the device (a single-process run)")
         from . import bam_export as _bam_export
         out["sorted_bam"] = _bam_export.run(args, workDir, base_names, casc, uniq, res, order, tm)
-    if getattr(args, "coverage", None):  # --coverage: <sample>.bedgraph, the depth of the same rows per base (and strand)
+    # --coverage: <sample>.bedgraph, the depth of the same rows per base (and strand); with --coverage-bigwig the same runs as
+    # <sample>.bw, per sample BEFORE its bedGraph (bigwig.run, called from coverage.run's loop)
+    if getattr(args, "coverage", None):
         if ann is not None or res is None:
             raise RuntimeError("--coverage needs the cascade's result on the device (a single-process run)")
         from . import coverage as _coverage
