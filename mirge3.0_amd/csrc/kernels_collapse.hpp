@@ -149,9 +149,9 @@ __global__ void k_collapse_init(uint32_t* __restrict__ rep, uint32_t* __restrict
 //                  workgroup's slab -- no capacity to overflow, however many copies of a read there are
 //                                                                               rec2[(b1 * W2 + w) * slab + off[b2] + i]
 //   k_part_dedup : per bucket, LDS table (key -> min j, count) over the bucket's R shares (R = G regions of level 1, or W2
-//                  slab ranges); the bucket's distinct reads are written to the output at a range reserved with one global
-//                  atomicAdd per workgroup (so the order of the unique reads of this path is unspecified; first[]
-//                  carries the first raw index)
+//                  slab ranges); the distinct reads of MIRGE_DEDUP_K buckets are written to the output at a range reserved with
+//                  one global atomicAdd (so the order of the unique reads of this path is unspecified; first[] carries the
+//                  first raw index); a workgroup walks several buckets, their global round trips overlapped (see the kernel)
 // ------------------------------------------------------------------------------------------
 #ifndef MIRGE_PART_CAP
 #define MIRGE_PART_CAP 4096  // largest LDS table per bucket (16 B per slot = 64 KiB)
@@ -410,6 +410,58 @@ k_part_split(const uint4* __restrict__ rec1, const uint32_t* __restrict__ cnt1, 
     }
 }
 
+// ---- k_part_dedup: persistent and software-pipelined over the buckets of a workgroup -------------------------------------------
+// What the kernel used to spend its time on (profiles/README.md round 5, profiles/dedup_pipelined.md): a bucket was a chain of four
+// DEPENDENT global round trips with barriers between them -- the shares' cnt / off words, the records, the returning add on the
+// output cursor, the output stores -- ~12 us per bucket whether it held 150 or 1 000 records, 1 024 buckets resident on the chip,
+// 8 192 buckets: 8 x 12 us.  Not the cursor (8 192 adds in 0.11 ms arrive 13.5 ns apart and are served in 11.6 ns), not the
+// records (1.5 per thread).  Here a workgroup STAYS (grid = the resident workgroups) and walks buckets w, w + grid, w + 2 grid, ...
+// with the round trips of consecutive buckets overlapped:
+//   while bucket i is inserted into the LDS table    the cnt / off words of bucket i + 2 are in flight (lanes 0..7 of every wave,
+//                                                    one register)
+//   behind bucket i's insert                         the first MIRGE_DEDUP_DEPTH records per thread of bucket i + 1 are asked for --
+//                                                    into the registers bucket i's were just taken from: a second set beside K
+//                                                    read-outs does not fit 64 VGPRs -- and are in flight behind the barrier, the
+//                                                    last group's stores, the read-out, the scan and the reservation
+//   behind the barrier                               every thread reads its PER slots out into registers and clears them: the table
+//                                                    is free for bucket i + 1 without waiting for anything global
+//   one reservation per MIRGE_DEDUP_K buckets        the read-outs of K buckets stay in registers, ONE returning add reserves their
+//                                                    output range, and the add is waited for -- and the stores are issued -- BEHIND
+//                                                    the insert of the next bucket
+// No workgroup waits for another one.  The one-level partition (R = G > 4 shares, samples of up to 131 072 reads) walks its
+// buckets in the same loop with the plain chain (prefix and offsets through LDS, a search per record, nothing asked for ahead);
+// its reservations are grouped and its stores deferred in the same way.
+#ifndef MIRGE_DEDUP_K
+#define MIRGE_DEDUP_K 2      // buckets per output reservation (the cursor's floor is 8 192 x 11.6 ns / K per 10 M reads)
+#endif
+#ifndef MIRGE_DEDUP_DEPTH
+#define MIRGE_DEDUP_DEPTH 2  // records per thread that are loaded one bucket ahead (K and DEPTH: <= 64 VGPRs at CAP = 2048, no scratch)
+#endif
+
+// a bucket's (up to four) shares of the two-level partition: inclusive ends of shares 0..2, the total, where each share starts
+// inside its slab, the first slab's record index -- wave-uniform, in scalar registers
+struct DedupShares {
+    uint32_t e0, e1, e2, total, o0, o1, o2, o3;
+    size_t base;
+};
+// lanes 0..3 of every wave hold the count of share `lane`, lanes 4..7 the offset of share `lane - 4` (0 beyond R): ONE register
+__device__ __forceinline__ DedupShares dedup_shares(uint32_t co, uint32_t cap32, size_t base) {
+    DedupShares s;
+    s.e0 = min((uint32_t)__builtin_amdgcn_readlane((int)co, 0), cap32);
+    s.e1 = s.e0 + min((uint32_t)__builtin_amdgcn_readlane((int)co, 1), cap32);
+    s.e2 = s.e1 + min((uint32_t)__builtin_amdgcn_readlane((int)co, 2), cap32);
+    s.total = s.e2 + min((uint32_t)__builtin_amdgcn_readlane((int)co, 3), cap32);
+    s.o0 = (uint32_t)__builtin_amdgcn_readlane((int)co, 4);
+    s.o1 = (uint32_t)__builtin_amdgcn_readlane((int)co, 5);
+    s.o2 = (uint32_t)__builtin_amdgcn_readlane((int)co, 6);
+    s.o3 = (uint32_t)__builtin_amdgcn_readlane((int)co, 7);
+    s.base = base;
+    return s;
+}
+__device__ __forceinline__ size_t dedup_record_at(const DedupShares& s, uint64_t rcap, uint32_t i) {
+    return s.base + (i < s.e0 ? (size_t)s.o0 + i : i < s.e1 ? rcap + s.o1 + (i - s.e0) : i < s.e2 ? 2 * rcap + s.o2 + (i - s.e1) : 3 * rcap + s.o3 + (i - s.e2));
+}
+
 // CAP = LDS table slots (16 B each): 2048 when the buckets hold <= 1024 records (4 workgroups per CU), else 4096
 // The table takes 32-64 KiB of LDS, so only 2-4 workgroups fit a CU: 1024-thread workgroups bring the waves.
 // The bucket's records lie in R shares: share r holds cnt[bucket * R + r] records (clamped to rcap) from
@@ -420,24 +472,28 @@ k_part_split(const uint4* __restrict__ rec1, const uint32_t* __restrict__ cnt1, 
 // leaves room for), their barrier phases overlap: 0.140 -> 0.126 ms per 9.6 M reads (256 threads: 0.132)
 #define MIRGE_DEDUP_THREADS 512
 #endif
-template <int CAP>
-__global__ void __launch_bounds__(MIRGE_DEDUP_THREADS)
+// Grid: the resident workgroups (n_cu x 4 at CAP = 2048, x 2 at 4096), never more than the B buckets; any grid in 1..B is correct.
+// (waves per SIMD: the residency the tables allow -- 4 x 512 threads per CU = 8 waves per SIMD = 64 VGPRs at CAP = 2048, half that at 4096 --
+//  is the register budget the compiler is held to: the persistent grid is sized for exactly that residency)
+// FEW: the bucket's records lie in R <= 4 shares (the two-level partition) -- an instance of its own, or the one-level partition's
+// prefix, search and addresses sit in the pipelined loop's register budget
+template <int CAP, bool FEW>
+__global__ void __launch_bounds__(MIRGE_DEDUP_THREADS) __attribute__((amdgpu_waves_per_eu(CAP <= 2048 ? 8 : 4)))
 k_part_dedup(const uint4* __restrict__ rec, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ off, uint32_t R,
-             uint64_t rcap, uint32_t NB2, uint64_t* __restrict__ useq, uint8_t* __restrict__ ulen,
+             uint64_t rcap, uint32_t NB2, uint32_t B, uint64_t* __restrict__ useq, uint8_t* __restrict__ ulen,
              uint32_t* __restrict__ ucnt, uint32_t* __restrict__ ufirst, uint32_t* __restrict__ cursor,
              uint32_t* __restrict__ hist, uint32_t* __restrict__ overflow, uint32_t* __restrict__ shard_cur_in, uint32_t shard_cap,
              const uint32_t* __restrict__ n_records, uint32_t rec_thresh, uint64_t* __restrict__ sseq, uint8_t* __restrict__ slen, uint32_t* __restrict__ scnt,
              uint32_t* __restrict__ sfirst) {
-    // Output mode, chosen HERE from the sample's record count (*n_records, written by k_part_agg; a line of its own): few records = few unique reads =
-    // the kernel's time is the one global cursor's returning adds (11.6 ns each, one per bucket) -> eight cursors into the staging
-    // arrays (s*), k_part_compact closes the gaps; many records = the kernel's time is its records -> the one cursor, straight into
-    // the output arrays (and k_part_compact returns at once).  Uniform over the launch: every workgroup reads the same word.
-    // (the word is ASKED FOR here and LOOKED AT behind the table's read-out, where the output range is reserved: a workgroup is a
-    // latency chain of ~12 us and eight rounds of them fill the chip -- waiting for this load at the top cost the kernel 13 us)
-    // ... and asked for with a VECTOR load (an address the compiler cannot prove uniform): a scalar load would be waited for at the
-    // kernel's first `s_waitcnt lgkmcnt(0)` -- scalar loads and LDS operations share that counter --, i.e. at the top after all; the
-    // vector load is in flight together with the bucket's first records.
-    // ... by ONE thread of the workgroup (every lane asking was 65 k requests for one address per launch: a hot spot on one L2 channel).
+    constexpr int T = MIRGE_DEDUP_THREADS, PER = CAP / T, K = MIRGE_DEDUP_K, D = MIRGE_DEDUP_DEPTH;
+    static_assert(PER % 4 == 0 && K >= 2 && D >= 1, "a thread reads its slots out with 16-byte LDS operations");
+    // Output mode, chosen HERE from the sample's record count (*n_records, written by k_part_agg; a line of its own): few records =
+    // few unique reads per bucket = short buckets, whose reservations then come faster than one cursor serves them (11.6 ns per
+    // returning add) -> eight cursors into the staging arrays (s*), k_part_compact closes the gaps; many records -> the one cursor,
+    // straight into the output arrays (and k_part_compact returns at once).  Uniform over the launch: every workgroup reads the same
+    // word, ONCE, by ONE thread (every lane asking was 65 k requests for one address per launch: a hot spot on one L2 channel), with a
+    // VECTOR load (an address the compiler cannot prove uniform: a scalar load would be waited for at the kernel's first
+    // `s_waitcnt lgkmcnt(0)` -- scalar loads and LDS operations share that counter), looked at in front of the workgroup's first barrier (the first bucket's share words were asked for with it).
     uint32_t lane_zero = 0u;
     asm volatile("" : "+v"(lane_zero));  // (a zero in a vector register the compiler cannot see through)
     uint32_t n_rec_now = 0u;
@@ -445,57 +501,30 @@ k_part_dedup(const uint4* __restrict__ rec, const uint32_t* __restrict__ cnt, co
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds_k[];  // [CAP] keys, then [CAP] minj, [CAP] cnt
     uint32_t* lds_min = reinterpret_cast<uint32_t*>(lds_k + CAP);
     uint32_t* lds_cnt = lds_min + CAP;
-    uint32_t* lds_x = lds_cnt + CAP;  // [0] distinct keys, [1] output base, [2..17] scan scratch, [32..63] lengths (<= 31 nt)
-    uint32_t* pre = lds_x + 64;       // [MAXREG] inclusive prefix of the regions' fill counts
+    uint32_t* lds_x = lds_cnt + CAP;  // [0] distinct keys, [1] output base, [2..17] scan scratch, [18] the mode, [32..63] lengths (<= 31 nt)
+    uint32_t* pre = lds_x + 64;       // [MAXREG] inclusive prefix of the regions' fill counts (one-level partition)
+    uint32_t* roff = pre + MIRGE_PART_MAXREG;  // where share r starts inside its region
     uint32_t& n_distinct = lds_x[0];
-    {   // clear with 16-byte stores: keys and counts to 0, first indices to ~0 (the table's set-up and read-out are most of
-        // this kernel's LDS instructions: a bucket fills a tenth of its table)
+    {   // clear with 16-byte stores: keys and counts to 0, first indices to ~0.  Once per workgroup: afterwards the read-out clears
         uint4* k4 = reinterpret_cast<uint4*>(lds_k);
-        for (uint32_t i = threadIdx.x; i < CAP / 2; i += blockDim.x) k4[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (uint32_t i = threadIdx.x; i < CAP / 2; i += T) k4[i] = make_uint4(0u, 0u, 0u, 0u);
         uint4* m4 = reinterpret_cast<uint4*>(lds_min);
-        for (uint32_t i = threadIdx.x; i < CAP / 4; i += blockDim.x) m4[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        for (uint32_t i = threadIdx.x; i < CAP / 4; i += T) m4[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
         uint4* c4 = reinterpret_cast<uint4*>(lds_cnt);
-        for (uint32_t i = threadIdx.x; i < CAP / 4; i += blockDim.x) c4[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (uint32_t i = threadIdx.x; i < CAP / 4; i += T) c4[i] = make_uint4(0u, 0u, 0u, 0u);
     }
-    for (uint32_t i = threadIdx.x; i < 32 + 32; i += blockDim.x) lds_x[i] = 0;  // key-path reads are <= 31 nt
-    const uint4* in = rec + (size_t)(off ? blockIdx.x / NB2 : blockIdx.x) * R * rcap;
-    uint32_t* roff = pre + MIRGE_PART_MAXREG;  // where share r starts inside its region / slab
-    // up to four shares (the two-level partition): their bounds in registers, no search through LDS per record
-    const bool few = R <= 4;
+    for (uint32_t i = threadIdx.x; i < 32 + 32; i += T)
+        if (i != 18) lds_x[i] = 0;  // key-path reads are <= 31 nt; [18] is thread 0's to write in front of the first barrier
     const uint32_t cap32 = (uint32_t)min(rcap, (uint64_t)0xFFFFFFFFu);
-    uint32_t total_in, e0, e1, e2;
-    if (few) {
-        // (round 5) the shares' counts and offsets are loaded TOGETHER, one barrier, and every thread adds the four counts up itself
-        // instead of region_prefix's serial pass and second barrier.  Measured: 0.125 -> 0.123 ms -- a bucket costs ~12 us whatever
-        // it holds (0.11 ms per 8192 buckets on a sample with 3 % unique reads as on one with 42 %; the waves wait 70 % of their
-        // cycles), but this round trip was not what they wait for.  Kept for the barrier it saves.
-        if (threadIdx.x < R) {
-            pre[threadIdx.x] = min(cnt[(size_t)blockIdx.x * R + threadIdx.x], cap32);
-            roff[threadIdx.x] = off ? off[(size_t)blockIdx.x * R + threadIdx.x] : 0u;
-        }
-        __syncthreads();  // (covers the clears too)
-        e0 = pre[0]; e1 = e0 + (R > 1 ? pre[1] : 0u); e2 = e1 + (R > 2 ? pre[2] : 0u);
-        total_in = e2 + (R > 3 ? pre[3] : 0u);
-    } else {
-        total_in = region_prefix(cnt + (size_t)blockIdx.x * R, R, cap32, pre);  // (its barriers cover the clears)
-        for (uint32_t r = threadIdx.x; r < R; r += blockDim.x) roff[r] = off ? off[(size_t)blockIdx.x * R + r] : 0u;
-        __syncthreads();
-        e0 = pre[0]; e1 = R > 1 ? pre[1] : e0; e2 = R > 2 ? pre[2] : e1;
-    }
-    // a bucket with fewer records than the table has slots cannot fill it: the distinct-key counter (one LDS atomic on a
-    // single address per new key, serialised over the lanes) is kept for the oversized buckets only
-    const bool counted = total_in >= (uint32_t)(CAP - 64);
-    const uint32_t o0 = roff[0], o1 = R > 1 ? roff[1] : 0u, o2 = R > 2 ? roff[2] : 0u, o3 = R > 3 ? roff[3] : 0u;
-    for (uint32_t i = threadIdx.x; i < total_in; i += blockDim.x) {
-        size_t at;
-        if (few) {
-            at = i < e0 ? (size_t)o0 + i : i < e1 ? rcap + o1 + (i - e0) : i < e2 ? 2 * rcap + o2 + (i - e1) : 3 * rcap + o3 + (i - e2);
-        } else {
-            uint32_t k;
-            const uint32_t r = region_of(pre, R, i, k);
-            at = (size_t)r * rcap + roff[r] + k;
-        }
-        const uint4 rc = in[at];
+    const uint32_t grid = gridDim.x;
+    // the thread's index as the bucket loop sees it: made opaque once per trip (below), or the compiler hoists every predicate
+    // of it (the scan's lane masks, `tid == 0`, `lane < R`, ...) out of the loop as scalar register pairs and then spills them
+    uint32_t tid = threadIdx.x;
+
+    // one record into the table (a record stands for rc.w identical reads of one k_part_agg chunk).  `counted`: a bucket with fewer
+    // records than the table has slots cannot fill it: the distinct-key counter (one LDS atomic on a single address per new key,
+    // serialised over the lanes) is kept for the oversized buckets only
+    auto insert = [&](const uint4 rc, const bool counted) {
         const unsigned long long key = ((unsigned long long)rc.y << 32) | rc.x;
         const uint32_t j = rc.z;
         uint32_t s = (uint32_t)(mirge_mix64(key) >> 7) & (CAP - 1);
@@ -510,55 +539,200 @@ k_part_dedup(const uint4* __restrict__ rec, const uint32_t* __restrict__ cnt, co
             s = (s + 1) & (CAP - 1);
         }
         if (*(volatile uint32_t*)&lds_min[s] > j) atomicMin(&lds_min[s], j);
-        atomicAdd(&lds_cnt[s], rc.w);  // a record stands for rc.w identical reads of one workgroup's chunk
-    }
-    __syncthreads();
-    // emit the bucket's distinct reads: one global cursor add per workgroup reserves their output range
-    constexpr int PER = CAP / MIRGE_DEDUP_THREADS;
-    const uint32_t s0 = threadIdx.x * PER;
-    uint32_t mine = 0;
+        atomicAdd(&lds_cnt[s], rc.w);
+    };
+    // the read-out of a bucket: a thread's PER slots, in registers (PER x 4 dwords), and the table cleared behind them
+    struct ReadOut {
+        unsigned long long key[PER];
+        uint32_t mn[PER], ct[PER];
+    };
+    ReadOut ro[K];
+    static_assert(K * 16 <= 32 && CAP <= 65536, "a thread's K ranks share one register");
+    uint32_t ranks = 0u, tot[K];  // a thread's rank among its bucket's distinct keys (16 bits each, ro[q]'s at 16 q); the bucket's distinct keys
+    auto read_out = [&](ReadOut& o, uint32_t& rk, uint32_t& total) {
+        const uint32_t s0 = tid * PER;
+        uint32_t mine = 0, zero = 0u;
+        asm volatile("" : "+v"(zero));  // (made HERE: the compiler kept eight registers of 0 and ~0 for these stores across the whole loop)
+        const uint32_t ones = ~zero;
 #pragma unroll
-    for (int i = 0; i < PER; i++) mine += lds_k[s0 + i] != 0ull;
-    uint32_t total;
-    uint32_t rank = block_excl_scan<MIRGE_DEDUP_THREADS / 64>(mine, total, lds_x + 2);
-    uint32_t* const shard_cur = (shard_cur_in && n_rec_now < rec_thresh) ? shard_cur_in : nullptr;  // (thread 0's: it reserves the range)
-    // Where the bucket's unique reads go.  One global cursor for all buckets (shard_cur == nullptr) is a returning add on ONE
-    // address per bucket, and such adds are served one after the other, 11.6 ns each: 8192 buckets = 0.095 of this kernel's
-    // 0.116 ms whatever they hold (profiles/README.md, round 5).  With shards, bucket b adds to cursor b mod MIRGE_DEDUP_SHARDS
-    // (each on a line and channel of its own) and writes into that shard's stretch of a staging area; k_part_compact closes
-    // the gaps between the stretches afterwards.
-    if (threadIdx.x == 0) {
-        uint32_t at = 0;
-        if (total) {
-            if (shard_cur) {
-                const uint32_t x = blockIdx.x % MIRGE_DEDUP_SHARDS;
-                const uint32_t o = atomicAdd(&shard_cur[x * MIRGE_DEDUP_SHARD_STRIDE], total);
-                if (o + total > shard_cap) { atomicOr(overflow, 1u); at = 0xFFFFFFFFu; }  // (no room: nothing is written, the call is redone)
-                else at = x * shard_cap + o;
-            } else at = atomicAdd(cursor, total);
+        for (int p = 0; p < PER; p += 2) {
+            ulonglong2* at = reinterpret_cast<ulonglong2*>(&lds_k[s0 + p]);
+            const ulonglong2 k2 = *at;
+            *at = make_ulonglong2((unsigned long long)zero, (unsigned long long)zero);
+            o.key[p] = k2.x; o.key[p + 1] = k2.y;
+            mine += (k2.x != 0ull) + (k2.y != 0ull);
         }
-        lds_x[1] = at;
-        lds_x[18] = shard_cur ? 1u : 0u;  // (the mode, for the other threads: [2..17] is the scan's scratch, [32..63] the lengths)
-    }
-    __syncthreads();
-    if (lds_x[1] == 0xFFFFFFFFu) return;
-    if (lds_x[18]) { useq = sseq; ulen = slen; ucnt = scnt; ufirst = sfirst; }
-    rank += lds_x[1];
 #pragma unroll
-    for (int i = 0; i < PER; i++) {
-        const unsigned long long key = lds_k[s0 + i];
-        if (key == 0ull) continue;
-        const int L = (63 - __clzll((long long)key)) >> 1;  // the sentinel bit sits at 2*len
-        useq[rank] = key ^ (1ull << (2 * L));
-        ulen[rank] = (uint8_t)L;
-        ucnt[rank] = lds_cnt[s0 + i];
-        ufirst[rank] = lds_min[s0 + i];
-        if (hist) atomicAdd(&lds_x[32 + L], 1u);
-        rank++;
+        for (int p = 0; p < PER; p += 4) {
+            uint4* am = reinterpret_cast<uint4*>(&lds_min[s0 + p]);
+            uint4* ac = reinterpret_cast<uint4*>(&lds_cnt[s0 + p]);
+            const uint4 m = *am, c = *ac;
+            *am = make_uint4(ones, ones, ones, ones);
+            *ac = make_uint4(zero, zero, zero, zero);
+            o.mn[p] = m.x; o.mn[p + 1] = m.y; o.mn[p + 2] = m.z; o.mn[p + 3] = m.w;
+            o.ct[p] = c.x; o.ct[p + 1] = c.y; o.ct[p + 2] = c.z; o.ct[p + 3] = c.w;
+        }
+        if (tid == 0) n_distinct = 0u;
+        // (the scan's barriers stand between these clears and the next bucket's inserts)
+        rk = block_excl_scan<T / 64>(mine, total, lds_x + 2, tid);
+        total = (uint32_t)__builtin_amdgcn_readfirstlane((int)total);
+    };
+    // Where a group of buckets' unique reads go: one thread reserves their range with ONE returning add -- on the one global cursor
+    // (served one after the other, 11.6 ns each: 8 192 / K adds per 10 M reads), or, with shards, on cursor x (each on a line and
+    // channel of its own) for a range in that shard's stretch of the staging area; k_part_compact closes the gaps between the
+    // stretches afterwards.  The add is ISSUED here and its answer LOOKED AT in publish_base, one insert later.
+    const uint32_t* shard_cur = nullptr;  // (shard_cur_in or nullptr, the same in every thread: set by take_mode)
+    // (by thread 8, into `res_o`: a lane of the register in which lanes 0..7 of every wave keep the next shares in flight -- a
+    //  register of its own for one thread's answer did not fit 64 VGPRs)
+    uint32_t res_total = 0u, res_x = 0u, n_groups = 0u;
+    auto reserve = [&](uint32_t& res_o, uint32_t total) {
+        res_total = total;
+        res_x = (blockIdx.x + n_groups++) % MIRGE_DEDUP_SHARDS;
+        if (tid == 8 && total) res_o = shard_cur ? atomicAdd(&shard_cur_in[res_x * MIRGE_DEDUP_SHARD_STRIDE], total) : atomicAdd(cursor, total);
+    };
+    auto publish_base = [&](uint32_t res_o) {  // (a barrier follows)
+        if (tid == 8) {
+            uint32_t at = 0;
+            if (res_total) {
+                if (shard_cur) {
+                    if (res_o + res_total > shard_cap) { atomicOr(overflow, 1u); at = 0xFFFFFFFFu; }  // (no room: nothing is written, the call is redone)
+                    else at = res_x * shard_cap + res_o;
+                } else at = res_o;
+            }
+            lds_x[1] = at;
+        }
+    };
+    // the mode, for the other threads: thread 0 writes it in front of the workgroup's first barrier, everyone reads it behind it and
+    // takes the staging arrays for the output arrays from there on
+    auto publish_mode = [&]() { if (tid == 0) lds_x[18] = (shard_cur_in && n_rec_now < rec_thresh) ? 1u : 0u; };
+    auto take_mode = [&]() {
+        if (__builtin_amdgcn_readfirstlane((int)lds_x[18])) { shard_cur = shard_cur_in; useq = sseq; ulen = slen; ucnt = scnt; ufirst = sfirst; }
+    };
+    auto emit = [&](const ReadOut& o, uint32_t r) {  // r: where this thread's first distinct key goes
+#pragma unroll
+        for (int p = 0; p < PER; p++) {
+            const unsigned long long key = o.key[p];
+            if (key == 0ull) continue;
+            const int L = (63 - __clzll((long long)key)) >> 1;  // the sentinel bit sits at 2*len
+            useq[r] = key ^ (1ull << (2 * L));
+            ulen[r] = (uint8_t)L;
+            ucnt[r] = o.ct[p];
+            ufirst[r] = o.mn[p];
+            if (hist) atomicAdd(&lds_x[32 + L], 1u);
+            r++;
+        }
+    };
+    auto emit_group = [&](uint32_t n) {  // the last n read-outs (the newest is ro[K - 1]), back to back from the published base
+        const uint32_t at = lds_x[1];
+        if (at == 0xFFFFFFFFu) return;
+        uint32_t run = at;
+#pragma unroll
+        for (int q = 0; q < K; q++)
+            if ((uint32_t)(K - q) <= n) { emit(ro[q], run + ((ranks >> (16 * q)) & 0xFFFFu)); run += tot[q]; }
+    };
+
+    // ---- the bucket loop.  FEW (R <= 4 shares per bucket, the two-level partition: every sample above 131 072 reads): the pipeline of
+    // the header; otherwise the one-level partition's plain chain in the same loop ----
+    constexpr bool few = FEW;
+    const uint32_t m = (B - blockIdx.x + grid - 1) / grid;  // this workgroup's buckets: blockIdx.x + i * grid, i < m
+    const uint32_t nb2_lg = off ? (uint32_t)__builtin_ctz(NB2) : 0u;  // (B and the level-1 bins are powers of two)
+    auto bucket_base = [&](uint32_t i) { return (size_t)((blockIdx.x + i * grid) >> nb2_lg) * R * rcap; };
+    // lanes 0..7 of every wave: the shares' counts and offsets.  Held across a bucket only while they are in flight (nco: the
+    // bucket after the next); of the next bucket the record count alone is kept, in a scalar register -- a bucket with more
+    // records than were asked for ahead asks for its shares again (the L2 has them)
+    auto ask_shares = [&](uint32_t i, uint32_t& co) {  // (lanes 0..7 only: thread 8 keeps its reservation in the same register)
+        const uint32_t lane = tid & 63u, r = lane & 3u;
+        if (lane < 8u) {
+            co = 0u;
+            if (few && i < m && r < R && (lane < 4u || off)) {
+                const size_t cell = (size_t)(blockIdx.x + i * grid) * R + r;
+                co = (lane < 4u ? cnt : off)[cell];
+            }
+        }
+    };
+    uint4 pf[D];  // the first D records per thread of the next bucket, in flight
+    auto ask_records = [&](uint32_t i, uint32_t co) {  // returns the bucket's records
+        const DedupShares s = dedup_shares(co, cap32, bucket_base(i));
+#pragma unroll
+        for (int u = 0; u < D; u++) {
+            const uint32_t j = tid + u * T;
+            if (j < s.total) pf[u] = rec[dedup_record_at(s, rcap, j)];
+        }
+        return s.total;
+    };
+    uint32_t nco = 0u;  // lanes 0..7 of every wave: shares in flight; thread 8: the answer of the returning add in flight (res_o)
+    ask_shares(0, nco);
+    uint32_t total_next = ask_records(0, nco);  // (no share, no record: the one-level partition)
+    ask_shares(1, nco);
+    publish_mode();
+    __syncthreads();  // the clears, the mode
+    take_mode();
+    uint32_t pend = 0u;            // buckets of the group whose range is reserved and whose read-outs wait in ro[]
+    uint32_t held = 0u, gsum = 0u;  // buckets read out for the group that is being collected, their distinct keys
+    // ONE loop for both partitions, and one more trip than the workgroup has buckets: the last group's stores
+    for (uint32_t i = 0; i <= m; i++) {
+        asm volatile("" : "+v"(tid));
+        if (i < m) {
+            uint32_t total_in = total_next;
+            if (!few) {
+                // the one-level partition (R = G > 4 regions per bucket, at most 64 buckets): prefix and offsets through LDS, a search
+                // per record, nothing asked for ahead
+                const uint32_t b = blockIdx.x + i * grid;
+                for (uint32_t r = tid; r < R; r += T) {
+                    pre[r] = min(cnt[(size_t)b * R + r], cap32);
+                    roff[r] = off ? off[(size_t)b * R + r] : 0u;
+                }
+                __syncthreads();
+                if (tid == 0) {  // (as region_prefix: R <= 256, a serial pass over LDS costs less than the barriers of a block scan)
+                    uint32_t run = 0;
+                    for (uint32_t r = 0; r < R; r++) { run += pre[r]; pre[r] = run; }
+                }
+                __syncthreads();
+                total_in = (uint32_t)__builtin_amdgcn_readfirstlane((int)pre[R - 1]);
+            }
+            const bool counted = total_in >= (uint32_t)(CAP - 64);
+            uint32_t co = 0u, u = 0;
+            if (total_in > (uint32_t)(D * T)) ask_shares(i, co);  // (more records than were asked for ahead)
+            for (uint32_t j = tid; j < total_in; j += T, u++) {
+                uint4 rc;
+                if (few && u < (uint32_t)D) {
+                    // asked for one bucket ago (consumed before the next ones are asked for: a second set of these registers would
+                    // not fit 64 VGPRs beside K read-outs)
+                    rc = pf[0];
+#pragma unroll
+                    for (int q = 1; q < D; q++) if (u == (uint32_t)q) rc = pf[q];
+                } else if (few) {
+                    rc = rec[dedup_record_at(dedup_shares(co, cap32, bucket_base(i)), rcap, j)];
+                } else {
+                    uint32_t k;
+                    const uint32_t r = region_of(pre, R, j, k);
+                    rc = rec[bucket_base(i) + (size_t)r * rcap + roff[r] + k];
+                }
+                insert(rc, counted);
+            }
+            // bucket i + 1's shares have arrived (asked for one bucket ago): ask for its first records, and for bucket i + 2's
+            // shares; both are in flight behind this bucket's barrier, read-out, scan and reservation and the last group's stores
+            total_next = ask_records(i + 1, nco);
+            ask_shares(i + 2, nco);
+        }
+        // the group reserved one bucket ago: its add has had an insert's time to come back
+        if (pend) publish_base(nco);
+        __syncthreads();
+        if (pend) { emit_group(pend); pend = 0u; }
+        if (i < m) {
+#pragma unroll
+            for (int q = 0; q + 1 < K; q++) { ro[q] = ro[q + 1]; tot[q] = tot[q + 1]; }
+            uint32_t rk;
+            read_out(ro[K - 1], rk, tot[K - 1]);
+            ranks = (ranks >> 16) | (rk << (16 * (K - 1)));
+            gsum += tot[K - 1];
+            if (++held == (uint32_t)K || i == m - 1) { reserve(nco, gsum); pend = held; held = 0u; gsum = 0u; }
+        }
     }
     if (!hist) return;  // (the histogram comes from k_len_hist on the side stream: see there)
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < 32; i += blockDim.x)
+    asm volatile("" : "+v"(tid));  // (or the prologue's addresses are kept for this across the loop)
+    for (uint32_t i = tid; i < 32; i += T)
         if (lds_x[32 + i]) atomicAdd(&hist[i], lds_x[32 + i]);
 }
 

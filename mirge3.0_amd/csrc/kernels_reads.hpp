@@ -175,8 +175,8 @@ __global__ void k_table_bits(const uint32_t* __restrict__ bucket, uint64_t nb, u
 // block-wide exclusive scan of one value per thread (256 threads = 4 waves of 64)
 // ------------------------------------------------------------------------------------------
 template <int NW = MIRGE_BLOCK / 64>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* lds4) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* lds4, uint32_t tid = threadIdx.x) {
+    const int lane = tid & 63, wv = tid >> 6;  // (tid: the caller's copy of threadIdx.x, where it keeps one the compiler cannot see through)
     uint32_t inc = v;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {

@@ -68,7 +68,7 @@ static void part_len_hist(mirge_ctx* c, const ReadGroup& out, const CollapseTmp&
 
 // partitioned key path after k_part_agg.  `part` 1: the second radix level (k_part_split is one workgroup per CU like
 // k_part_agg: the small groups' kernels, enqueued while these run, find room beside them); 2: the per-bucket
-// de-duplication (8192 workgroups: takes the machine); 0: both.  The main queue used to idle ~0.1 ms behind
+// de-duplication (a persistent grid of every workgroup the chip holds: takes the machine); 0: both.  The main queue used to idle ~0.1 ms behind
 // k_part_agg while the host enqueued the small groups' launches (profiles/r02_timeline.txt).
 static int collapse_part_rest(mirge_ctx* c, int gi, const ReadGroup& in, ReadGroup& out, CollapseTmp& t, uint32_t* dmeta, int part = 0) {
     const bool two = t.NB2 > 1;
@@ -89,15 +89,25 @@ static int collapse_part_rest(mirge_ctx* c, int gi, const ReadGroup& in, ReadGro
         const bool sh = t.shard_cur != nullptr;
         uint64_t* const oseq = reinterpret_cast<uint64_t*>(out.seq);
         uint8_t* const olen = reinterpret_cast<uint8_t*>(out.len);
-        if (t.cap == 2048)
-            hipLaunchKernelGGL(k_part_dedup<2048>, dim3(t.B), dim3(MIRGE_DEDUP_THREADS), 2048 * 16 + 4096, c->cur, rec, cnt, off, R, rcap, t.NB2,
-                               oseq, olen, out.counts, out.first, dmeta + gi, (uint32_t*)nullptr, dmeta + MIRGE_META_OVERFLOW, t.shard_cur, t.shard_cap,
+        // a persistent kernel: the grid is the workgroups a CU holds at once (four 36 KiB tables, or two 68 KiB ones, and 2048 threads)
+        // times the CUs, and never more than the buckets; workgroup w walks buckets w, w + grid, ...  MIRGE_DEDUP_GRID caps the grid
+        // (tests: 1 = one workgroup walks every bucket; sweeps)
+        static const uint32_t grid_env = std::getenv("MIRGE_DEDUP_GRID") ? (uint32_t)std::max(1, std::atoi(std::getenv("MIRGE_DEDUP_GRID"))) : 0u;
+        uint32_t grid = std::min<uint32_t>(t.B, (uint32_t)c->n_cu * (t.cap == 2048 ? 4u : 2u));
+        if (grid_env) grid = std::min(grid, grid_env);
+        auto launch = [&](auto kern, unsigned lds) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(MIRGE_DEDUP_THREADS), lds, c->cur, rec, cnt, off, R, rcap, t.NB2, t.B, oseq, olen, out.counts,
+                               out.first, dmeta + gi, (uint32_t*)nullptr, dmeta + MIRGE_META_OVERFLOW, t.shard_cur, t.shard_cap,
                                (const uint32_t*)(dmeta + MIRGE_META_RECORDS), t.rec_thresh, t.s_seq, t.s_len, t.s_cnt, t.s_first);
-        else
-            hipLaunchKernelGGL(k_part_dedup<MIRGE_PART_CAP>, dim3(t.B), dim3(MIRGE_DEDUP_THREADS), MIRGE_PART_CAP * 16 + 4096, c->cur, rec,
-                               cnt, off, R, rcap, t.NB2, oseq, olen, out.counts, out.first, dmeta + gi, (uint32_t*)nullptr,
-                               dmeta + MIRGE_META_OVERFLOW, t.shard_cur, t.shard_cap, (const uint32_t*)(dmeta + MIRGE_META_RECORDS), t.rec_thresh,
-                               t.s_seq, t.s_len, t.s_cnt, t.s_first);
+        };
+        // <CAP, FEW>: up to four shares per bucket (the two-level partition) take the pipelined instance
+        if (t.cap == 2048) {
+            if (R <= 4) launch(k_part_dedup<2048, true>, 2048 * 16 + 4096);
+            else launch(k_part_dedup<2048, false>, 2048 * 16 + 4096);
+        } else {
+            if (R <= 4) launch(k_part_dedup<MIRGE_PART_CAP, true>, MIRGE_PART_CAP * 16 + 4096);
+            else launch(k_part_dedup<MIRGE_PART_CAP, false>, MIRGE_PART_CAP * 16 + 4096);
+        }
         if (sh) {
             LaunchScope ls2(c, "k_part_compact.w1", in.n);
             hipLaunchKernelGGL(k_part_compact, dim3((unsigned)c->n_cu * 8), dim3(256), 0, c->cur, (const uint32_t*)t.shard_cur, t.shard_cap,
@@ -163,7 +173,9 @@ static int collapse_phase_a(mirge_ctx* c, int gi, const ReadGroup& in, ReadGroup
             if (std::find(attr_done.begin(), attr_done.end(), c->device) == attr_done.end()) {
                 HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_part_agg), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           1024 * 16 + 256 * 4 + 32768 * 4 + 64));  // CS = 1024 at B = 32768; 2048 * 16 + 16384 * 4 is smaller
-                HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_part_dedup<MIRGE_PART_CAP>),
+                HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_part_dedup<MIRGE_PART_CAP, true>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, MIRGE_PART_CAP * 16 + 4096));
+                HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_part_dedup<MIRGE_PART_CAP, false>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, MIRGE_PART_CAP * 16 + 4096));
                 attr_done.push_back(c->device);
             }
@@ -190,8 +202,10 @@ static int collapse_phase_a(mirge_ctx* c, int gi, const ReadGroup& in, ReadGroup
         CHECK(dalloc(c, &t.cnt1, (size_t)NB1 * G));
         // sharded output of k_part_dedup (the first attempt only): a shard's stretch holds an eighth of the reads plus an eighth of
         // that and 64 k -- a hash that fills it sets the overflow flag.  Measured (round 5, interleaved): a sample with 3 % unique reads
-        // 0.529 -> 0.488 ms per step (the kernel 0.103 -> 0.066 + 0.008 for k_part_compact: it was waiting for the one cursor), the
-        // default draw with 42 % unique reads 1.184 -> 1.190 (0.116 -> 0.123 + 0.028: there the kernel's time is its records).  So:
+        // 0.529 -> 0.488 ms per step (the kernel 0.103 -> 0.066 + 0.008 for k_part_compact: its short buckets reserve faster than one cursor
+        // serves, 11.6 ns per add), the default draw with 42 % unique reads 1.184 -> 1.190 (0.116 -> 0.123 + 0.028: there the adds arrive
+        // 13.5 ns apart and the cursor did not bind -- the time was each bucket's chain of dependent round trips, which k_part_dedup now
+        // overlaps across the buckets of a persistent workgroup; with one add per MIRGE_DEDUP_K buckets the cursor still does not bind).  So:
         // when the context's previous collapse found under a fifth of its reads unique -- the samples of a batch are alike; the
         // first one takes the cursor.  MIRGE_DEDUP_SHARDED=1 / 0: always / never (tests, A/B).
         // Round 6: the choice is made ON THE DEVICE, per sample, from the record count k_part_agg leaves behind the overflow flag --
