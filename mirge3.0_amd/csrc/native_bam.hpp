@@ -3,7 +3,7 @@
 // native_sam.hpp), measured and keyed (k_bam_measure), radix-sorted by (refID, pos, reverse) -- an LSD sort is stable, so ties keep the
 // .sam file's row order --, one 64-bit scan of the sorted rows' bytes, then the BGZF blocks chunk by chunk: k_bam_blocks builds and
 // deflates every block of a chunk in LDS, a scan of the members' sizes and k_bam_compact close the gaps, the compressed chunk is
-// copied to one of two page-locked halves and put into the file with positioned writes while the next chunk is being encoded.  The
+// copied to one of two page-locked halves and put into the file while the next chunk is being encoded (StagePipe, native_stage.hpp).  The
 // uncompressed stream never exists whole, neither on the device nor on the host.  The index is built per ROW on the host from the
 // sorted rows' stream offsets and the members' file offsets.
 // MIRGE_BAM_BLOCK_BYTES (64 .. 65280, default 65280): uncompressed bytes per BGZF block; MIRGE_BAM_CHUNK_BLOCKS: blocks per chunk
@@ -14,16 +14,6 @@
 #pragma once
 
 static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-static int bam_pwrite_all(int fd, const uint8_t* src, size_t n, unsigned long long at, const char* path) {
-    size_t done = 0;
-    while (done < n) {
-        const ssize_t wr = ::pwrite(fd, src + done, n - done, (off_t)(at + done));
-        if (wr <= 0) return fail(-8, std::string("mirge_bam_write_device: write error on ") + path);
-        done += (size_t)wr;
-    }
-    return 0;
-}
 
 // one block as a BGZF member through zlib (level 6, raw deflate); a block zlib cannot shrink is stored by zlib itself
 static int bam_host_member(const uint8_t* src, uint32_t n, std::vector<uint8_t>& out) {
@@ -103,8 +93,8 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
         return fail(-1, "mirge_bam_write_device: bad argument");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     HostClock hc("bam_write_device");
-    const uint32_t block = (uint32_t)std::min<size_t>(MIRGE_BAM_MAX_BLOCK, std::max<size_t>(64, sam_env_bytes("MIRGE_BAM_BLOCK_BYTES", MIRGE_BAM_MAX_BLOCK)));
-    const size_t chunk_blocks = std::max<size_t>(1, std::min<size_t>(sam_env_bytes("MIRGE_BAM_CHUNK_BLOCKS", std::max<size_t>(1, ((size_t)64 << 20) / block)), (size_t)1 << 20));
+    const uint32_t block = (uint32_t)std::min<size_t>(MIRGE_BAM_MAX_BLOCK, std::max<size_t>(64, env_bytes("MIRGE_BAM_BLOCK_BYTES", MIRGE_BAM_MAX_BLOCK)));
+    const size_t chunk_blocks = std::max<size_t>(1, std::min<size_t>(env_bytes("MIRGE_BAM_CHUNK_BLOCKS", std::max<size_t>(1, ((size_t)64 << 20) / block)), (size_t)1 << 20));
     const char* dv = std::getenv("MIRGE_BAM_DEFLATE");
     const bool on_host = dv && std::strcmp(dv, "host") == 0, dynamic = dv && std::strcmp(dv, "dynamic") == 0, tight = dv && std::strcmp(dv, "tight") == 0;
     if (dv && *dv && !on_host && !dynamic && !tight && std::strcmp(dv, "device") != 0)
@@ -122,10 +112,10 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     int32_t* d_refid = nullptr;
     uint8_t *d_header = nullptr, *d_slots = nullptr, *d_comp[2] = {nullptr, nullptr};
     void* tmp2 = nullptr;
-    int rc = 0, fd = -1;
+    int rc = 0;
     int64_t n_records = 0, n_file = 0;
     unsigned long long body = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    OutFile bam("mirge_bam_write_device"), bai("mirge_bam_write_device");  // (both or neither: commit_all)
     do {
         if ((rc = prep.build(c, "mirge_bam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
         const SamTables& t = prep.t;
@@ -223,16 +213,9 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
         const size_t cb = (size_t)std::min<unsigned long long>(chunk_blocks, n_blocks);
         const size_t half = cb * slot_stride, meta = ((cb + 1) * 4 + 15) & ~size_t(15);
         std::vector<unsigned long long> coff((size_t)n_blocks + 1, 0ull);
-        fd = ::open(bam_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) { rc = fail(-8, std::string("cannot write ") + bam_path); break; }
-        if (2 * (half + meta) > c->sam_pinned_bytes) {  // page-locked staging of two chunks, kept between samples (shared with --sam-out)
-            if (c->sam_pinned) (void)hipHostFree(c->sam_pinned);
-            c->sam_pinned = nullptr; c->sam_pinned_bytes = 0;
-            if (hipHostMalloc((void**)&c->sam_pinned, 2 * (half + meta), hipHostMallocDefault) != hipSuccess) {
-                rc = fail(-3, "mirge_bam_write_device: cannot page-lock " + std::to_string(2 * (half + meta)) + " bytes"); break;
-            }
-            c->sam_pinned_bytes = 2 * (half + meta);
-        }
+        if ((rc = bam.open(bam_path))) break;
+        StagePipe pipe(c, bam.who, "a chunk failed on the device");
+        if ((rc = pipe.ensure(half + meta))) break;
         if (!on_host && (rc = dalloc(c, &d_slots, half + 16))) break;
         if (!on_host && (rc = dalloc(c, &d_sizes, cb + 1))) break;
         size_t tb4 = 0;
@@ -249,17 +232,15 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
             if (tb4 > std::max(std::max(tb2, tb3), (size_t)16)) { c->release(tmp2); tmp2 = nullptr; if ((rc = dalloc(c, (uint8_t**)&tmp2, tb4))) break; }
             tmp4 = tmp2;
         }
-        ev[0] = c->get_evt(); ev[1] = c->get_evt();
         unsigned long long file_at = 0;
         std::vector<std::vector<uint8_t>> members;
         std::vector<uint8_t> joined;
         auto blocks_of = [&](unsigned long long ci) { return (size_t)std::min<unsigned long long>(chunk_blocks, n_blocks - ci * chunk_blocks); };
-        auto put = [&](unsigned long long ci) -> int {  // chunk ci has been queued: fetch it, write it behind what is there
+        auto take = [&](unsigned long long ci) -> int {  // chunk ci's event has passed: fetch it, write it behind what is there
             const int h = (int)(ci & 1);
             const size_t nb = blocks_of(ci);
             const unsigned long long b0 = ci * chunk_blocks;
-            uint8_t* stage = c->sam_pinned + (size_t)h * (half + meta);
-            if (hipEventSynchronize(ev[h]) != hipSuccess) return fail(-2, "mirge_bam_write_device: a chunk failed on the device");
+            uint8_t* stage = pipe.half(ci);
             if (!on_host) {
                 const uint32_t* boff = reinterpret_cast<const uint32_t*>(stage + half);  // exclusive scan of the members' sizes
                 const size_t total = boff[nb];
@@ -267,7 +248,7 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
                 if (hipMemcpyAsync(stage, d_comp[h], total, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
                     return fail(-2, "mirge_bam_write_device: the copy of a chunk failed");
                 for (size_t b = 0; b < nb; b++) coff[(size_t)b0 + b] = file_at + boff[b];
-                if (int r = bam_pwrite_all(fd, stage, total, file_at, bam_path)) return r;
+                if (int r = bam.put(stage, total, file_at)) return r;
                 file_at += total;
                 return 0;
             }
@@ -284,15 +265,15 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
                 coff[(size_t)b0 + b] = file_at + joined.size();
                 joined.insert(joined.end(), members[b].begin(), members[b].end());
             }
-            if (int r = bam_pwrite_all(fd, joined.data(), joined.size(), file_at, bam_path)) return r;
+            if (int r = bam.put(joined.data(), joined.size(), file_at)) return r;
             file_at += joined.size();
             return 0;
         };
-        for (unsigned long long ci = 0; ci < n_chunks && rc == 0; ci++) {
+        auto queue = [&](unsigned long long ci) -> int {
             const int h = (int)(ci & 1);
             const size_t nb = blocks_of(ci);
             const unsigned long long b0 = ci * chunk_blocks;
-            uint8_t* stage = c->sam_pinned + (size_t)h * (half + meta);
+            uint8_t* stage = pipe.half(ci);
             const unsigned grid = (unsigned)std::min<size_t>(nb, (size_t)1 << 20);  // one workgroup per block: the hardware balances them
             {
                 LaunchScope ls(c, "k_bam_blocks", (double)nb * block);
@@ -320,36 +301,22 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
                     e = hipMemcpyAsync(stage + half, d_boff[h], (nb + 1) * 4, hipMemcpyDeviceToHost, c->stream);
                 }
             }
-            if (e == hipSuccess) e = hipEventRecord(ev[h], c->stream);
-            if (e != hipSuccess) { rc = fail(-2, std::string("mirge_bam_write_device: ") + hipGetErrorString(e)); break; }
-            if (ci) rc = put(ci - 1);  // (chunk ci - 1's half of the staging is free again before chunk ci + 1 is queued)
-        }
-        if (rc == 0 && n_chunks) rc = put(n_chunks - 1);
-        if (rc) break;
+            return e == hipSuccess ? 0 : fail(-2, std::string("mirge_bam_write_device: ") + hipGetErrorString(e));
+        };
+        if ((rc = pipe.run(n_chunks, queue, take))) break;
         coff[(size_t)n_blocks] = file_at;
-        if ((rc = bam_pwrite_all(fd, kBgzfEof, sizeof(kBgzfEof), file_at, bam_path))) break;
+        if ((rc = bam.put(kBgzfEof, sizeof(kBgzfEof), file_at))) break;
         file_at += sizeof(kBgzfEof);
         n_records = (int64_t)records; n_file = (int64_t)file_at;
         hc.lap("encoded + written");
         // ---- the index
-        const std::vector<uint8_t> bai = bam_build_index(n_ref, n_rows, h_key.data(), h_span.data(), h_count.data(), h_off.data(), H, block, coff);
-        const int bfd = ::open(bai_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (bfd < 0) { rc = fail(-8, std::string("cannot write ") + bai_path); break; }
-        rc = bam_pwrite_all(bfd, bai.data(), bai.size(), 0, bai_path);
-        if (::close(bfd) != 0 && rc == 0) rc = fail(-8, std::string("mirge_bam_write_device: cannot close ") + bai_path);
-        if (rc) (void)::unlink(bai_path);
+        const std::vector<uint8_t> index = bam_build_index(n_ref, n_rows, h_key.data(), h_span.data(), h_count.data(), h_off.data(), H, block, coff);
+        if ((rc = bai.open(bai_path)) || (rc = bai.put(index.data(), index.size(), 0))) break;
         hc.lap("indexed");
     } while (0);
     (void)hipStreamSynchronize(c->stream);
     c->drain();
-    bool regular = false;
-    if (fd >= 0) {
-        struct stat st;
-        regular = ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-        if (::close(fd) != 0 && rc == 0) rc = fail(-8, std::string("mirge_bam_write_device: cannot close ") + bam_path);
-    }
-    if (rc != 0 && regular) (void)::unlink(bam_path);  // never a partial file that looks like a result
-    for (auto& x : ev) if (x) c->evt_pool.push_back(x);
+    if (rc == 0) rc = commit_all({&bai, &bam});  // (a failed .bai takes the .bam with it: an OutFile that is not committed removes its file)
     prep.release(c);
     c->release(d_key); c->release(d_key2); c->release(d_total); c->release(d_stotal); c->release(d_off); c->release(d_nrec); c->release(d_count);
     c->release(d_fixed); c->release(d_sfixed); c->release(d_srows); c->release(d_perm); c->release(d_perm2); c->release(d_bflags); c->release(d_span);

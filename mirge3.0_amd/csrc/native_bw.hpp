@@ -1,9 +1,9 @@
 // native_bw.hpp -- part of mirge_native.hip (one translation unit, behind native_cov.hpp): `<sample>.bw` of `--coverage-bigwig`
 // (kernels_bw.hpp; the format: mirge3_amd/bigwig.py).  BwJob takes the resident runs of CovDev::runs as they are and writes one file per
 // strand: the run range of every (strand, rank), the zoom levels' counts (which decide how many levels the header names), then the
-// sections and every kept level's blocks, group by group through the page-locked halves `--sam-out` uses, and last the indexes and the
+// sections and every kept level's blocks, group by group through StagePipe (native_stage.hpp), and last the indexes and the
 // front of the file from the sizes and bounds copied back (bw_layout.hpp).  MIRGE_BW_SECTION_ITEMS / MIRGE_BW_ZOOM_BASE /
-// MIRGE_BW_DEFLATE / MIRGE_BW_CHUNK_BYTES are read per call.  Both exports write to `<path>.tmp` and rename when every file is whole.
+// MIRGE_BW_DEFLATE / MIRGE_BW_CHUNK_BYTES are read per call.  Both exports write to `<path>.tmp` (OutFile) and rename when every file is whole.
 #pragma once
 #include "bw_layout.hpp"
 
@@ -23,22 +23,20 @@ struct BwJob {
     BwPart* d_part = nullptr;
     uint8_t *d_slots = nullptr, *d_out[2] = {nullptr, nullptr};
     std::vector<BwRec*> d_recs;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     unsigned long long max_depth[2] = {0, 0};
-    int fd = -1;
-    std::string cur_path;
+    OutFile out[2];  // the strands' files, written as `<path>.tmp`: both are renamed, or neither stays (commit_all)
 
-    BwJob(mirge_ctx* c_, const std::string& w, CovDev& d) : c(c_), who(w), dev(d) {}
+    BwJob(mirge_ctx* c_, const std::string& w, CovDev& d) : c(c_), who(w), dev(d), out{{w, true}, {w, true}} {}
 
     int env() {
-        const size_t s = sam_env_bytes("MIRGE_BW_SECTION_ITEMS", MIRGE_BW_MAX_SECTION), b = sam_env_bytes("MIRGE_BW_ZOOM_BASE", 64);
+        const size_t s = env_bytes("MIRGE_BW_SECTION_ITEMS", MIRGE_BW_MAX_SECTION), b = env_bytes("MIRGE_BW_ZOOM_BASE", 64);
         if (s < 1 || s > MIRGE_BW_MAX_SECTION) return fail(-1, who + ": MIRGE_BW_SECTION_ITEMS takes 1 to 1024");
         if (b < 1 || b > MIRGE_BW_MAX_REDUCTION) return fail(-1, who + ": MIRGE_BW_ZOOM_BASE takes 1 to 2^20");
         S = (uint32_t)s; base = (uint32_t)b;
         const char* m = std::getenv("MIRGE_BW_DEFLATE");
         if (m && *m && std::strcmp(m, "device") != 0 && std::strcmp(m, "none") != 0) return fail(-1, who + ": MIRGE_BW_DEFLATE takes device or none");
         deflate = (m && std::strcmp(m, "none") == 0) ? 0 : 1;
-        chunk = std::min<size_t>((size_t)1 << 30, std::max<size_t>(sam_env_bytes("MIRGE_BW_CHUNK_BYTES", (size_t)32 << 20), 64));
+        chunk = std::min<size_t>((size_t)1 << 30, std::max<size_t>(env_bytes("MIRGE_BW_CHUNK_BYTES", (size_t)32 << 20), 64));
         return 0;
     }
     // names (rank order), sizes and byte-order ids as the caller gives them: ids must be the ranks of the names sorted by bytes
@@ -66,18 +64,8 @@ struct BwJob {
         HIPOK(hipcub::DeviceScan::ExclusiveSum(dev.tmp, tb, d_cnt, d_cnt_off, (int)(n + 1), c->stream));
         return 0;
     }
-    int put(const void* src, size_t nn, uint64_t at) {
-        const uint8_t* p = static_cast<const uint8_t*>(src);
-        size_t done = 0;
-        while (done < nn) {
-            const ssize_t wr = ::pwrite(fd, p + done, nn - done, (off_t)(at + done));
-            if (wr <= 0) return fail(-8, who + ": write error on " + cur_path);
-            done += (size_t)wr;
-        }
-        return 0;
-    }
     // the blocks of `blk` (sections of the runs, or records of `recs`) to the file from `pos` on; placed / pos / largest are updated
-    int stream(bool records, const BwRec* recs, const std::vector<BwBlk>& blk, uint64_t& pos, std::vector<BwPlaced>& placed, uint32_t& largest) {
+    int stream(OutFile& file, bool records, const BwRec* recs, const std::vector<BwBlk>& blk, uint64_t& pos, std::vector<BwPlaced>& placed, uint32_t& largest) {
         const size_t nb = blk.size();
         if (nb == 0) return 0;
         const uint32_t payload = records ? S * 32u : 24u + S * 12u, stride = (payload + 11u + 15u) & ~15u;
@@ -87,13 +75,8 @@ struct BwJob {
         c->release(d_sizes); d_sizes = nullptr; c->release(d_off); d_off = nullptr; c->release(d_bounds); d_bounds = nullptr;
         CHECK(dalloc(c, &d_blk, nb)); CHECK(dalloc(c, &d_slots, buf)); CHECK(dalloc(c, &d_out[0], buf)); CHECK(dalloc(c, &d_out[1], buf));
         CHECK(dalloc(c, &d_sizes, G + 1)); CHECK(dalloc(c, &d_off, G + 1)); CHECK(dalloc(c, &d_bounds, 3 * G));
-        if (2 * buf > c->sam_pinned_bytes) {  // page-locked staging of two groups, kept between samples (shared with --sam-out)
-            if (c->sam_pinned) (void)hipHostFree(c->sam_pinned);
-            c->sam_pinned = nullptr; c->sam_pinned_bytes = 0;
-            if (hipHostMalloc((void**)&c->sam_pinned, 2 * buf, hipHostMallocDefault) != hipSuccess)
-                return fail(-3, who + ": cannot page-lock " + std::to_string(2 * buf) + " bytes");
-            c->sam_pinned_bytes = 2 * buf;
-        }
+        StagePipe pipe(c, who, "the copy of a group of blocks failed");
+        CHECK(pipe.ensure(buf));
         HIPOK(hipMemcpyAsync(d_blk, blk.data(), nb * sizeof(BwBlk), hipMemcpyHostToDevice, c->stream));
         size_t tb = 0;
         HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_sizes, d_off, (int)(G + 1), c->stream));
@@ -101,12 +84,8 @@ struct BwJob {
         std::vector<uint32_t> h_sizes(G), h_bounds(3 * G);
         uint64_t at[2] = {0, 0};
         size_t bytes[2] = {0, 0};
-        auto flush = [&](size_t g) -> int {  // group g has been queued: wait for its copy, write it
-            if (hipEventSynchronize(ev[g & 1]) != hipSuccess) return fail(-2, who + ": the copy of a group of blocks failed");
-            return put(c->sam_pinned + (g & 1) * buf, bytes[g & 1], at[g & 1]);
-        };
-        const size_t n_groups = (nb + G - 1) / G;
-        for (size_t g = 0; g < n_groups; g++) {
+        auto take = [&](unsigned long long g) -> int { return file.put(pipe.half(g), bytes[g & 1], at[g & 1]); };  // group g is in its half
+        auto queue = [&](unsigned long long g) -> int {
             const size_t g0 = g * G, ng = std::min(G, nb - g0);
             HIPOK(hipMemsetAsync(d_sizes + ng, 0, 4, c->stream));
             {
@@ -136,21 +115,19 @@ struct BwJob {
             }
             at[g & 1] = pos; bytes[g & 1] = total;
             pos += total;
-            HIPOK(hipMemcpyAsync(c->sam_pinned + (g & 1) * buf, d_out[g & 1], total, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipEventRecord(ev[g & 1], c->stream));
-            if (g) CHECK(flush(g - 1));  // (group g - 1's half of the staging is free again before group g + 1 is queued)
-        }
-        return flush(n_groups - 1);
+            HIPOK(hipMemcpyAsync(pipe.half(g), d_out[g & 1], total, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        return pipe.run((nb + G - 1) / G, queue, take);
     }
     // blocks of up to S of [lo, hi) on chromId cidx
     void cut(std::vector<BwBlk>& blk, uint64_t lo, uint64_t hi, uint32_t cidx) const {
         for (uint64_t a = lo; a < hi; a += S) blk.push_back(BwBlk{(uint32_t)a, (uint32_t)std::min<uint64_t>(S, hi - a), cidx});
     }
     // file f (strand f of a stranded run) to `path`; stats[0..15] = sections, items, levels, bytes, largest depth, records per level
-    int one_file(int f, const std::string& path, int64_t* stats) {
-        cur_path = path;
-        fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) return fail(-8, "cannot write " + path);
+    int one_file(int f, const char* path, int64_t* stats) {
+        OutFile& file = out[f];
+        CHECK(file.open(path));
         const uint32_t* fr = first.data() + (size_t)f * n_rank;
         const uint32_t r0 = dev.n_runs ? fr[0] : 0, r1 = dev.n_runs ? fr[n_rank] : 0, n = r1 - r0;
         std::vector<BwBlk> secs;
@@ -217,35 +194,35 @@ struct BwJob {
         uint64_t pos = data_at + 8;
         uint32_t largest = 0;
         std::vector<BwPlaced> placed;
-        CHECK(stream(false, nullptr, secs, pos, placed, largest));
+        CHECK(stream(file, false, nullptr, secs, pos, placed, largest));
         BwBytes o;
         o.u64(secs.size());
-        CHECK(put(o.b.data(), 8, data_at));
+        CHECK(file.put(o.b.data(), 8, data_at));
         const uint64_t index_at = pos;
         o.b.clear();
         bw_rtree(placed, index_at, index_at, o);
-        CHECK(put(o.b.data(), o.b.size(), pos));
+        CHECK(file.put(o.b.data(), o.b.size(), pos));
         pos += o.b.size();
         for (size_t k = 0; k < zoom.size(); k++) {
             zoom[k].data_at = pos;
             o.b.clear(); o.u32((uint32_t)zcount[k]);
-            CHECK(put(o.b.data(), 4, pos));
+            CHECK(file.put(o.b.data(), 4, pos));
             pos += 4;
             placed.clear();
-            CHECK(stream(true, d_recs[k], zblk[k], pos, placed, largest));
+            CHECK(stream(file, true, d_recs[k], zblk[k], pos, placed, largest));
             zoom[k].index_at = pos;
             o.b.clear();
             bw_rtree(placed, pos, pos, o);
-            CHECK(put(o.b.data(), o.b.size(), pos));
+            CHECK(file.put(o.b.data(), o.b.size(), pos));
             pos += o.b.size();
         }
         o.b.clear(); o.u32(MIRGE_BW_MAGIC);
-        CHECK(put(o.b.data(), 4, pos));
+        CHECK(file.put(o.b.data(), 4, pos));
         pos += 4;
         o.b.clear();
         bw_front(keys, size_by_cid, zoom, index_at, tot, deflate ? largest : 0u, o);
         if (o.b.size() != data_at) return fail(-3, who + ": the front of the file is not the size it was planned with");
-        CHECK(put(o.b.data(), o.b.size(), 0));
+        CHECK(file.put(o.b.data(), o.b.size(), 0));
         if (stats) {
             stats[0] = (int64_t)secs.size(); stats[1] = (int64_t)n; stats[2] = (int64_t)zoom.size(); stats[3] = (int64_t)pos; stats[4] = (int64_t)max_depth[f];
             for (size_t k = 0; k < zoom.size(); k++) stats[5 + k] = (int64_t)zcount[k];
@@ -260,7 +237,6 @@ struct BwJob {
         CHECK(dalloc(c, &d_ln, (size_t)n_rank)); CHECK(dalloc(c, &d_cid, (size_t)n_rank)); CHECK(dalloc(c, &d_first, nq));
         CHECK(dalloc(c, &d_err, (size_t)1)); CHECK(dalloc(c, &d_max, (size_t)2)); CHECK(dalloc(c, &d_pick, (size_t)n_rank + 1));
         CHECK(dalloc(c, &d_cnt, (size_t)n_runs + 1)); CHECK(dalloc(c, &d_cnt_off, (size_t)n_runs + 1));
-        ev[0] = c->get_evt(); ev[1] = c->get_evt();
         if (n_runs) {
             uint32_t herr = MIRGE_BW_NONE;
             HIPOK(hipMemcpyAsync(d_ln, h_ln.data(), (size_t)n_rank * 4, hipMemcpyHostToDevice, c->stream));
@@ -286,25 +262,15 @@ struct BwJob {
             }
         }
         for (uint32_t f = 0; f < n_str; f++) {
-            const int rc = one_file((int)f, std::string(paths[f]) + ".tmp", stats ? stats + 16 * f : nullptr);
+            const int rc = one_file((int)f, paths[f], stats ? stats + 16 * f : nullptr);
             (void)hipStreamSynchronize(c->stream);
-            if (fd >= 0 && ::close(fd) != 0 && rc == 0) { fd = -1; return fail(-8, who + ": cannot close " + cur_path); }
-            fd = -1;
             if (rc) return rc;
         }
-        for (uint32_t f = 0; f < n_str; f++)
-            if (::rename((std::string(paths[f]) + ".tmp").c_str(), paths[f]) != 0) return fail(-8, who + ": cannot rename to " + paths[f]);
-        return 0;
+        return commit_all({&out[0], &out[1]});  // (renamed only now that every file is whole)
     }
-    // after write(), failed or not: nothing of a failed call stays
-    void release(bool failed, bool stranded, const char* const* paths) {
+    // after write(), failed or not: the device memory goes back; a failed call's files go with the job (OutFile)
+    void release() {
         (void)hipStreamSynchronize(c->stream);
-        if (fd >= 0) { (void)::close(fd); fd = -1; }
-        for (int f = 0; f < (stranded ? 2 : 1); f++) {
-            (void)::unlink((std::string(paths[f]) + ".tmp").c_str());
-            if (failed) (void)::unlink(paths[f]);
-        }
-        for (auto& x : ev) if (x) c->evt_pool.push_back(x);
         for (auto p : d_recs) c->release(p);
         for (void* p : {(void*)d_ln, (void*)d_cid, (void*)d_first, (void*)d_err, (void*)d_sizes, (void*)d_off, (void*)d_bounds, (void*)d_rec_run, (void*)d_rec_bin,
                         (void*)d_max, (void*)d_cnt, (void*)d_cnt_off, (void*)d_pick, (void*)d_blk, (void*)d_part, (void*)d_slots, (void*)d_out[0], (void*)d_out[1]})
@@ -323,10 +289,7 @@ extern "C" int mirge_bigwig_from_intervals(mirge_ctx* c, int64_t n, const int32_
     if (2 * (unsigned long long)n >= 0x7FFFFFF0ull) return fail(-5, who + ": too many intervals for one call (two events each must fit 32-bit indices)");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     const size_t sn = (size_t)n;
-    int32_t *d_rank = nullptr, *d_len = nullptr;
-    long long* d_start = nullptr;
-    uint32_t* d_w = nullptr;
-    uint8_t* d_minus = nullptr;
+    CovUpload up;
     CovDev dev;
     BwJob job(c, who, dev);
     const char* paths[2] = {path, stranded ? path_minus : nullptr};
@@ -334,22 +297,15 @@ extern "C" int mirge_bigwig_from_intervals(mirge_ctx* c, int64_t n, const int32_
         CHECK(job.env());
         CHECK(job.chromosomes(n_rank, rank_names, rank_name_off, chrom_size, chrom_id));
         for (size_t i = 0; i < sn; i++) if (chrom_rank[i] >= n_rank) return fail(-1, who + ": a chromosome rank beyond the names given");
-        if (sn) {
-            CHECK(dalloc(c, &d_rank, sn)); CHECK(dalloc(c, &d_len, sn)); CHECK(dalloc(c, &d_start, sn)); CHECK(dalloc(c, &d_w, sn)); CHECK(dalloc(c, &d_minus, sn));
-            HIPOK(hipMemcpyAsync(d_rank, chrom_rank, sn * 4, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_start, start, sn * 8, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_len, len, sn * 4, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_w, weight, sn * 4, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_minus, minus, sn, hipMemcpyHostToDevice, c->stream));
-        }
-        CHECK(dev.runs(c, who, CovIntervals{d_rank, d_start, d_len, d_w, d_minus}, sn, (uint32_t)n_rank, stranded != 0));
+        CHECK(up.upload(c, sn, chrom_rank, start, len, weight, minus));
+        CHECK(dev.runs(c, who, up.intervals(), sn, (uint32_t)n_rank, stranded != 0));
         return job.write(stranded != 0, paths, stats_out, err_out);
     };
     const int rc = run();
-    job.release(rc != 0, stranded != 0, paths);
+    job.release();
     c->drain();
     dev.release(c);
-    c->release(d_rank); c->release(d_len); c->release(d_start); c->release(d_w); c->release(d_minus);
+    up.release(c);
     return rc;
 }
 
@@ -380,7 +336,7 @@ extern "C" int mirge_bigwig_write_device(mirge_ctx* c, const mirge_reads* U, con
         return 0;
     };
     const int rc = run();
-    job.release(rc != 0, stranded != 0, paths);
+    job.release();
     c->drain();
     in.release(c);
     dev.release(c);

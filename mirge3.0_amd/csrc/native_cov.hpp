@@ -2,7 +2,7 @@
 // everything behind the interval list -- events, radix sort, inclusive sum, three compactions, the runs, their text -- and serves both
 // exports: mirge_coverage_runs (intervals from the host, runs back to the host: tests and other callers) and
 // mirge_coverage_write_device (intervals from the resident run through SamPrep, the rows of `--sam-out`; text to one or two files, chunk
-// by chunk through the page-locked halves `--sam-out` uses).  MIRGE_COV_CHUNK_BYTES / MIRGE_COV_TILE_BYTES (read per call): the chunk
+// by chunk through StagePipe, native_stage.hpp).  CovUpload: the host's intervals on the device.  MIRGE_COV_CHUNK_BYTES / MIRGE_COV_TILE_BYTES (read per call): the chunk
 // and the workgroup's tile; tests make them small so that their boundaries fall inside numbers and names.
 #pragma once
 
@@ -131,6 +131,26 @@ struct CovDev {
     }
 };
 
+// n intervals as the host gives them, on the device: what mirge_coverage_runs and mirge_bigwig_from_intervals hand to CovDev::runs
+struct CovUpload {
+    int32_t *d_rank = nullptr, *d_len = nullptr;
+    long long* d_start = nullptr;
+    uint32_t* d_w = nullptr;
+    uint8_t* d_minus = nullptr;
+    CovIntervals intervals() const { return CovIntervals{d_rank, d_start, d_len, d_w, d_minus}; }
+    int upload(mirge_ctx* c, size_t n, const int32_t* chrom_rank, const int64_t* start, const int32_t* len, const uint32_t* weight, const uint8_t* minus) {
+        if (n == 0) return 0;
+        CHECK(dalloc(c, &d_rank, n)); CHECK(dalloc(c, &d_len, n)); CHECK(dalloc(c, &d_start, n)); CHECK(dalloc(c, &d_w, n)); CHECK(dalloc(c, &d_minus, n));
+        HIPOK(hipMemcpyAsync(d_rank, chrom_rank, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_start, start, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_len, len, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_w, weight, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_minus, minus, n, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }
+    void release(mirge_ctx* c) { c->release(d_rank); c->release(d_len); c->release(d_start); c->release(d_w); c->release(d_minus); }
+};
+
 extern "C" int mirge_coverage_runs(mirge_ctx* c, int64_t n, const int32_t* chrom_rank, const int64_t* start, const int32_t* len, const uint32_t* weight,
                                    const uint8_t* minus, int32_t stranded, uint8_t* run_strand, int32_t* run_chrom, int64_t* run_start,
                                    int64_t* run_end, int64_t* run_depth, int64_t* n_runs_out) {
@@ -145,19 +165,11 @@ extern "C" int mirge_coverage_runs(mirge_ctx* c, int64_t n, const int32_t* chrom
     for (int64_t i = 0; i < n; i++) top = std::max(top, chrom_rank[i]);
     if (top >= (1 << 24)) return fail(-1, who + ": a chromosome rank beyond 2^24");
     const size_t sn = (size_t)n;
-    int32_t *d_rank = nullptr, *d_len = nullptr;
-    long long* d_start = nullptr;
-    uint32_t* d_w = nullptr;
-    uint8_t* d_minus = nullptr;
+    CovUpload up;
     CovDev dev;
     auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_rank, sn)); CHECK(dalloc(c, &d_len, sn)); CHECK(dalloc(c, &d_start, sn)); CHECK(dalloc(c, &d_w, sn)); CHECK(dalloc(c, &d_minus, sn));
-        HIPOK(hipMemcpyAsync(d_rank, chrom_rank, sn * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_start, start, sn * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_len, len, sn * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_w, weight, sn * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_minus, minus, sn, hipMemcpyHostToDevice, c->stream));
-        CHECK(dev.runs(c, who, CovIntervals{d_rank, d_start, d_len, d_w, d_minus}, sn, (uint32_t)top + 1u, stranded != 0));
+        CHECK(up.upload(c, sn, chrom_rank, start, len, weight, minus));
+        CHECK(dev.runs(c, who, up.intervals(), sn, (uint32_t)top + 1u, stranded != 0));
         if (dev.n_runs > 2 * sn) return fail(-3, who + ": more runs than events");
         if (dev.n_runs) {
             HIPOK(hipMemcpyAsync(run_strand, dev.r.strand, dev.n_runs, hipMemcpyDeviceToHost, c->stream));
@@ -173,7 +185,7 @@ extern "C" int mirge_coverage_runs(mirge_ctx* c, int64_t n, const int32_t* chrom
     (void)hipStreamSynchronize(c->stream);
     c->drain();
     dev.release(c);
-    c->release(d_rank); c->release(d_len); c->release(d_start); c->release(d_w); c->release(d_minus);
+    up.release(c);
     if (rc == 0) *n_runs_out = (int64_t)dev.n_runs;
     return rc;
 }
@@ -274,17 +286,16 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
         if (rank_name_off[k + 1] < rank_name_off[k] || rank_name_off[k + 1] - rank_name_off[0] >= 0x7FFFFFF0ll) return fail(-1, who + ": malformed chromosome names");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     HostClock hc("coverage_write_device");
-    size_t tile = sam_env_bytes("MIRGE_COV_TILE_BYTES", 8160);
+    size_t tile = env_bytes("MIRGE_COV_TILE_BYTES", 8160);
     tile = std::min<size_t>(MIRGE_COV_MAX_TILE, std::max<size_t>(64, tile)) & ~size_t(15);
-    size_t chunk = sam_env_bytes("MIRGE_COV_CHUNK_BYTES", (size_t)32 << 20);
+    size_t chunk = env_bytes("MIRGE_COV_CHUNK_BYTES", (size_t)32 << 20);
     chunk = std::min<size_t>((size_t)1 << 30, std::max(chunk, tile)) / tile * tile;
 
     CovInput in;
     CovDev dev;
     uint8_t* d_text[2] = {nullptr, nullptr};
-    int rc = 0, fd[2] = {-1, -1};
-    const char* paths[2] = {path, stranded ? path_minus : nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = 0;
+    OutFile out[2] = {{who}, {who}};  // (the strands' files: both or neither, commit_all)
     size_t n_rows = 0;
     hipError_t e = hipSuccess;
     do {
@@ -296,44 +307,14 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
         hc.lap("measured");
         // ---- the file or files: every error of the data has been raised by now
         const unsigned long long body = dev.body, split = stranded ? dev.split : dev.body;
-        for (int f = 0; f < 2 && rc == 0; f++) {
-            if (!paths[f]) continue;
-            fd[f] = ::open(paths[f], O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            if (fd[f] < 0) rc = fail(-8, std::string("cannot write ") + paths[f]);
-        }
-        if (rc) break;
+        if ((rc = out[0].open(path)) || (stranded && (rc = out[1].open(path_minus)))) break;
         if (body) {
             const size_t buf = (size_t)std::min<unsigned long long>(chunk, body);
-            if (2 * buf > c->sam_pinned_bytes) {  // page-locked staging of two chunks, kept between samples (shared with --sam-out)
-                if (c->sam_pinned) (void)hipHostFree(c->sam_pinned);
-                c->sam_pinned = nullptr; c->sam_pinned_bytes = 0;
-                if (hipHostMalloc((void**)&c->sam_pinned, 2 * buf, hipHostMallocDefault) != hipSuccess) {
-                    rc = fail(-3, who + ": cannot page-lock " + std::to_string(2 * buf) + " bytes"); break;
-                }
-                c->sam_pinned_bytes = 2 * buf;
-            }
+            StagePipe pipe(c, who);
+            if ((rc = pipe.ensure(buf))) break;
             if ((rc = dalloc(c, &d_text[0], buf + 16))) break;
             if (body > buf && (rc = dalloc(c, &d_text[1], buf + 16))) break;
-            ev[0] = c->get_evt(); ev[1] = c->get_evt();
-            const unsigned long long n_chunks = (body + chunk - 1) / chunk;
-            auto put_part = [&](int f, const uint8_t* src, size_t nn, unsigned long long at) -> int {
-                size_t done = 0;
-                while (done < nn) {
-                    const ssize_t wr = ::pwrite(fd[f], src + done, nn - done, (off_t)(at + done));
-                    if (wr <= 0) return fail(-8, who + ": write error on " + paths[f]);
-                    done += (size_t)wr;
-                }
-                return 0;
-            };
-            auto put = [&](unsigned long long ci) -> int {  // chunk ci has been queued: wait for its copy; the plus strand's bytes end at `split`
-                if (hipEventSynchronize(ev[ci & 1]) != hipSuccess) return fail(-2, who + ": the copy of a chunk failed");
-                const unsigned long long at0 = ci * chunk, at1 = at0 + std::min<unsigned long long>(chunk, body - at0);
-                const uint8_t* src = c->sam_pinned + (ci & 1) * buf;
-                if (at0 < split) CHECK(put_part(0, src, (size_t)(std::min(at1, split) - at0), at0));
-                if (at1 > split) { const unsigned long long b0 = std::max(at0, split); CHECK(put_part(1, src + (b0 - at0), (size_t)(at1 - b0), b0 - split)); }
-                return 0;
-            };
-            for (unsigned long long ci = 0; ci < n_chunks && rc == 0; ci++) {
+            auto queue = [&](unsigned long long ci) -> int {
                 const unsigned long long at0 = ci * chunk;
                 const uint32_t nn = (uint32_t)std::min<unsigned long long>(chunk, body - at0);
                 const size_t tiles = ((size_t)nn + tile - 1) / tile;
@@ -343,28 +324,24 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
                                        (uint32_t)dev.n_runs, (const uint32_t*)dev.d_name_off, (const uint8_t*)dev.d_name_data,
                                        (const unsigned long long*)dev.d_off, at0, nn, (uint32_t)tile, d_text[ci & 1]);
                 }
-                e = hipMemcpyAsync(c->sam_pinned + (ci & 1) * buf, d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipEventRecord(ev[ci & 1], c->stream);
-                if (e != hipSuccess) { rc = fail(-2, who + ": " + hipGetErrorString(e)); break; }
-                if (ci) rc = put(ci - 1);  // (chunk ci - 1's half of the staging is free again before chunk ci + 1 is queued)
-            }
-            if (rc == 0) rc = put(n_chunks - 1);
+                e = hipMemcpyAsync(pipe.half(ci), d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream);
+                return e == hipSuccess ? 0 : fail(-2, who + ": " + hipGetErrorString(e));
+            };
+            auto take = [&](unsigned long long ci) -> int {  // chunk ci is in its half; the plus strand's bytes end at `split`
+                const unsigned long long at0 = ci * chunk, at1 = at0 + std::min<unsigned long long>(chunk, body - at0);
+                const uint8_t* src = pipe.half(ci);
+                if (at0 < split) CHECK(out[0].put(src, (size_t)(std::min(at1, split) - at0), at0));
+                if (at1 > split) { const unsigned long long b0 = std::max(at0, split); CHECK(out[1].put(src + (b0 - at0), (size_t)(at1 - b0), b0 - split)); }
+                return 0;
+            };
+            rc = pipe.run((body + chunk - 1) / chunk, queue, take);
         }
         if (rc) break;
         hc.lap("formatted + written");
     } while (0);
     (void)hipStreamSynchronize(c->stream);
     c->drain();
-    for (int f = 0; f < 2; f++) {
-        if (fd[f] < 0) continue;
-        struct stat st;
-        const bool regular = ::fstat(fd[f], &st) == 0 && S_ISREG(st.st_mode);
-        if (::close(fd[f]) != 0 && rc == 0) rc = fail(-8, who + ": cannot close " + paths[f]);
-        fd[f] = regular ? -2 : -1;
-    }
-    if (rc != 0)  // never a partial file that looks like a result
-        for (int f = 0; f < 2; f++) if (fd[f] == -2) (void)::unlink(paths[f]);
-    for (auto& x : ev) if (x) c->evt_pool.push_back(x);
+    if (rc == 0) rc = commit_all({&out[0], &out[1]});
     in.release(c);
     dev.release(c);
     c->release(d_text[0]); c->release(d_text[1]);

@@ -83,9 +83,9 @@ struct mirge_ctx {
     // page-locked staging of mirge_annotation_csv_device (the text of mapped.csv + unmapped.csv), kept between samples
     uint8_t* csv_pinned = nullptr;
     size_t csv_pinned_bytes = 0;
-    // page-locked staging of mirge_sam_write_device: two chunks of a sample's SAM text, kept between samples
-    uint8_t* sam_pinned = nullptr;
-    size_t sam_pinned_bytes = 0;
+    // page-locked staging of the chunked exporters (StagePipe, native_stage.hpp): two chunks of a sample's output, kept between samples
+    uint8_t* stage_pinned = nullptr;
+    size_t stage_pinned_bytes = 0;
     // start / end clocks of the workgroups of the last profiled k_cascade_bulk launch (mirge_cascade_wg_times)
     // k_cascade_heavy (kernels_cascade.hpp): per read group {reads listed, workgroups done}, zero between launches; the threshold the
     // current configuration's steps carry (0: no library holds a bucket that large -- no deferral, no extra launch)
@@ -395,7 +395,7 @@ extern "C" void mirge_ctx_destroy(mirge_ctx* c) {
     if (c->prof_pinned) (void)hipHostFree(c->prof_pinned);
     if (c->join_pinned) (void)hipHostFree(c->join_pinned);
     if (c->csv_pinned) (void)hipHostFree(c->csv_pinned);
-    if (c->sam_pinned) (void)hipHostFree(c->sam_pinned);
+    if (c->stage_pinned) (void)hipHostFree(c->stage_pinned);
     if (c->wg_pinned) (void)hipHostFree(c->wg_pinned);
     if (c->heavy_cnt) (void)hipFree(c->heavy_cnt);
     if (c->join_dev) (void)hipFree(c->join_dev);

@@ -2,9 +2,12 @@
 // other native_*.hpp, and -- on its own, with g++ -fsanitize=address,undefined -- by tests/hostsim/host_only_main.cpp: the GPU pool
 // has no device sanitizer, and these ~400 lines of raw-cursor formatting, index checks and text rebuilding are where a host-side
 // memory error would live ("race detection / sanitizers").  What is here: the error state (fail / mirge_last_error),
-// the host timing hook, the mapped.csv / unmapped.csv formatter (mirge_annotation_csv), the GFF3 writer (mirge_gff_write), the
+// the host timing hook, the exporters' output file (OutFile, commit_all), the mapped.csv / unmapped.csv formatter (mirge_annotation_csv), the GFF3 writer (mirge_gff_write), the
 // text of a merged library, the argument checks of mirge_lib_create_packed.
 #pragma once
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 // ------------------------------------------------------------------------------------------
 // errors
 // ------------------------------------------------------------------------------------------
@@ -39,6 +42,59 @@ struct HostClock {
         t0 = t;
     }
 };
+
+// One output file of an exporter: positioned writes until done, and never a partial file that looks like a result -- an OutFile that
+// is not committed takes its file with it (a FIFO or a device node it was pointed at is closed and left alone).  tmp: the bytes go to
+// `<path>.tmp`, which commit() renames to `<path>`; a failure removes both names.  Files that stand or fall together: commit_all.
+struct OutFile {
+    std::string who, path;
+    bool tmp = false, regular = false;
+    int fd = -1;
+    OutFile(std::string w, bool tmp_ = false) : who(std::move(w)), tmp(tmp_) {}
+    OutFile(const OutFile&) = delete;
+    OutFile& operator=(const OutFile&) = delete;
+    ~OutFile() { if (fd >= 0) discard(); }
+    std::string target() const { return tmp ? path + ".tmp" : path; }
+    int open(const std::string& p) {
+        path = p;
+        fd = ::open(target().c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) { const int rc = fail(-8, "cannot write " + target()); path.clear(); return rc; }
+        struct stat st;
+        regular = ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+        return 0;
+    }
+    int put(const void* src, size_t n, unsigned long long at) {
+        for (size_t done = 0; done < n;) {
+            const ssize_t wr = ::pwrite(fd, static_cast<const uint8_t*>(src) + done, n - done, (off_t)(at + done));
+            if (wr <= 0) return fail(-8, who + ": write error on " + target());
+            done += (size_t)wr;
+        }
+        return 0;
+    }
+    int commit() {  // (of a file never opened: nothing)
+        if (fd < 0) return 0;
+        const bool closed = ::close(fd) == 0;
+        fd = -1;
+        if (closed && (!tmp || ::rename(target().c_str(), path.c_str()) == 0)) return 0;
+        const int rc = fail(-8, who + (closed ? ": cannot rename to " + path : ": cannot close " + target()));
+        discard();
+        return rc;
+    }
+    void discard() {  // open or committed: the file goes
+        if (fd >= 0) (void)::close(fd);
+        fd = -1;
+        if (tmp && !path.empty()) (void)::unlink(target().c_str());
+        if ((tmp || regular) && !path.empty()) (void)::unlink(path.c_str());
+        path.clear();
+    }
+};
+// every open file of a group is committed, or none of the group stays
+static int commit_all(std::initializer_list<OutFile*> group) {
+    int rc = 0;
+    for (OutFile* f : group) if (rc == 0) rc = f->commit();
+    if (rc) for (OutFile* f : group) f->discard();
+    return rc;
+}
 
 
 namespace {

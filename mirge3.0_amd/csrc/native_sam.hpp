@@ -1,18 +1,11 @@
 // native_sam.hpp -- part of mirge_native.hip (one translation unit): `<sample>.sam` of `--sam-out` from the device-resident run
 // (kernels_sam.hpp).  One call writes ONE sample's file: rows chosen and ordered (k_sam_select, one scan), measured (k_sam_measure,
 // one 64-bit scan), then the text produced chunk by chunk (k_sam_write) into one of two device buffers, copied to page-locked
-// staging and put into the file with positioned writes while the next chunk is being formatted.  The text of a sample is one
+// staging and put into the file while the next chunk is being formatted (StagePipe, native_stage.hpp).  The text of a sample is one
 // line per RAW read (a gigabyte for 10 M reads): it never exists whole, neither on the device nor on the host.
 // MIRGE_SAM_CHUNK_BYTES / MIRGE_SAM_TILE_BYTES (read per call): the chunk and the workgroup's tile; tests make them small so that
 // their boundaries fall inside lines, inside a QNAME's digits and inside a row of many copies.
 #pragma once
-
-static size_t sam_env_bytes(const char* name, size_t dflt) {
-    const char* v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    const long long x = std::atoll(v);
-    return x > 0 ? (size_t)x : dflt;
-}
 
 // What `--sam-out` and `--sorted-bam` share: the passes' lift tables on the device (ONE blob: 8-byte items first, then 4-byte, then
 // bytes) and the file's rows in class order (k_sam_select, one scan, k_sam_rows).  build() leaves the stream synchronised.
@@ -159,18 +152,18 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     HostClock hc("sam_write_device");
     // ---- sizes of the chunked output
-    size_t tile = sam_env_bytes("MIRGE_SAM_TILE_BYTES", 8160);  // 255 probe points of 32 bytes + the one behind the tile's end: one per thread
+    size_t tile = env_bytes("MIRGE_SAM_TILE_BYTES", 8160);  // 255 probe points of 32 bytes + the one behind the tile's end: one per thread
     tile = std::min<size_t>(MIRGE_SAM_MAX_TILE, std::max<size_t>(64, tile)) & ~size_t(15);
-    size_t chunk = sam_env_bytes("MIRGE_SAM_CHUNK_BYTES", (size_t)32 << 20);
+    size_t chunk = env_bytes("MIRGE_SAM_CHUNK_BYTES", (size_t)32 << 20);
     chunk = std::min<size_t>((size_t)1 << 30, std::max(chunk, tile)) / tile * tile;
 
     SamPrep prep;
     uint8_t* d_text[2] = {nullptr, nullptr};
     uint32_t* d_fixed = nullptr;
     unsigned long long *d_total = nullptr, *d_off = nullptr, *d_nlines = nullptr;
-    int rc = 0, fd = -1;
+    int rc = 0;
     int64_t n_lines = 0, n_bytes = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    OutFile out("mirge_sam_write_device");
     do {
         if ((rc = prep.build(c, "mirge_sam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
         const SamTables& t = prep.t;
@@ -199,36 +192,15 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
         if (e != hipSuccess) { rc = fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e)); break; }
         hc.lap("measured");
         // ---- the file: header, then the body chunk by chunk
-        fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0 || (header_len && ::pwrite(fd, header, (size_t)header_len, 0) != (ssize_t)header_len)) { rc = fail(-8, std::string("cannot write ") + path); break; }
+        if ((rc = out.open(path))) break;
+        if (header_len && out.put(header, (size_t)header_len, 0)) { rc = fail(-8, std::string("cannot write ") + path); break; }
         if (body) {
             const size_t buf = (size_t)std::min<unsigned long long>(chunk, body);
-            if (2 * buf > c->sam_pinned_bytes) {  // page-locked staging of two chunks, kept between samples
-                if (c->sam_pinned) (void)hipHostFree(c->sam_pinned);
-                c->sam_pinned = nullptr; c->sam_pinned_bytes = 0;
-                if (hipHostMalloc((void**)&c->sam_pinned, 2 * buf, hipHostMallocDefault) != hipSuccess) {
-                    rc = fail(-3, "mirge_sam_write_device: cannot page-lock " + std::to_string(2 * buf) + " bytes"); break;
-                }
-                c->sam_pinned_bytes = 2 * buf;
-            }
+            StagePipe pipe(c, out.who);
+            if ((rc = pipe.ensure(buf))) break;
             if ((rc = dalloc(c, &d_text[0], buf + 16))) break;
             if (body > buf && (rc = dalloc(c, &d_text[1], buf + 16))) break;
-            ev[0] = c->get_evt(); ev[1] = c->get_evt();
-            const unsigned long long n_chunks = (body + chunk - 1) / chunk;
-            auto put = [&](unsigned long long ci) -> int {  // chunk ci has been queued: wait for its copy, write it at its place
-                if (hipEventSynchronize(ev[ci & 1]) != hipSuccess) return fail(-2, "mirge_sam_write_device: the copy of a chunk failed");
-                const unsigned long long at0 = ci * chunk;
-                const size_t nn = (size_t)std::min<unsigned long long>(chunk, body - at0);
-                const uint8_t* src = c->sam_pinned + (ci & 1) * buf;
-                size_t done = 0;
-                while (done < nn) {
-                    const ssize_t wr = ::pwrite(fd, src + done, nn - done, (off_t)((unsigned long long)header_len + at0 + done));
-                    if (wr <= 0) return fail(-8, std::string("mirge_sam_write_device: write error on ") + path);
-                    done += (size_t)wr;
-                }
-                return 0;
-            };
-            for (unsigned long long ci = 0; ci < n_chunks && rc == 0; ci++) {
+            auto queue = [&](unsigned long long ci) -> int {
                 const unsigned long long at0 = ci * chunk;
                 const uint32_t nn = (uint32_t)std::min<unsigned long long>(chunk, body - at0);
                 const size_t tiles = ((size_t)nn + tile - 1) / tile;
@@ -238,12 +210,14 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
                                        (const uint32_t*)d_rows, (uint32_t)n_rows, (const uint32_t*)d_fixed, (const unsigned long long*)d_off, at0, nn,
                                        (uint32_t)tile, d_text[ci & 1]);
                 }
-                e = hipMemcpyAsync(c->sam_pinned + (ci & 1) * buf, d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipEventRecord(ev[ci & 1], c->stream);
-                if (e != hipSuccess) { rc = fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e)); break; }
-                if (ci) rc = put(ci - 1);  // (chunk ci - 1's half of the staging is free again before chunk ci + 1 is queued)
-            }
-            if (rc == 0) rc = put(n_chunks - 1);
+                e = hipMemcpyAsync(pipe.half(ci), d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream);
+                return e == hipSuccess ? 0 : fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e));
+            };
+            auto take = [&](unsigned long long ci) -> int {  // chunk ci is in its half: write it at its place
+                const unsigned long long at0 = ci * chunk;
+                return out.put(pipe.half(ci), (size_t)std::min<unsigned long long>(chunk, body - at0), (unsigned long long)header_len + at0);
+            };
+            rc = pipe.run((body + chunk - 1) / chunk, queue, take);
         }
         if (rc) break;
         n_lines = (int64_t)lines; n_bytes = (int64_t)body;
@@ -251,14 +225,7 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     } while (0);
     (void)hipStreamSynchronize(c->stream);
     c->drain();
-    bool regular = false;
-    if (fd >= 0) {
-        struct stat st;
-        regular = ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-        if (::close(fd) != 0 && rc == 0) rc = fail(-8, std::string("mirge_sam_write_device: cannot close ") + path);
-    }
-    if (rc != 0 && regular) (void)::unlink(path);  // never a partial file that looks like a result
-    for (auto& x : ev) if (x) c->evt_pool.push_back(x);
+    if (rc == 0) rc = out.commit();  // (an OutFile that is not committed takes its file with it)
     prep.release(c);
     c->release(d_text[0]); c->release(d_text[1]); c->release(d_fixed); c->release(d_total); c->release(d_off); c->release(d_nlines);
     if (rc == 0) {

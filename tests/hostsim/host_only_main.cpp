@@ -4,8 +4,12 @@
 // The GPU pool has no device sanitizer; these functions never touch the device, so the very translation unit the product
 // compiles runs here under the host sanitizers.  Cases: names that need CSV quoting (comma, quote, line break), empty libraries
 // and empty references, reads of 0, 1, 255 and 600 nt, 1 and 17 samples, unmapped-only and mapped-only outputs, row orders that are
-// permutations, out-of-range indices that must be refused, a GFF with reads that hold an N and records at the text limit.
+// permutations, out-of-range indices that must be refused, a GFF with reads that hold an N and records at the text limit; the
+// exporters' output file (OutFile, commit_all): what stays and what goes after a commit, a failed open, a write error, a FIFO.
 #include <fcntl.h>
+#include <signal.h>
+#include <sys/resource.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -336,6 +340,92 @@ int main(int argc, char** argv) {
         bg[bg.size() / 2] ^= 1;
         EXPECT(mirge_gz_inflate((const uint8_t*)bg.data(), (int64_t)bg.size(), out3.data(), (int64_t)out3.size(), &n, 5) != 0);
         std::printf("gz: %d inflated in parallel and equal, %d left to the serial route\n", taken, refused);
+    }
+    // ---------------- OutFile / commit_all: the exporters' output files (everything stays inside `dir`)
+    {
+        auto exists = [](const std::string& p) { struct stat st; return ::lstat(p.c_str(), &st) == 0; };
+        const std::string a = dir + "/of_a.bin", b = dir + "/of_b.bin", nodir = dir + "/no_such_dir/x.bin", fifo = dir + "/of_fifo";
+        std::string want(100000, '\0');
+        for (auto& ch : want) ch = (char)rng();
+        {   // commit keeps the bytes; puts out of order, at their offsets
+            OutFile f("t");
+            EXPECT(f.open(a) == 0 && f.regular);
+            EXPECT(f.put(want.data() + 70000, 30000, 70000) == 0 && f.put(want.data(), 1, 0) == 0 && f.put(want.data() + 1, 69999, 1) == 0);
+            EXPECT(f.put(want.data(), 0, 5) == 0 && f.commit() == 0 && f.commit() == 0);
+        }
+        EXPECT(slurp(a) == want);
+        {   // ... and open truncates what was there; an uncommitted regular file is gone after the destructor
+            OutFile f("t");
+            EXPECT(f.open(a) == 0 && f.put("xy", 2, 0) == 0 && slurp(a) == "xy");
+        }
+        EXPECT(!exists(a));
+        {   // an uncommitted FIFO is closed and left alone (this end keeps it open, so the writer's open does not block)
+            EXPECT(::mkfifo(fifo.c_str(), 0600) == 0);
+            const int keep = ::open(fifo.c_str(), O_RDWR);
+            EXPECT(keep >= 0);
+            { OutFile f("t"); EXPECT(f.open(fifo) == 0 && !f.regular); }
+            EXPECT(exists(fifo));
+            ::close(keep);
+            ::unlink(fifo.c_str());
+        }
+        {   // a directory that does not exist: -8, named, nothing made -- plain and through a temporary name
+            OutFile f("t"), g("t", true);
+            EXPECT(f.open(nodir) == -8 && std::string(mirge_last_error()) == "cannot write " + nodir);
+            EXPECT(g.open(nodir) == -8 && std::string(mirge_last_error()) == "cannot write " + nodir + ".tmp");
+            EXPECT(f.commit() == 0 && g.commit() == 0);  // (never opened: nothing to commit)
+        }
+        EXPECT(!exists(dir + "/no_such_dir"));
+        {   // a write error (the file size limit, its signal ignored): -8, named, and the file goes with the OutFile
+            struct rlimit old, low;
+            EXPECT(::getrlimit(RLIMIT_FSIZE, &old) == 0);
+            low = old; low.rlim_cur = 4096;
+            void (*was)(int) = ::signal(SIGXFSZ, SIG_IGN);
+            EXPECT(::setrlimit(RLIMIT_FSIZE, &low) == 0);
+            int rc_in = 0, rc_past = 0;
+            std::string msg;
+            {
+                OutFile f("who");
+                rc_in = f.open(a) || f.put(want.data(), 1000, 0);
+                rc_past = f.put(want.data(), 10000, 1000);  // (crosses the limit: a short write, then none)
+                msg = mirge_last_error();
+            }
+            ::setrlimit(RLIMIT_FSIZE, &old);
+            ::signal(SIGXFSZ, was);
+            EXPECT(rc_in == 0 && rc_past == -8 && msg == "who: write error on " + a && !exists(a));
+        }
+        {   // a temporary name: success leaves only the final name ...
+            OutFile f("t", true);
+            EXPECT(f.open(a) == 0 && exists(a + ".tmp") && !exists(a) && f.put(want.data(), want.size(), 0) == 0 && f.commit() == 0);
+            EXPECT(!exists(a + ".tmp") && slurp(a) == want);
+        }
+        {   // ... failure neither, also a final name that was there before
+            OutFile f("t", true);
+            EXPECT(f.open(a) == 0 && f.put("xy", 2, 0) == 0 && slurp(a) == want);
+        }
+        EXPECT(!exists(a) && !exists(a + ".tmp"));
+        {   // a temporary name that cannot be renamed (the final name is a directory that holds something): named, and the temporary goes
+            EXPECT(::mkdir(b.c_str(), 0700) == 0 && ::mkdir((b + "/inner").c_str(), 0700) == 0);
+            OutFile f("who", true);
+            EXPECT(f.open(b) == 0 && f.commit() == -8 && std::string(mirge_last_error()) == "who: cannot rename to " + b && !exists(b + ".tmp"));
+            ::rmdir((b + "/inner").c_str());
+            ::rmdir(b.c_str());
+        }
+        {   // a pair whose second open fails leaves nothing of the first
+            OutFile f("t"), g("t");
+            EXPECT(f.open(a) == 0 && f.put("xy", 2, 0) == 0 && g.open(nodir) == -8);
+        }
+        EXPECT(!exists(a));
+        {   // a group: all committed (one of them never opened), or -- the second cannot be renamed -- none of it stays
+            OutFile f("t"), g("t"), h("t");
+            EXPECT(f.open(a) == 0 && g.open(b) == 0 && f.put("1", 1, 0) == 0 && g.put("2", 1, 0) == 0 && commit_all({&f, &g, &h}) == 0);
+            EXPECT(slurp(a) == "1" && slurp(b) == "2");
+            ::unlink(b.c_str());
+            EXPECT(::mkdir(b.c_str(), 0700) == 0 && ::mkdir((b + "/inner").c_str(), 0700) == 0);
+            OutFile p("t", true), q("t", true);
+            EXPECT(p.open(a) == 0 && q.open(b) == 0 && commit_all({&p, &q}) == -8 && !exists(a) && !exists(a + ".tmp") && !exists(b + ".tmp"));
+            ::rmdir((b + "/inner").c_str());
+            ::rmdir(b.c_str());
+        }
     }
     std::printf("host-only functions clean\n");
     return 0;
