@@ -64,6 +64,9 @@ int mirge_ctx_create(int device, void* hip_stream, mirge_ctx** out);
    passes take the probe path, with the same results. */
 void mirge_ctx_destroy(mirge_ctx* ctx);
 int mirge_ctx_sync(mirge_ctx* ctx);
+/* out[0] = bytes the pool has from the driver, out[1] = blocks handed out and not back, out[2] = blocks in the free list.
+ * Host bookkeeping only: queues nothing, waits for nothing.  Deferred blocks count as handed out until a join returns them. */
+int mirge_ctx_pool_stats(mirge_ctx* ctx, int64_t out[3]);
 
 /* ---- libraries: replaces `bowtie <index>` opening an .ebwt index (manifoldAlign.py:97-99)
  * and `bowtie-build`.  seq_ascii/offsets: the reference sequences in library order.          */

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MIRGE_NATIVE_SO") or os.path.join(_HERE, "csrc", "libmirge_native.so")
 
 EXPORTS = [
-    "mirge_last_error", "mirge_device_count", "mirge_gz_inflate", "mirge_gz_inflate_progress", "mirge_ctx_create", "mirge_ctx_destroy", "mirge_ctx_sync",
+    "mirge_last_error", "mirge_device_count", "mirge_gz_inflate", "mirge_gz_inflate_progress", "mirge_ctx_create", "mirge_ctx_destroy", "mirge_ctx_sync", "mirge_ctx_pool_stats",
     "mirge_lib_create", "mirge_lib_create_packed", "mirge_lib_packed_sizes", "mirge_lib_packed_copy", "mirge_lib_destroy", "mirge_lib_n_refs", "mirge_lib_device_bytes", "mirge_lib_prepare",
     "mirge_reads_pack", "mirge_reads_parse", "mirge_reads_parse_trim", "mirge_reads_parse_umi", "mirge_reads_concat", "mirge_reads_destroy", "mirge_reads_count", "mirge_reads_total_bases",
     "mirge_reads_n_samples", "mirge_reads_group_counts", "mirge_reads_iupac_seen", "mirge_reads_unpack", "mirge_collapse", "mirge_collapse_weighted", "mirge_collapse_merge", "mirge_collapse_fetch", "mirge_collapse_order", "mirge_collapse_order_sorted", "mirge_collapse_nonzero",
@@ -319,6 +319,12 @@ class Context:
 
     def sync(self):
         _check(load().mirge_ctx_sync(self._h), "mirge_ctx_sync")
+
+    def pool_stats(self):
+        """(bytes the pool has from the driver, blocks handed out and not back, blocks in the free list): host bookkeeping only"""
+        out = (C.c_int64 * 3)()
+        _check(load().mirge_ctx_pool_stats(self._h, out), "mirge_ctx_pool_stats")
+        return int(out[0]), int(out[1]), int(out[2])
 
     # ---- measurement
     def timer_start(self):

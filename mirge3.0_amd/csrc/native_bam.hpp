@@ -106,228 +106,200 @@ extern "C" int mirge_bam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     const unsigned long long H = (unsigned long long)header_len;
 
     SamPrep prep;
-    unsigned long long *d_key = nullptr, *d_key2 = nullptr, *d_total = nullptr, *d_stotal = nullptr, *d_off = nullptr, *d_nrec = nullptr, *d_count = nullptr;
-    uint32_t *d_fixed = nullptr, *d_sfixed = nullptr, *d_srows = nullptr, *d_perm = nullptr, *d_perm2 = nullptr, *d_bflags = nullptr, *d_span = nullptr;
+    unsigned long long *d_key, *d_key2, *d_total, *d_stotal, *d_off, *d_nrec, *d_count;
+    uint32_t *d_fixed, *d_sfixed, *d_srows, *d_perm, *d_perm2, *d_bflags, *d_span;
     uint32_t *d_sizes = nullptr, *d_boff[2] = {nullptr, nullptr};
-    int32_t* d_refid = nullptr;
-    uint8_t *d_header = nullptr, *d_slots = nullptr, *d_comp[2] = {nullptr, nullptr};
-    void* tmp2 = nullptr;
-    int rc = 0;
-    int64_t n_records = 0, n_file = 0;
-    unsigned long long body = 0;
-    OutFile bam("mirge_bam_write_device"), bai("mirge_bam_write_device");  // (both or neither: commit_all)
-    do {
-        if ((rc = prep.build(c, "mirge_bam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
-        const SamTables& t = prep.t;
-        const size_t n_rows = prep.n_rows;
-        hc.lap("rows chosen");
-        // ---- chromosome -> refID per pass, the header
-        for (int p = 0; p < n_pass && rc == 0; p++) {
-            const int64_t nn = chrom_refid_off[p + 1] - chrom_refid_off[p];
-            bool named = false;
-            for (int k = 0; k < n_class; k++) named |= class_pass[k] == p;
-            if (chrom_refid_off[p] < 0 || nn < 0 || (named && nn != passes[p].n_chrom)) rc = fail(-1, "mirge_bam_write_device: the refID table of pass " + std::to_string(p) + " does not fit its chromosomes");
-            for (int64_t k = 0; k < nn && rc == 0; k++)
-                if (chrom_refid[chrom_refid_off[p] + k] >= n_ref) rc = fail(-1, "mirge_bam_write_device: a refID beyond the reference list");
-        }
-        if (rc) break;
-        const size_t n_map = (size_t)chrom_refid_off[n_pass];
-        if ((rc = dalloc(c, &d_refid, n_map + 1))) break;
-        if ((rc = dalloc(c, &d_header, (size_t)H + 16))) break;
-        if ((rc = dalloc(c, &d_bflags, 16))) break;
-        if ((rc = dalloc(c, &d_nrec, 2))) break;
-        if ((rc = dalloc(c, &d_key, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_key2, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_perm, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_perm2, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_fixed, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_sfixed, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_srows, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_span, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_count, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_total, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_stotal, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_off, n_rows + 1))) break;
-        BamTables bt;
-        std::memset(&bt, 0, sizeof(bt));
-        for (int p = 0; p < n_pass; p++) bt.refid[p] = d_refid + chrom_refid_off[p];
-        bt.header = d_header; bt.header_len = H;
-        hipError_t e = hipSuccess;
-        if (n_map) e = hipMemcpyAsync(d_refid, chrom_refid, n_map * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_header, header, (size_t)H, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_bflags, 0, 64, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_nrec, 0, 16, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_stotal + n_rows, 0, 8, c->stream);
-        if (e == hipSuccess && n_rows) {
-            LaunchScope ls(c, "k_bam_measure", (double)n_rows);
-            hipLaunchKernelGGL(k_bam_measure, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)prep.d_rows, (uint32_t)n_rows, d_key,
-                               d_fixed, d_total, d_nrec, d_bflags);
-        }
-        uint32_t hflags[4] = {0, 0, 0, 0};
-        unsigned long long records = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(hflags, d_bflags, 16, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&records, d_nrec, 8, hipMemcpyDeviceToHost, c->stream);
-        { const hipError_t e2 = hipStreamSynchronize(c->stream); if (e == hipSuccess) e = e2; }
-        if (e != hipSuccess) { rc = fail(-2, std::string("mirge_bam_write_device: ") + hipGetErrorString(e)); break; }
-        if (hflags[0] & 2u) {
-            std::string name = "?";
-            if (hflags[1] < (uint32_t)n_pass && (int64_t)hflags[2] < passes[hflags[1]].n_chrom) {
-                const mirge_sam_pass& in = passes[hflags[1]];
-                name.assign(in.chrom_data + in.chrom_off[hflags[2]], in.chrom_data + in.chrom_off[hflags[2] + 1]);
-            }
-            rc = fail(-1, "mirge_bam_write_device: reads lie on '" + name + "', which no @SQ line of the header names");
-            break;
-        }
-        if (hflags[0] & 4u) { rc = fail(-1, "mirge_bam_write_device: a read lies outside [1, 2^29] of its reference: a BAM index cannot hold it"); break; }
-        if (hflags[0] & 8u) { rc = fail(-1, "mirge_bam_write_device: the QNAME of a read of " + std::to_string(hflags[3]) + " nt exceeds 254 characters (BAM's l_read_name is one byte)"); break; }
-        hc.lap("measured");
-        // ---- rows sorted by (refID, pos, reverse); their bytes scanned
-        size_t tb2 = 0, tb3 = 0;
-        if (n_rows) {
-            hipLaunchKernelGGL(k_iota, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, d_perm, (uint32_t)n_rows);
-            e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, d_key, d_key2, d_perm, d_perm2, (int)n_rows, 0, 64, c->stream);
-        }
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, d_stotal, d_off, (int)(n_rows + 1), c->stream);
-        if (e == hipSuccess && (rc = dalloc(c, (uint8_t**)&tmp2, std::max<size_t>(std::max(tb2, tb3), 16)))) break;
-        if (e == hipSuccess && n_rows) {
-            LaunchScope ls(c, "bam_sort_rows", (double)n_rows);
-            e = hipcub::DeviceRadixSort::SortPairs(tmp2, tb2, d_key, d_key2, d_perm, d_perm2, (int)n_rows, 0, 64, c->stream);
-            hipLaunchKernelGGL(k_bam_gather, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_perm2, (uint32_t)n_rows,
-                               (const uint32_t*)prep.d_rows, (const uint32_t*)d_fixed, (const unsigned long long*)d_total, d_srows, d_sfixed, d_stotal);
-            hipLaunchKernelGGL(k_bam_row_table, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, d_span, d_count);
-        }
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp2, tb3, d_stotal, d_off, (int)(n_rows + 1), c->stream);
-        std::vector<unsigned long long> h_key(n_rows + 1), h_count(n_rows + 1), h_off(n_rows + 1);
-        std::vector<uint32_t> h_span(n_rows + 1);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_off.data(), d_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_key.data(), d_key2, n_rows * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_count.data(), d_count, n_rows * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && n_rows) e = hipMemcpyAsync(h_span.data(), d_span, n_rows * 4, hipMemcpyDeviceToHost, c->stream);
-        { const hipError_t e2 = hipStreamSynchronize(c->stream); if (e == hipSuccess) e = e2; }
-        if (e != hipSuccess) { rc = fail(-2, std::string("mirge_bam_write_device: ") + hipGetErrorString(e)); break; }
-        body = h_off[n_rows];
-        hc.lap("sorted");
-        // ---- the file, chunk by chunk
-        const unsigned long long stream_bytes = H + body, n_blocks = (stream_bytes + block - 1) / block;
-        const unsigned long long n_chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;
-        const size_t cb = (size_t)std::min<unsigned long long>(chunk_blocks, n_blocks);
-        const size_t half = cb * slot_stride, meta = ((cb + 1) * 4 + 15) & ~size_t(15);
-        std::vector<unsigned long long> coff((size_t)n_blocks + 1, 0ull);
-        if ((rc = bam.open(bam_path))) break;
-        StagePipe pipe(c, bam.who, "a chunk failed on the device");
-        if ((rc = pipe.ensure(half + meta))) break;
-        if (!on_host && (rc = dalloc(c, &d_slots, half + 16))) break;
-        if (!on_host && (rc = dalloc(c, &d_sizes, cb + 1))) break;
-        size_t tb4 = 0;
-        void* tmp4 = nullptr;
-        for (int h = 0; h < 2 && rc == 0; h++) {
-            if (h == 1 && n_chunks < 2) break;
-            if ((rc = dalloc(c, &d_comp[h], half + 16))) break;
-            if (!on_host) rc = dalloc(c, &d_boff[h], cb + 1);
-        }
-        if (rc) break;
-        if (!on_host) {
-            e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb4, d_sizes, d_boff[0], (int)(cb + 1), c->stream);
-            if (e != hipSuccess) { rc = fail(-2, std::string("mirge_bam_write_device: ") + hipGetErrorString(e)); break; }
-            if (tb4 > std::max(std::max(tb2, tb3), (size_t)16)) { c->release(tmp2); tmp2 = nullptr; if ((rc = dalloc(c, (uint8_t**)&tmp2, tb4))) break; }
-            tmp4 = tmp2;
-        }
-        unsigned long long file_at = 0;
-        std::vector<std::vector<uint8_t>> members;
-        std::vector<uint8_t> joined;
-        auto blocks_of = [&](unsigned long long ci) { return (size_t)std::min<unsigned long long>(chunk_blocks, n_blocks - ci * chunk_blocks); };
-        auto take = [&](unsigned long long ci) -> int {  // chunk ci's event has passed: fetch it, write it behind what is there
-            const int h = (int)(ci & 1);
-            const size_t nb = blocks_of(ci);
-            const unsigned long long b0 = ci * chunk_blocks;
-            uint8_t* stage = pipe.half(ci);
-            if (!on_host) {
-                const uint32_t* boff = reinterpret_cast<const uint32_t*>(stage + half);  // exclusive scan of the members' sizes
-                const size_t total = boff[nb];
-                if (total > half) return fail(-6, "mirge_bam_write_device: a chunk's members do not fit their slots");
-                if (hipMemcpyAsync(stage, d_comp[h], total, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
-                    return fail(-2, "mirge_bam_write_device: the copy of a chunk failed");
-                for (size_t b = 0; b < nb; b++) coff[(size_t)b0 + b] = file_at + boff[b];
-                if (int r = bam.put(stage, total, file_at)) return r;
-                file_at += total;
-                return 0;
-            }
-            members.resize(nb);
-            std::atomic<int> bad{0};
-            mirge_gz::parallel_for((int)nb, T, [&](int b) {
-                const unsigned long long at0 = (b0 + (unsigned long long)b) * block;
-                const uint32_t n = (uint32_t)std::min<unsigned long long>(block, stream_bytes - at0);
-                if (bam_host_member(stage + (size_t)b * block, n, members[(size_t)b])) bad = 1;
-            });
-            if (bad) return fail(-6, "mirge_bam_write_device: zlib could not deflate a block");
-            joined.clear();
-            for (size_t b = 0; b < nb; b++) {
-                coff[(size_t)b0 + b] = file_at + joined.size();
-                joined.insert(joined.end(), members[b].begin(), members[b].end());
-            }
-            if (int r = bam.put(joined.data(), joined.size(), file_at)) return r;
-            file_at += joined.size();
-            return 0;
-        };
-        auto queue = [&](unsigned long long ci) -> int {
-            const int h = (int)(ci & 1);
-            const size_t nb = blocks_of(ci);
-            const unsigned long long b0 = ci * chunk_blocks;
-            uint8_t* stage = pipe.half(ci);
-            const unsigned grid = (unsigned)std::min<size_t>(nb, (size_t)1 << 20);  // one workgroup per block: the hardware balances them
-            {
-                LaunchScope ls(c, "k_bam_blocks", (double)nb * block);
-                if (dynamic)  // deflate == 2: an instantiation of its own (kernels_bam.hpp)
-                    hipLaunchKernelGGL(k_bam_blocks_dynamic, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
-                                       (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
-                else if (tight)  // deflate == 3: likewise
-                    hipLaunchKernelGGL(k_bam_blocks_tight, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
-                                       (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
-                else
-                    hipLaunchKernelGGL(k_bam_blocks, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, (const uint32_t*)d_sfixed,
-                                       (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, on_host ? 0 : 1, slot_stride,
-                                       on_host ? d_comp[h] : d_slots, d_sizes);
-            }
-            if (on_host) {
-                const size_t nn = (size_t)(std::min<unsigned long long>(stream_bytes, (b0 + nb) * block) - b0 * block);
-                e = hipMemcpyAsync(stage, d_comp[h], nn, hipMemcpyDeviceToHost, c->stream);
-            } else {
-                e = hipMemsetAsync(d_sizes + nb, 0, 4, c->stream);
-                if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp4, tb4, d_sizes, d_boff[h], (int)(nb + 1), c->stream);
-                if (e == hipSuccess) {
-                    LaunchScope ls(c, "k_bam_compact", (double)nb);
-                    hipLaunchKernelGGL(k_bam_compact, dim3((unsigned)std::min<size_t>(nb, (size_t)c->n_cu * 8)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint8_t*)d_slots,
-                                       slot_stride, (const uint32_t*)d_sizes, (const uint32_t*)d_boff[h], (uint32_t)nb, d_comp[h]);
-                    e = hipMemcpyAsync(stage + half, d_boff[h], (nb + 1) * 4, hipMemcpyDeviceToHost, c->stream);
-                }
-            }
-            return e == hipSuccess ? 0 : fail(-2, std::string("mirge_bam_write_device: ") + hipGetErrorString(e));
-        };
-        if ((rc = pipe.run(n_chunks, queue, take))) break;
-        coff[(size_t)n_blocks] = file_at;
-        if ((rc = bam.put(kBgzfEof, sizeof(kBgzfEof), file_at))) break;
-        file_at += sizeof(kBgzfEof);
-        n_records = (int64_t)records; n_file = (int64_t)file_at;
-        hc.lap("encoded + written");
-        // ---- the index
-        const std::vector<uint8_t> index = bam_build_index(n_ref, n_rows, h_key.data(), h_span.data(), h_count.data(), h_off.data(), H, block, coff);
-        if ((rc = bai.open(bai_path)) || (rc = bai.put(index.data(), index.size(), 0))) break;
-        hc.lap("indexed");
-    } while (0);
-    (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    if (rc == 0) rc = commit_all({&bai, &bam});  // (a failed .bai takes the .bam with it: an OutFile that is not committed removes its file)
-    prep.release(c);
-    c->release(d_key); c->release(d_key2); c->release(d_total); c->release(d_stotal); c->release(d_off); c->release(d_nrec); c->release(d_count);
-    c->release(d_fixed); c->release(d_sfixed); c->release(d_srows); c->release(d_perm); c->release(d_perm2); c->release(d_bflags); c->release(d_span);
-    c->release(d_sizes); c->release(d_boff[0]); c->release(d_boff[1]); c->release(d_refid); c->release(d_header); c->release(d_slots);
-    c->release(d_comp[0]); c->release(d_comp[1]); c->release(tmp2);
-    if (rc == 0) {
-        if (n_records_out) *n_records_out = n_records;
-        if (n_stream_bytes_out) *n_stream_bytes_out = (int64_t)(H + body);
-        if (n_file_bytes_out) *n_file_bytes_out = n_file;
+    int32_t* d_refid;
+    uint8_t *d_header, *d_slots = nullptr, *d_comp[2] = {nullptr, nullptr};
+    void* tmp2;
+    // (what the copies from the device fill stands in front of the scope: it is still there when the scope waits for the stream)
+    uint32_t hflags[4] = {0, 0, 0, 0};
+    unsigned long long records = 0;
+    std::vector<unsigned long long> h_key, h_count, h_off;
+    std::vector<uint32_t> h_span;
+    OutFile bam("mirge_bam_write_device"), bai("mirge_bam_write_device");  // (both or neither: commit_all; uncommitted, a file goes)
+    PoolScope scope(c);
+    CHECK(prep.build(scope, "mirge_bam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass));
+    const SamTables& t = prep.t;
+    const size_t n_rows = prep.n_rows;
+    hc.lap("rows chosen");
+    // ---- chromosome -> refID per pass, the header
+    for (int p = 0; p < n_pass; p++) {
+        const int64_t nn = chrom_refid_off[p + 1] - chrom_refid_off[p];
+        bool named = false;
+        for (int k = 0; k < n_class; k++) named |= class_pass[k] == p;
+        if (chrom_refid_off[p] < 0 || nn < 0 || (named && nn != passes[p].n_chrom)) return fail(-1, "mirge_bam_write_device: the refID table of pass " + std::to_string(p) + " does not fit its chromosomes");
+        for (int64_t k = 0; k < nn; k++)
+            if (chrom_refid[chrom_refid_off[p] + k] >= n_ref) return fail(-1, "mirge_bam_write_device: a refID beyond the reference list");
     }
-    return rc;
+    const size_t n_map = (size_t)chrom_refid_off[n_pass];
+    CHECK(scope.get(&d_refid, n_map + 1)); CHECK(scope.get(&d_header, (size_t)H + 16)); CHECK(scope.get(&d_bflags, 16)); CHECK(scope.get(&d_nrec, 2));
+    CHECK(scope.get(&d_key, n_rows + 1)); CHECK(scope.get(&d_key2, n_rows + 1)); CHECK(scope.get(&d_perm, n_rows + 1)); CHECK(scope.get(&d_perm2, n_rows + 1));
+    CHECK(scope.get(&d_fixed, n_rows + 1)); CHECK(scope.get(&d_sfixed, n_rows + 1)); CHECK(scope.get(&d_srows, n_rows + 1)); CHECK(scope.get(&d_span, n_rows + 1));
+    CHECK(scope.get(&d_count, n_rows + 1)); CHECK(scope.get(&d_total, n_rows + 1)); CHECK(scope.get(&d_stotal, n_rows + 1)); CHECK(scope.get(&d_off, n_rows + 1));
+    BamTables bt;
+    std::memset(&bt, 0, sizeof(bt));
+    for (int p = 0; p < n_pass; p++) bt.refid[p] = d_refid + chrom_refid_off[p];
+    bt.header = d_header; bt.header_len = H;
+    if (n_map) HIPOK(hipMemcpyAsync(d_refid, chrom_refid, n_map * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_header, header, (size_t)H, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(d_bflags, 0, 64, c->stream));
+    HIPOK(hipMemsetAsync(d_nrec, 0, 16, c->stream));
+    HIPOK(hipMemsetAsync(d_stotal + n_rows, 0, 8, c->stream));
+    if (n_rows) {
+        LaunchScope ls(c, "k_bam_measure", (double)n_rows);
+        hipLaunchKernelGGL(k_bam_measure, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)prep.d_rows, (uint32_t)n_rows, d_key,
+                           d_fixed, d_total, d_nrec, d_bflags);
+    }
+    HIPOK(hipMemcpyAsync(hflags, d_bflags, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(&records, d_nrec, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    if (hflags[0] & 2u) {
+        std::string name = "?";
+        if (hflags[1] < (uint32_t)n_pass && (int64_t)hflags[2] < passes[hflags[1]].n_chrom) {
+            const mirge_sam_pass& in = passes[hflags[1]];
+            name.assign(in.chrom_data + in.chrom_off[hflags[2]], in.chrom_data + in.chrom_off[hflags[2] + 1]);
+        }
+        return fail(-1, "mirge_bam_write_device: reads lie on '" + name + "', which no @SQ line of the header names");
+    }
+    if (hflags[0] & 4u) return fail(-1, "mirge_bam_write_device: a read lies outside [1, 2^29] of its reference: a BAM index cannot hold it");
+    if (hflags[0] & 8u) return fail(-1, "mirge_bam_write_device: the QNAME of a read of " + std::to_string(hflags[3]) + " nt exceeds 254 characters (BAM's l_read_name is one byte)");
+    hc.lap("measured");
+    // ---- rows sorted by (refID, pos, reverse); their bytes scanned
+    size_t tb2 = 0, tb3 = 0;
+    if (n_rows) {
+        hipLaunchKernelGGL(k_iota, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, d_perm, (uint32_t)n_rows);
+        HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, d_key, d_key2, d_perm, d_perm2, (int)n_rows, 0, 64, c->stream));
+    }
+    HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, d_stotal, d_off, (int)(n_rows + 1), c->stream));
+    CHECK(scope.get((uint8_t**)&tmp2, std::max<size_t>(std::max(tb2, tb3), 16)));
+    if (n_rows) {
+        LaunchScope ls(c, "bam_sort_rows", (double)n_rows);
+        HIPOK(hipcub::DeviceRadixSort::SortPairs(tmp2, tb2, d_key, d_key2, d_perm, d_perm2, (int)n_rows, 0, 64, c->stream));
+        hipLaunchKernelGGL(k_bam_gather, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_perm2, (uint32_t)n_rows,
+                           (const uint32_t*)prep.d_rows, (const uint32_t*)d_fixed, (const unsigned long long*)d_total, d_srows, d_sfixed, d_stotal);
+        hipLaunchKernelGGL(k_bam_row_table, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, d_span, d_count);
+    }
+    HIPOK(hipcub::DeviceScan::ExclusiveSum(tmp2, tb3, d_stotal, d_off, (int)(n_rows + 1), c->stream));
+    h_key.resize(n_rows + 1); h_count.resize(n_rows + 1); h_off.resize(n_rows + 1); h_span.resize(n_rows + 1);
+    HIPOK(hipMemcpyAsync(h_off.data(), d_off, (n_rows + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_rows) {
+        HIPOK(hipMemcpyAsync(h_key.data(), d_key2, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(h_count.data(), d_count, n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(h_span.data(), d_span, n_rows * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPOK(hipStreamSynchronize(c->stream));
+    const unsigned long long body = h_off[n_rows];
+    hc.lap("sorted");
+    // ---- the file, chunk by chunk
+    const unsigned long long stream_bytes = H + body, n_blocks = (stream_bytes + block - 1) / block;
+    const unsigned long long n_chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;
+    const size_t cb = (size_t)std::min<unsigned long long>(chunk_blocks, n_blocks);
+    const size_t half = cb * slot_stride, meta = ((cb + 1) * 4 + 15) & ~size_t(15);
+    std::vector<unsigned long long> coff((size_t)n_blocks + 1, 0ull);
+    CHECK(bam.open(bam_path));
+    StagePipe pipe(c, bam.who, "a chunk failed on the device");
+    CHECK(pipe.ensure(half + meta));
+    if (!on_host) { CHECK(scope.get(&d_slots, half + 16)); CHECK(scope.get(&d_sizes, cb + 1)); }
+    size_t tb4 = 0;
+    for (int h = 0; h < (n_chunks < 2 ? 1 : 2); h++) {
+        CHECK(scope.get(&d_comp[h], half + 16));
+        if (!on_host) CHECK(scope.get(&d_boff[h], cb + 1));
+    }
+    if (!on_host) {
+        HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb4, d_sizes, d_boff[0], (int)(cb + 1), c->stream));
+        if (tb4 > std::max(std::max(tb2, tb3), (size_t)16)) { scope.give(tmp2); CHECK(scope.get((uint8_t**)&tmp2, tb4)); }
+    }
+    unsigned long long file_at = 0;
+    std::vector<std::vector<uint8_t>> members;
+    std::vector<uint8_t> joined;
+    auto blocks_of = [&](unsigned long long ci) { return (size_t)std::min<unsigned long long>(chunk_blocks, n_blocks - ci * chunk_blocks); };
+    auto take = [&](unsigned long long ci) -> int {  // chunk ci's event has passed: fetch it, write it behind what is there
+        const int h = (int)(ci & 1);
+        const size_t nb = blocks_of(ci);
+        const unsigned long long b0 = ci * chunk_blocks;
+        uint8_t* stage = pipe.half(ci);
+        if (!on_host) {
+            const uint32_t* boff = reinterpret_cast<const uint32_t*>(stage + half);  // exclusive scan of the members' sizes
+            const size_t total = boff[nb];
+            if (total > half) return fail(-6, "mirge_bam_write_device: a chunk's members do not fit their slots");
+            if (hipMemcpyAsync(stage, d_comp[h], total, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+                return fail(-2, "mirge_bam_write_device: the copy of a chunk failed");
+            for (size_t b = 0; b < nb; b++) coff[(size_t)b0 + b] = file_at + boff[b];
+            if (int r = bam.put(stage, total, file_at)) return r;
+            file_at += total;
+            return 0;
+        }
+        members.resize(nb);
+        std::atomic<int> bad{0};
+        mirge_gz::parallel_for((int)nb, T, [&](int b) {
+            const unsigned long long at0 = (b0 + (unsigned long long)b) * block;
+            const uint32_t n = (uint32_t)std::min<unsigned long long>(block, stream_bytes - at0);
+            if (bam_host_member(stage + (size_t)b * block, n, members[(size_t)b])) bad = 1;
+        });
+        if (bad) return fail(-6, "mirge_bam_write_device: zlib could not deflate a block");
+        joined.clear();
+        for (size_t b = 0; b < nb; b++) {
+            coff[(size_t)b0 + b] = file_at + joined.size();
+            joined.insert(joined.end(), members[b].begin(), members[b].end());
+        }
+        if (int r = bam.put(joined.data(), joined.size(), file_at)) return r;
+        file_at += joined.size();
+        return 0;
+    };
+    auto queue = [&](unsigned long long ci) -> int {
+        const int h = (int)(ci & 1);
+        const size_t nb = blocks_of(ci);
+        const unsigned long long b0 = ci * chunk_blocks;
+        uint8_t* stage = pipe.half(ci);
+        const unsigned grid = (unsigned)std::min<size_t>(nb, (size_t)1 << 20);  // one workgroup per block: the hardware balances them
+        {
+            LaunchScope ls(c, "k_bam_blocks", (double)nb * block);
+            if (dynamic)  // deflate == 2: an instantiation of its own (kernels_bam.hpp)
+                hipLaunchKernelGGL(k_bam_blocks_dynamic, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
+                                   (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
+            else if (tight)  // deflate == 3: likewise
+                hipLaunchKernelGGL(k_bam_blocks_tight, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows,
+                                   (const uint32_t*)d_sfixed, (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, slot_stride, d_slots, d_sizes);
+            else
+                hipLaunchKernelGGL(k_bam_blocks, dim3(grid), dim3(MIRGE_BLOCK), 0, c->stream, t, bt, (const uint32_t*)d_srows, (uint32_t)n_rows, (const uint32_t*)d_sfixed,
+                                   (const unsigned long long*)d_off, stream_bytes, b0, (uint32_t)nb, block, on_host ? 0 : 1, slot_stride,
+                                   on_host ? d_comp[h] : d_slots, d_sizes);
+        }
+        if (on_host) {
+            const size_t nn = (size_t)(std::min<unsigned long long>(stream_bytes, (b0 + nb) * block) - b0 * block);
+            HIPOK(hipMemcpyAsync(stage, d_comp[h], nn, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIPOK(hipMemsetAsync(d_sizes + nb, 0, 4, c->stream));
+            HIPOK(hipcub::DeviceScan::ExclusiveSum(tmp2, tb4, d_sizes, d_boff[h], (int)(nb + 1), c->stream));
+            {
+                LaunchScope ls(c, "k_bam_compact", (double)nb);
+                hipLaunchKernelGGL(k_bam_compact, dim3((unsigned)std::min<size_t>(nb, (size_t)c->n_cu * 8)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint8_t*)d_slots,
+                                   slot_stride, (const uint32_t*)d_sizes, (const uint32_t*)d_boff[h], (uint32_t)nb, d_comp[h]);
+            }
+            HIPOK(hipMemcpyAsync(stage + half, d_boff[h], (nb + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
+    };
+    CHECK(pipe.run(n_chunks, queue, take));
+    coff[(size_t)n_blocks] = file_at;
+    CHECK(bam.put(kBgzfEof, sizeof(kBgzfEof), file_at));
+    file_at += sizeof(kBgzfEof);
+    hc.lap("encoded + written");
+    // ---- the index
+    const std::vector<uint8_t> index = bam_build_index(n_ref, n_rows, h_key.data(), h_span.data(), h_count.data(), h_off.data(), H, block, coff);
+    CHECK(bai.open(bai_path)); CHECK(bai.put(index.data(), index.size(), 0));
+    hc.lap("indexed");
+    // The rows' host arrays (84 MB for 3 M rows) go here, in front of the scope's wait, not behind it as the call's last act: freed
+    // last, the NEXT call's first kernels (SamPrep::build) took 15 to 20 ms longer, in system time (profiles/pool_scope_ab.md).
+    // Nothing is on its way into them: the stream was waited for behind their copies.
+    std::vector<unsigned long long>().swap(h_key); std::vector<unsigned long long>().swap(h_count); std::vector<unsigned long long>().swap(h_off);
+    std::vector<uint32_t>().swap(h_span);
+    CHECK(commit_all({&bai, &bam}));  // (a failed .bai takes the .bam with it; every chunk has been taken, nothing is still on its way)
+    if (n_records_out) *n_records_out = (int64_t)records;
+    if (n_stream_bytes_out) *n_stream_bytes_out = (int64_t)stream_bytes;
+    if (n_file_bytes_out) *n_file_bytes_out = (int64_t)file_at;
+    return 0;
 }
 
 // bam_huff_lengths (kernels_bam.hpp) alone on the device: the code lengths of counts[n_sym] under the limit max_bits
@@ -335,21 +307,14 @@ extern "C" int mirge_bam_huffman_probe(mirge_ctx* c, const uint32_t* counts, int
     if (!c || !counts || !lengths_out || n_sym < 1 || n_sym > MIRGE_BAM_HUFF_MAX || max_bits < 1 || max_bits > 15 || (1 << max_bits) < n_sym)
         return fail(-1, "mirge_bam_huffman_probe: 1 .. " + std::to_string(MIRGE_BAM_HUFF_MAX) + " symbols, max_bits 1 .. 15 with 2^max_bits >= the symbols");
     HIPOK(hipSetDevice(c->device));
-    uint32_t* d_cnt = nullptr;
-    uint8_t* d_len = nullptr;
-    int rc = 0;
-    do {
-        if ((rc = dalloc(c, &d_cnt, (size_t)n_sym))) break;
-        if ((rc = dalloc(c, &d_len, (size_t)n_sym + 16))) break;
-        hipError_t e = hipMemcpyAsync(d_cnt, counts, (size_t)n_sym * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_bam_huff_probe, dim3(1), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_cnt, (uint32_t)n_sym, (uint32_t)max_bits, d_len);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(lengths_out, d_len, (size_t)n_sym, hipMemcpyDeviceToHost, c->stream);
-        { const hipError_t e2 = hipStreamSynchronize(c->stream); if (e == hipSuccess) e = e2; }
-        if (e != hipSuccess) rc = fail(-2, std::string("mirge_bam_huffman_probe: ") + hipGetErrorString(e));
-    } while (0);
-    c->release(d_cnt); c->release(d_len);
-    return rc;
+    uint32_t* d_cnt;
+    uint8_t* d_len;
+    PoolScope scope(c);
+    CHECK(scope.get(&d_cnt, (size_t)n_sym)); CHECK(scope.get(&d_len, (size_t)n_sym + 16));
+    HIPOK(hipMemcpyAsync(d_cnt, counts, (size_t)n_sym * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_bam_huff_probe, dim3(1), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_cnt, (uint32_t)n_sym, (uint32_t)max_bits, d_len);
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(lengths_out, d_len, (size_t)n_sym, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    return 0;
 }

@@ -4,11 +4,13 @@
 // sections and every kept level's blocks, group by group through StagePipe (native_stage.hpp), and last the indexes and the
 // front of the file from the sizes and bounds copied back (bw_layout.hpp).  MIRGE_BW_SECTION_ITEMS / MIRGE_BW_ZOOM_BASE /
 // MIRGE_BW_DEFLATE / MIRGE_BW_CHUNK_BYTES are read per call.  Both exports write to `<path>.tmp` (OutFile) and rename when every file is whole.
+// The job's blocks are the calling export's (PoolScope); the job stands in front of that scope, for copies from the device fill its words.
 #pragma once
 #include "bw_layout.hpp"
 
 struct BwJob {
     mirge_ctx* c;
+    PoolScope* scope = nullptr;  // write()'s
     std::string who;
     CovDev& dev;
     uint32_t n_rank = 0, S = MIRGE_BW_MAX_SECTION, base = 64;
@@ -23,7 +25,10 @@ struct BwJob {
     BwPart* d_part = nullptr;
     uint8_t *d_slots = nullptr, *d_out[2] = {nullptr, nullptr};
     std::vector<BwRec*> d_recs;
-    unsigned long long max_depth[2] = {0, 0};
+    unsigned long long max_depth[2] = {0, 0}, n_k = 0;  // (with herr, pick and part: what copies from the device fill)
+    uint32_t herr = MIRGE_BW_NONE;
+    std::vector<unsigned long long> pick;
+    std::vector<BwPart> part;
     OutFile out[2];  // the strands' files, written as `<path>.tmp`: both are renamed, or neither stays (commit_all)
 
     BwJob(mirge_ctx* c_, const std::string& w, CovDev& d) : c(c_), who(w), dev(d), out{{w, true}, {w, true}} {}
@@ -60,7 +65,7 @@ struct BwJob {
     int scan64(size_t n) {  // d_cnt[0 .. n] -> d_cnt_off
         size_t tb = 0;
         HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt, d_cnt_off, (int)(n + 1), c->stream));
-        CHECK(dev.need_tmp(c, tb));
+        CHECK(dev.need_tmp(*scope, tb));
         HIPOK(hipcub::DeviceScan::ExclusiveSum(dev.tmp, tb, d_cnt, d_cnt_off, (int)(n + 1), c->stream));
         return 0;
     }
@@ -70,18 +75,17 @@ struct BwJob {
         if (nb == 0) return 0;
         const uint32_t payload = records ? S * 32u : 24u + S * 12u, stride = (payload + 11u + 15u) & ~15u;
         const size_t G = std::min(nb, std::max<size_t>(1, chunk / stride)), buf = G * stride;
-        c->release(d_blk); d_blk = nullptr; c->release(d_slots); d_slots = nullptr;
-        for (int h = 0; h < 2; h++) { c->release(d_out[h]); d_out[h] = nullptr; }
-        c->release(d_sizes); d_sizes = nullptr; c->release(d_off); d_off = nullptr; c->release(d_bounds); d_bounds = nullptr;
-        CHECK(dalloc(c, &d_blk, nb)); CHECK(dalloc(c, &d_slots, buf)); CHECK(dalloc(c, &d_out[0], buf)); CHECK(dalloc(c, &d_out[1], buf));
-        CHECK(dalloc(c, &d_sizes, G + 1)); CHECK(dalloc(c, &d_off, G + 1)); CHECK(dalloc(c, &d_bounds, 3 * G));
+        scope->give(d_blk); scope->give(d_slots); scope->give(d_out[0]); scope->give(d_out[1]);  // (the stretch before this one's)
+        scope->give(d_sizes); scope->give(d_off); scope->give(d_bounds);
+        CHECK(scope->get(&d_blk, nb)); CHECK(scope->get(&d_slots, buf)); CHECK(scope->get(&d_out[0], buf)); CHECK(scope->get(&d_out[1], buf));
+        CHECK(scope->get(&d_sizes, G + 1)); CHECK(scope->get(&d_off, G + 1)); CHECK(scope->get(&d_bounds, 3 * G));
+        std::vector<uint32_t> h_sizes(G), h_bounds(3 * G);  // (in front of the pipe: it waits for the stream on its way out)
         StagePipe pipe(c, who, "the copy of a group of blocks failed");
         CHECK(pipe.ensure(buf));
         HIPOK(hipMemcpyAsync(d_blk, blk.data(), nb * sizeof(BwBlk), hipMemcpyHostToDevice, c->stream));
         size_t tb = 0;
         HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_sizes, d_off, (int)(G + 1), c->stream));
-        CHECK(dev.need_tmp(c, tb));
-        std::vector<uint32_t> h_sizes(G), h_bounds(3 * G);
+        CHECK(dev.need_tmp(*scope, tb));
         uint64_t at[2] = {0, 0};
         size_t bytes[2] = {0, 0};
         auto take = [&](unsigned long long g) -> int { return file.put(pipe.half(g), bytes[g & 1], at[g & 1]); };  // group g is in its half
@@ -136,10 +140,10 @@ struct BwJob {
         std::vector<BwZoomHead> zoom;
         std::vector<std::vector<BwBlk>> zblk;
         std::vector<uint64_t> zcount;
-        for (auto p : d_recs) c->release(p);
+        for (auto p : d_recs) scope->give(p);
         d_recs.clear();
         unsigned long long prev = n;
-        std::vector<unsigned long long> pick((size_t)n_rank + 1);
+        pick.assign((size_t)n_rank + 1, 0);
         for (int k = 0; k < MIRGE_BW_MAX_LEVELS && n; k++) {
             const unsigned long long R64 = (unsigned long long)base << (2 * k);
             if (R64 > MIRGE_BW_MAX_REDUCTION) break;
@@ -148,13 +152,13 @@ struct BwJob {
             { LaunchScope ls(c, "k_bw_zoom_count", (double)n);
               hipLaunchKernelGGL(k_bw_zoom_count, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, dev.r, r0, r1, R, d_cnt); }
             CHECK(scan64(n));
-            unsigned long long n_k = 0;
+            n_k = 0;
             HIPOK(hipMemcpyAsync(&n_k, d_cnt_off + n, 8, hipMemcpyDeviceToHost, c->stream));
             HIPOK(hipStreamSynchronize(c->stream));
             if (2 * n_k > prev) break;
-            BwRec* recs = nullptr;
-            c->release(d_rec_run); d_rec_run = nullptr; c->release(d_rec_bin); d_rec_bin = nullptr;
-            CHECK(dalloc(c, &d_rec_run, (size_t)n_k)); CHECK(dalloc(c, &d_rec_bin, (size_t)n_k)); CHECK(dalloc(c, &recs, (size_t)n_k));
+            BwRec* recs;
+            scope->give(d_rec_run); scope->give(d_rec_bin);
+            CHECK(scope->get(&d_rec_run, (size_t)n_k)); CHECK(scope->get(&d_rec_bin, (size_t)n_k)); CHECK(scope->get(&recs, (size_t)n_k));
             d_recs.push_back(recs);
             { LaunchScope ls(c, "k_bw_zoom_bins", (double)n);
               hipLaunchKernelGGL(k_bw_zoom_bins, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, dev.r, r0, r1, R, (const unsigned long long*)d_cnt_off, d_rec_run, d_rec_bin); }
@@ -175,9 +179,9 @@ struct BwJob {
         // ---- the total summary: the sections' partials in section order
         BwTotals tot;
         if (!secs.empty()) {
-            c->release(d_blk); d_blk = nullptr; c->release(d_part); d_part = nullptr;
-            CHECK(dalloc(c, &d_blk, secs.size())); CHECK(dalloc(c, &d_part, secs.size()));
-            std::vector<BwPart> part(secs.size());
+            scope->give(d_blk); scope->give(d_part);
+            CHECK(scope->get(&d_blk, secs.size())); CHECK(scope->get(&d_part, secs.size()));
+            part.assign(secs.size(), BwPart{});
             HIPOK(hipMemcpyAsync(d_blk, secs.data(), secs.size() * sizeof(BwBlk), hipMemcpyHostToDevice, c->stream));
             { LaunchScope ls(c, "k_bw_summary", (double)secs.size());
               hipLaunchKernelGGL(k_bw_summary, dim3(grid_for(c, secs.size())), dim3(MIRGE_BLOCK), 0, c->stream, dev.r, (const BwBlk*)d_blk, (uint32_t)secs.size(), d_part); }
@@ -230,15 +234,16 @@ struct BwJob {
         return 0;
     }
     // the runs of dev -> paths[0] (and paths[1] when stranded); err_out = {3, rank, end, LN} for a run beyond its chromosome
-    int write(bool stranded, const char* const* paths, int64_t* stats, int64_t* err_out) {
+    int write(PoolScope& sc, bool stranded, const char* const* paths, int64_t* stats, int64_t* err_out) {
+        scope = &sc;
         const uint32_t n_str = stranded ? 2u : 1u, n_runs = (uint32_t)dev.n_runs;
         const size_t nq = (size_t)n_str * n_rank + 1;
         first.assign(nq, 0);
-        CHECK(dalloc(c, &d_ln, (size_t)n_rank)); CHECK(dalloc(c, &d_cid, (size_t)n_rank)); CHECK(dalloc(c, &d_first, nq));
-        CHECK(dalloc(c, &d_err, (size_t)1)); CHECK(dalloc(c, &d_max, (size_t)2)); CHECK(dalloc(c, &d_pick, (size_t)n_rank + 1));
-        CHECK(dalloc(c, &d_cnt, (size_t)n_runs + 1)); CHECK(dalloc(c, &d_cnt_off, (size_t)n_runs + 1));
+        CHECK(sc.get(&d_ln, (size_t)n_rank)); CHECK(sc.get(&d_cid, (size_t)n_rank)); CHECK(sc.get(&d_first, nq));
+        CHECK(sc.get(&d_err, (size_t)1)); CHECK(sc.get(&d_max, (size_t)2)); CHECK(sc.get(&d_pick, (size_t)n_rank + 1));
+        CHECK(sc.get(&d_cnt, (size_t)n_runs + 1)); CHECK(sc.get(&d_cnt_off, (size_t)n_runs + 1));
         if (n_runs) {
-            uint32_t herr = MIRGE_BW_NONE;
+            herr = MIRGE_BW_NONE;
             HIPOK(hipMemcpyAsync(d_ln, h_ln.data(), (size_t)n_rank * 4, hipMemcpyHostToDevice, c->stream));
             HIPOK(hipMemcpyAsync(d_cid, h_cid.data(), (size_t)n_rank * 4, hipMemcpyHostToDevice, c->stream));
             HIPOK(hipMemsetAsync(d_err, 0xFF, 4, c->stream));
@@ -268,14 +273,6 @@ struct BwJob {
         }
         return commit_all({&out[0], &out[1]});  // (renamed only now that every file is whole)
     }
-    // after write(), failed or not: the device memory goes back; a failed call's files go with the job (OutFile)
-    void release() {
-        (void)hipStreamSynchronize(c->stream);
-        for (auto p : d_recs) c->release(p);
-        for (void* p : {(void*)d_ln, (void*)d_cid, (void*)d_first, (void*)d_err, (void*)d_sizes, (void*)d_off, (void*)d_bounds, (void*)d_rec_run, (void*)d_rec_bin,
-                        (void*)d_max, (void*)d_cnt, (void*)d_cnt_off, (void*)d_pick, (void*)d_blk, (void*)d_part, (void*)d_slots, (void*)d_out[0], (void*)d_out[1]})
-            c->release(p);
-    }
 };
 
 extern "C" int mirge_bigwig_from_intervals(mirge_ctx* c, int64_t n, const int32_t* chrom_rank, const int64_t* start, const int32_t* len, const uint32_t* weight,
@@ -293,20 +290,13 @@ extern "C" int mirge_bigwig_from_intervals(mirge_ctx* c, int64_t n, const int32_
     CovDev dev;
     BwJob job(c, who, dev);
     const char* paths[2] = {path, stranded ? path_minus : nullptr};
-    auto run = [&]() -> int {
-        CHECK(job.env());
-        CHECK(job.chromosomes(n_rank, rank_names, rank_name_off, chrom_size, chrom_id));
-        for (size_t i = 0; i < sn; i++) if (chrom_rank[i] >= n_rank) return fail(-1, who + ": a chromosome rank beyond the names given");
-        CHECK(up.upload(c, sn, chrom_rank, start, len, weight, minus));
-        CHECK(dev.runs(c, who, up.intervals(), sn, (uint32_t)n_rank, stranded != 0));
-        return job.write(stranded != 0, paths, stats_out, err_out);
-    };
-    const int rc = run();
-    job.release();
-    c->drain();
-    dev.release(c);
-    up.release(c);
-    return rc;
+    PoolScope scope(c);
+    CHECK(job.env());
+    CHECK(job.chromosomes(n_rank, rank_names, rank_name_off, chrom_size, chrom_id));
+    for (size_t i = 0; i < sn; i++) if (chrom_rank[i] >= n_rank) return fail(-1, who + ": a chromosome rank beyond the names given");
+    CHECK(up.upload(scope, sn, chrom_rank, start, len, weight, minus));
+    CHECK(dev.runs(scope, who, up.intervals(), sn, (uint32_t)n_rank, stranded != 0));
+    return job.write(scope, stranded != 0, paths, stats_out, err_out);
 }
 
 extern "C" int mirge_bigwig_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
@@ -325,20 +315,13 @@ extern "C" int mirge_bigwig_write_device(mirge_ctx* c, const mirge_reads* U, con
     CovDev dev;
     BwJob job(c, who, dev);
     const char* paths[2] = {path, stranded ? path_minus : nullptr};
-    auto run = [&]() -> int {
-        CHECK(job.env());
-        CHECK(job.chromosomes(n_rank, rank_names, rank_name_off, chrom_size, chrom_id));
-        CHECK(in.build(c, who, U, res, order, sample, class_pass, n_class, passes, n_pass, chrom_rank, chrom_rank_off, n_rank, err_out, hc));
-        CHECK(dev.runs(c, who, in.intervals(), in.n_rows, (uint32_t)n_rank, stranded != 0));
-        hc.lap("runs");
-        CHECK(job.write(stranded != 0, paths, stats_out, err_out));
-        hc.lap("files written");
-        return 0;
-    };
-    const int rc = run();
-    job.release();
-    c->drain();
-    in.release(c);
-    dev.release(c);
-    return rc;
+    PoolScope scope(c);
+    CHECK(job.env());
+    CHECK(job.chromosomes(n_rank, rank_names, rank_name_off, chrom_size, chrom_id));
+    CHECK(in.build(scope, who, U, res, order, sample, class_pass, n_class, passes, n_pass, chrom_rank, chrom_rank_off, n_rank, err_out, hc));
+    CHECK(dev.runs(scope, who, in.intervals(), in.n_rows, (uint32_t)n_rank, stranded != 0));
+    hc.lap("runs");
+    CHECK(job.write(scope, stranded != 0, paths, stats_out, err_out));
+    hc.lap("files written");
+    return 0;
 }

@@ -62,7 +62,8 @@ struct mirge_ctx {
     // before the final join (a block still in use on one stream could be handed to the other).
     bool overlap_mode = false;
     int n_cu = 256;
-    // pool
+    // pool: stream-ordered reuse on the one main stream.  The step's hot path (pack, collapse, cascade, count join) calls alloc / release /
+    // defer itself; a report or export call owns its blocks through a PoolScope (below).  mirge_ctx_pool_stats reads these three.
     std::multimap<size_t, void*> free_blocks;
     std::unordered_map<void*, size_t> sizes;
     size_t pool_bytes = 0;
@@ -212,6 +213,32 @@ struct mirge_ctx {
 
 template <typename T>
 static int dalloc(mirge_ctx* c, T** out, size_t count) { return c->alloc((void**)out, count * sizeof(T)); }
+
+// The pool blocks of one report or export call: all back in the pool on every way out, behind a wait for the main stream.  A host
+// buffer that an async copy of the call reads or writes is declared BEFORE the scope (destroyed after the scope's wait), or has a
+// wait of its own behind the copy.  Not for the step's hot path (defer, fork/join ordering: native_collapse.hpp and its kin).
+struct PoolScope {
+    mirge_ctx* const c;
+    std::vector<void*> held;
+    explicit PoolScope(mirge_ctx* ctx) : c(ctx) {}
+    PoolScope(const PoolScope&) = delete;
+    PoolScope& operator=(const PoolScope&) = delete;
+    template <class T> int get(T** out, size_t count) {  // dalloc, remembered
+        CHECK(dalloc(c, out, count));
+        held.push_back(*out);
+        return 0;
+    }
+    template <class T> void give(T*& p) {  // back to the pool now, forgotten, and p nulled (nullptr: nothing) -- a scratch block regrown, a per-file block
+        auto it = std::find(held.begin(), held.end(), (void*)p);
+        if (it != held.end()) { held.erase(it); c->release((void*)p); }
+        p = nullptr;
+    }
+    ~PoolScope() {
+        (void)hipStreamSynchronize(c->stream);
+        c->drain();
+        for (void* p : held) c->release(p);
+    }
+};
 
 // launch bracket: HIP events on the ctx stream around each kernel when profiling is on
 struct LaunchScope {
@@ -422,6 +449,14 @@ extern "C" int mirge_ctx_sync(mirge_ctx* c) {
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     HIPOK(hipStreamSynchronize(c->stream));
     c->drain();
+    return 0;
+}
+
+extern "C" int mirge_ctx_pool_stats(mirge_ctx* c, int64_t out[3]) {
+    if (!c || !out) return fail(-1, "mirge_ctx_pool_stats: bad argument");
+    out[0] = (int64_t)c->pool_bytes;
+    out[1] = (int64_t)c->sizes.size() - (int64_t)c->free_blocks.size();
+    out[2] = (int64_t)c->free_blocks.size();
     return 0;
 }
 

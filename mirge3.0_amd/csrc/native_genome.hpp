@@ -109,7 +109,7 @@ extern "C" int mirge_genome_create_packed(mirge_ctx* c, const uint8_t* packed, i
 }
 
 // ---- the query tables of one scan (both exports below): queries on the device, their pieces sorted into the key tables, the
-// presence bitmaps, the scan's arguments.  genome_tables_build fills it, genome_tables_release gives everything back.
+// presence bitmaps, the scan's arguments.  genome_tables_build fills it from a PoolScope: the call's, or one batch's.
 struct GenomeTables {
     char* d_ascii = nullptr; int64_t* d_off = nullptr; GenomeQS* d_qs = nullptr;
     uint64_t *d_keys = nullptr, *d_skeys = nullptr, *d_bmoff = nullptr;
@@ -117,14 +117,11 @@ struct GenomeTables {
     unsigned long long* d_counts = nullptr; void* d_tmp = nullptr;
     GenomeScanArgs sa{};
     int64_t n = 0;
+    // what genome_tables_build's copies read and fill: a GenomeTables stands in front of the scope its blocks come from
+    std::vector<int64_t> off;
+    uint64_t bm_off[MIRGE_GENOME_MAXK + 1] = {0};
+    uint32_t tab[2 * (MIRGE_GENOME_MAXK + 1)] = {0};
 };
-
-static void genome_tables_release(mirge_ctx* c, GenomeTables& t) {
-    for (void* p : {(void*)t.d_ascii, (void*)t.d_off, (void*)t.d_qs, (void*)t.d_keys, (void*)t.d_skeys, (void*)t.d_vals, (void*)t.d_svals,
-                    (void*)t.d_bmoff, (void*)t.d_bitmap, (void*)t.d_tab, (void*)t.d_counts, t.d_tmp})
-        c->release(p);
-    t = GenomeTables{};
-}
 
 static int genome_check_args(const char* who, mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t n,
                              int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3) {
@@ -148,8 +145,9 @@ static int genome_check_args(const char* who, mirge_ctx* c, const mirge_genome* 
 }
 
 // queries [q0, q0 + n) of the caller's arrays -> tables and scan arguments; counts zeroed.  The stream is synchronised on return.
-static int genome_tables_build(mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t q0, int64_t n,
+static int genome_tables_build(PoolScope& scope, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t q0, int64_t n,
                                int32_t n_mm, int32_t seedlen, int32_t maxtotal, int32_t trim5, int32_t trim3, int32_t norc, GenomeTables& t) {
+    mirge_ctx* const c = scope.c;
     const int P = n_mm + 1;
     const uint32_t nqs = (uint32_t)(2 * n), nk = nqs * (uint32_t)P;
     // Key length.  A genome position probes every table, and a random k-mer is one of the n_keys keys of the longest table with
@@ -159,29 +157,32 @@ static int genome_tables_build(mirge_ctx* c, const mirge_genome* g, const char* 
     // own length, where the rate is their count over 4^length: the candidates there are the alignments such a short piece has.
     int kmax = 8;
     while (kmax < MIRGE_GENOME_MAXK && (1ull << (2 * kmax)) < 32ull * nk) kmax++;
-    uint64_t bm_off[MIRGE_GENOME_MAXK + 1] = {0};
+    uint64_t* const bm_off = t.bm_off;
+    std::vector<int64_t>& off = t.off;
+    uint32_t* const tab = t.tab;
     uint64_t bm_words = 0;
+    bm_off[0] = 0;
     for (int k = 1; k <= kmax; k++) { bm_off[k] = bm_words; bm_words += std::max<uint64_t>(1, (1ull << (2 * k)) / 32); }
     size_t tmp_bytes = 0;
     HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
                                               (uint32_t*)nullptr, (int)nk, 0, 64, c->stream));
     t.n = n;
     const int64_t b0 = offsets[q0], nb = offsets[q0 + n] - b0;
-    std::vector<int64_t> off((size_t)n + 1);
+    off.resize((size_t)n + 1);
     for (int64_t i = 0; i <= n; i++) off[(size_t)i] = offsets[q0 + i] - b0;
-    CHECK(dalloc(c, &t.d_ascii, (size_t)std::max<int64_t>(nb, 1)));
-    CHECK(dalloc(c, &t.d_off, (size_t)n + 1));
-    CHECK(dalloc(c, &t.d_qs, nqs));
-    CHECK(dalloc(c, &t.d_keys, nk)); CHECK(dalloc(c, &t.d_skeys, nk));
-    CHECK(dalloc(c, &t.d_vals, nk)); CHECK(dalloc(c, &t.d_svals, nk));
-    CHECK(dalloc(c, &t.d_bmoff, MIRGE_GENOME_MAXK + 1));
-    CHECK(dalloc(c, &t.d_bitmap, bm_words));
-    CHECK(dalloc(c, &t.d_tab, 2 * (MIRGE_GENOME_MAXK + 1)));
-    CHECK(dalloc(c, &t.d_counts, (size_t)n * 3));
-    CHECK(c->alloc(&t.d_tmp, tmp_bytes));
+    CHECK(scope.get(&t.d_ascii, (size_t)std::max<int64_t>(nb, 1)));
+    CHECK(scope.get(&t.d_off, (size_t)n + 1));
+    CHECK(scope.get(&t.d_qs, nqs));
+    CHECK(scope.get(&t.d_keys, nk)); CHECK(scope.get(&t.d_skeys, nk));
+    CHECK(scope.get(&t.d_vals, nk)); CHECK(scope.get(&t.d_svals, nk));
+    CHECK(scope.get(&t.d_bmoff, MIRGE_GENOME_MAXK + 1));
+    CHECK(scope.get(&t.d_bitmap, bm_words));
+    CHECK(scope.get(&t.d_tab, 2 * (MIRGE_GENOME_MAXK + 1)));
+    CHECK(scope.get(&t.d_counts, (size_t)n * 3));
+    CHECK(scope.get((uint8_t**)&t.d_tmp, tmp_bytes));
     if (nb) HIPOK(hipMemcpyAsync(t.d_ascii, queries + b0, (size_t)nb, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemcpyAsync(t.d_off, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPOK(hipMemcpyAsync(t.d_bmoff, bm_off, sizeof(bm_off), hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(t.d_bmoff, bm_off, sizeof(t.bm_off), hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemsetAsync(t.d_bitmap, 0, bm_words * 4, c->stream));
     HIPOK(hipMemsetAsync(t.d_tab, 0, 2 * (MIRGE_GENOME_MAXK + 1) * 4, c->stream));
     HIPOK(hipMemsetAsync(t.d_counts, 0, (size_t)n * 3 * 8, c->stream));
@@ -196,8 +197,7 @@ static int genome_tables_build(mirge_ctx* c, const mirge_genome* g, const char* 
         hipLaunchKernelGGL(k_genome_index, dim3((nk + 255) / 256), dim3(256), 0, c->stream, t.d_skeys, nk, t.d_bmoff, t.d_bitmap, t.d_tab,
                            t.d_tab + MIRGE_GENOME_MAXK + 1);
     }
-    uint32_t tab[2 * (MIRGE_GENOME_MAXK + 1)];
-    HIPOK(hipMemcpyAsync(tab, t.d_tab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(tab, t.d_tab, sizeof(t.tab), hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
     GenomeScanArgs& sa = t.sa;
     sa = GenomeScanArgs{};
@@ -234,18 +234,12 @@ extern "C" int mirge_genome_align_counts(mirge_ctx* c, const mirge_genome* g, co
     if (n == 0) return 0;
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     GenomeTables t;
-    auto run = [&]() -> int {
-        CHECK(genome_tables_build(c, g, queries, offsets, 0, n, n_mm, seedlen, maxtotal, trim5, trim3, 0, t));
-        std::vector<unsigned long long> h;
-        CHECK(genome_count_pass(c, g, t, h));
-        for (size_t i = 0; i < h.size(); i++) out[i] = h[i] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)h[i];
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    genome_tables_release(c, t);
-    return rc;
+    std::vector<unsigned long long> h;
+    PoolScope scope(c);
+    CHECK(genome_tables_build(scope, g, queries, offsets, 0, n, n_mm, seedlen, maxtotal, trim5, trim3, 0, t));
+    CHECK(genome_count_pass(c, g, t, h));
+    for (size_t i = 0; i < h.size(); i++) out[i] = h[i] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)h[i];
+    return 0;
 }
 
 // ---- alignments with positions (mirge_genome_align_loci[_strata]): the count pass, then the same scan as a fill pass, then two
@@ -287,107 +281,103 @@ extern "C" int mirge_genome_align_loci_strata(mirge_ctx* c, const mirge_genome* 
     if (const char* e = std::getenv("MIRGE_LOCI_BATCH")) { const long long v = std::atoll(e); if (v > 0 && v < batch) batch = v; }
     const int64_t n_batches = (n + batch - 1) / batch;
     GenomeTables t;
-    uint64_t *d_range = nullptr, *d_pos = nullptr, *d_pos2 = nullptr, *d_roff = nullptr;
-    uint32_t *d_cursor = nullptr, *d_meta = nullptr, *d_meta2 = nullptr, *d_flag = nullptr, *d_rq = nullptr, *d_rref = nullptr;
-    uint8_t *d_rs = nullptr, *d_rmm = nullptr, *d_best = nullptr; void* d_tmp = nullptr;
-    auto run = [&]() -> int {
-        // ---- pass 1: every query's total; what it reports (all of them, or none when -m caps it) -> its range of the records
-        std::vector<uint64_t> range((size_t)n + 1, 0);
-        std::vector<unsigned long long> h;
-        std::vector<uint8_t> best(strata ? (size_t)n : 0, 0);
-        for (int64_t b = 0; b < n_batches; b++) {
-            const int64_t q0 = b * batch, nq = std::min(batch, n - q0);
-            CHECK(genome_tables_build(c, g, queries, offsets, q0, nq, n_mm, seedlen, maxtotal, trim5, trim3, norc ? 1 : 0, t));
-            t.sa.strata = strata ? 1 : 0;
-            CHECK(genome_count_pass(c, g, t, h));
-            for (int64_t i = 0; i < nq; i++) {
-                const unsigned long long* hc = &h[(size_t)i * 3];
-                const uint64_t tot = hc[0] + hc[1] + hc[2];
-                totals[q0 + i] = tot;
-                uint64_t rep = tot;  // what the query reports: everything, or its best stratum
-                if (strata) {
-                    const int b = hc[0] ? 0 : (hc[1] ? 1 : 2);
-                    best[(size_t)(q0 + i)] = (uint8_t)b;
-                    rep = hc[b];
-                }
-                range[(size_t)(q0 + i) + 1] = (max_loci && rep > (uint64_t)max_loci) ? 0 : rep;
+    uint64_t *d_range, *d_pos, *d_pos2, *d_roff;
+    uint32_t *d_cursor, *d_meta, *d_meta2, *d_flag, *d_rq, *d_rref;
+    uint8_t *d_rs, *d_rmm, *d_best = nullptr; void* d_tmp;
+    std::vector<uint64_t> range((size_t)n + 1, 0);
+    std::vector<unsigned long long> h;
+    std::vector<uint8_t> best(strata ? (size_t)n : 0, 0);
+    std::vector<uint32_t> cur;
+    uint32_t flag = 0;
+    PoolScope scope(c);
+    // ---- pass 1: every query's total; what it reports (all of them, or none when -m caps it) -> its range of the records
+    for (int64_t b = 0; b < n_batches; b++) {
+        const int64_t q0 = b * batch, nq = std::min(batch, n - q0);
+        std::optional<PoolScope> one;  // of several batches, each has its tables to itself; one batch's serve the fill pass as they are
+        if (n_batches > 1) one.emplace(c);
+        CHECK(genome_tables_build(one ? *one : scope, g, queries, offsets, q0, nq, n_mm, seedlen, maxtotal, trim5, trim3, norc ? 1 : 0, t));
+        t.sa.strata = strata ? 1 : 0;
+        CHECK(genome_count_pass(c, g, t, h));
+        for (int64_t i = 0; i < nq; i++) {
+            const unsigned long long* hc = &h[(size_t)i * 3];
+            const uint64_t tot = hc[0] + hc[1] + hc[2];
+            totals[q0 + i] = tot;
+            uint64_t rep = tot;  // what the query reports: everything, or its best stratum
+            if (strata) {
+                const int b = hc[0] ? 0 : (hc[1] ? 1 : 2);
+                best[(size_t)(q0 + i)] = (uint8_t)b;
+                rep = hc[b];
             }
-            if (n_batches > 1) genome_tables_release(c, t);  // one batch: its tables serve the fill pass as they are
+            range[(size_t)(q0 + i) + 1] = (max_loci && rep > (uint64_t)max_loci) ? 0 : rep;
         }
-        for (int64_t i = 0; i < n; i++) range[(size_t)i + 1] += range[(size_t)i];
-        const uint64_t n_rec = range[(size_t)n];
-        if (n_rec > (uint64_t)MIRGE_LOCI_MAX_RECORDS)
-            return fail(-1, "mirge_genome_align_loci: " + std::to_string(n_rec) + " alignments to report; cap repeats with max_loci");
-        if (n_rec == 0) { *out = res.release(); return 0; }
-        CHECK(dalloc(c, &d_range, (size_t)n + 1)); CHECK(dalloc(c, &d_cursor, (size_t)n)); CHECK(dalloc(c, &d_flag, 1));
-        CHECK(dalloc(c, &d_pos, n_rec)); CHECK(dalloc(c, &d_pos2, n_rec)); CHECK(dalloc(c, &d_meta, n_rec)); CHECK(dalloc(c, &d_meta2, n_rec));
-        HIPOK(hipMemcpyAsync(d_range, range.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemsetAsync(d_cursor, 0, (size_t)n * 4, c->stream));
-        HIPOK(hipMemsetAsync(d_flag, 0, 4, c->stream));
-        if (strata) {
-            CHECK(dalloc(c, &d_best, (size_t)n));
-            HIPOK(hipMemcpyAsync(d_best, best.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    for (int64_t i = 0; i < n; i++) range[(size_t)i + 1] += range[(size_t)i];
+    const uint64_t n_rec = range[(size_t)n];
+    if (n_rec > (uint64_t)MIRGE_LOCI_MAX_RECORDS)
+        return fail(-1, "mirge_genome_align_loci: " + std::to_string(n_rec) + " alignments to report; cap repeats with max_loci");
+    if (n_rec == 0) { *out = res.release(); return 0; }
+    CHECK(scope.get(&d_range, (size_t)n + 1)); CHECK(scope.get(&d_cursor, (size_t)n)); CHECK(scope.get(&d_flag, 1));
+    CHECK(scope.get(&d_pos, n_rec)); CHECK(scope.get(&d_pos2, n_rec)); CHECK(scope.get(&d_meta, n_rec)); CHECK(scope.get(&d_meta2, n_rec));
+    HIPOK(hipMemcpyAsync(d_range, range.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(d_cursor, 0, (size_t)n * 4, c->stream));
+    HIPOK(hipMemsetAsync(d_flag, 0, 4, c->stream));
+    if (strata) {
+        CHECK(scope.get(&d_best, (size_t)n));
+        HIPOK(hipMemcpyAsync(d_best, best.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    // ---- pass 2: the same scan writes the records
+    for (int64_t b = 0; b < n_batches; b++) {
+        const int64_t q0 = b * batch, nq = std::min(batch, n - q0);
+        if (range[(size_t)(q0 + nq)] == range[(size_t)q0]) continue;  // nothing to report from this batch
+        std::optional<PoolScope> one;  // (several batches: this one's tables, built again)
+        if (n_batches > 1) {
+            one.emplace(c);
+            CHECK(genome_tables_build(*one, g, queries, offsets, q0, nq, n_mm, seedlen, maxtotal, trim5, trim3, norc ? 1 : 0, t));
         }
-        // ---- pass 2: the same scan writes the records
-        for (int64_t b = 0; b < n_batches; b++) {
-            const int64_t q0 = b * batch, nq = std::min(batch, n - q0);
-            if (range[(size_t)(q0 + nq)] == range[(size_t)q0]) continue;  // nothing to report from this batch
-            if (n_batches > 1) CHECK(genome_tables_build(c, g, queries, offsets, q0, nq, n_mm, seedlen, maxtotal, trim5, trim3, norc ? 1 : 0, t));
-            t.sa.range = d_range + q0; t.sa.cursor = d_cursor + q0; t.sa.rec_pos = d_pos; t.sa.rec_meta = d_meta; t.sa.overflow = d_flag;
-            t.sa.query_base = (uint32_t)q0;
-            t.sa.strata = strata ? 1 : 0; t.sa.best = strata ? d_best + q0 : nullptr;
-            if (t.sa.ntab && g->n_bases) {
-                const uint64_t strips = (g->n_bases + MIRGE_GENOME_STRIP - 1) / MIRGE_GENOME_STRIP;
-                LaunchScope ls(c, "k_genome_scan_fill", (double)g->n_bases);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_genome_scan<true>), dim3((unsigned)grid_for(c, strips)), dim3(256), 0, c->stream, t.sa);
-            }
-            HIPOK(hipStreamSynchronize(c->stream));
-            if (n_batches > 1) genome_tables_release(c, t);
+        t.sa.range = d_range + q0; t.sa.cursor = d_cursor + q0; t.sa.rec_pos = d_pos; t.sa.rec_meta = d_meta; t.sa.overflow = d_flag;
+        t.sa.query_base = (uint32_t)q0;
+        t.sa.strata = strata ? 1 : 0; t.sa.best = strata ? d_best + q0 : nullptr;
+        if (t.sa.ntab && g->n_bases) {
+            const uint64_t strips = (g->n_bases + MIRGE_GENOME_STRIP - 1) / MIRGE_GENOME_STRIP;
+            LaunchScope ls(c, "k_genome_scan_fill", (double)g->n_bases);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_genome_scan<true>), dim3((unsigned)grid_for(c, strips)), dim3(256), 0, c->stream, t.sa);
         }
-        std::vector<uint32_t> cur((size_t)n);
-        uint32_t flag = 0;
-        HIPOK(hipMemcpyAsync(cur.data(), d_cursor, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
         HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        for (int64_t i = 0; i < n && !flag; i++) flag = cur[(size_t)i] != range[(size_t)i + 1] - range[(size_t)i];
-        if (flag) return fail(-1, "mirge_genome_align_loci: the fill pass and the count pass disagree");
-        // ---- order: stable by (query, strand), then stable by stream position, which rises with (reference, offset)
-        int qbits = 1, pbits = 1;
-        while (qbits < 29 && (1ll << qbits) < n) qbits++;
-        while (pbits < 64 && (1ull << pbits) <= g->n_bases) pbits++;
-        size_t tb1 = 0, tb2 = 0;
-        HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, d_meta, d_meta2, d_pos, d_pos2, (int)n_rec, 2, 3 + qbits, c->stream));
-        HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, d_pos2, d_pos, d_meta2, d_meta, (int)n_rec, 0, pbits, c->stream));
-        CHECK(c->alloc(&d_tmp, std::max(tb1, tb2)));
-        HIPOK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb1, d_meta, d_meta2, d_pos, d_pos2, (int)n_rec, 2, 3 + qbits, c->stream));
-        HIPOK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb2, d_pos2, d_pos, d_meta2, d_meta, (int)n_rec, 0, pbits, c->stream));
-        CHECK(dalloc(c, &d_rq, n_rec)); CHECK(dalloc(c, &d_rref, n_rec)); CHECK(dalloc(c, &d_roff, n_rec));
-        CHECK(dalloc(c, &d_rs, n_rec)); CHECK(dalloc(c, &d_rmm, n_rec));
-        {
-            LaunchScope ls(c, "k_genome_loci_finish", (double)n_rec);
-            hipLaunchKernelGGL(k_genome_loci_finish, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n_rec, d_pos,
-                               d_meta, g->s_start, g->n_str, g->str_ref, g->str_off, d_rq, d_rref, d_roff, d_rs, d_rmm);
-        }
-        res->query.resize(n_rec); res->ref.resize(n_rec); res->off.resize(n_rec); res->strand.resize(n_rec); res->mm.resize(n_rec);
-        HIPOK(hipMemcpyAsync(res->query.data(), d_rq, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(res->ref.data(), d_rref, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(res->off.data(), d_roff, n_rec * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(res->strand.data(), d_rs, n_rec, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(res->mm.data(), d_rmm, n_rec, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        *out = res.release();
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    genome_tables_release(c, t);
-    for (void* p : {(void*)d_range, (void*)d_pos, (void*)d_pos2, (void*)d_roff, (void*)d_cursor, (void*)d_meta, (void*)d_meta2, (void*)d_flag,
-                    (void*)d_rq, (void*)d_rref, (void*)d_rs, (void*)d_rmm, (void*)d_best, d_tmp})
-        c->release(p);
-    return rc;
+    }
+    cur.resize((size_t)n);
+    HIPOK(hipMemcpyAsync(cur.data(), d_cursor, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    for (int64_t i = 0; i < n && !flag; i++) flag = cur[(size_t)i] != range[(size_t)i + 1] - range[(size_t)i];
+    if (flag) return fail(-1, "mirge_genome_align_loci: the fill pass and the count pass disagree");
+    // ---- order: stable by (query, strand), then stable by stream position, which rises with (reference, offset)
+    int qbits = 1, pbits = 1;
+    while (qbits < 29 && (1ll << qbits) < n) qbits++;
+    while (pbits < 64 && (1ull << pbits) <= g->n_bases) pbits++;
+    size_t tb1 = 0, tb2 = 0;
+    HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, d_meta, d_meta2, d_pos, d_pos2, (int)n_rec, 2, 3 + qbits, c->stream));
+    HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, d_pos2, d_pos, d_meta2, d_meta, (int)n_rec, 0, pbits, c->stream));
+    CHECK(scope.get((uint8_t**)&d_tmp, std::max(tb1, tb2)));
+    HIPOK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb1, d_meta, d_meta2, d_pos, d_pos2, (int)n_rec, 2, 3 + qbits, c->stream));
+    HIPOK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb2, d_pos2, d_pos, d_meta2, d_meta, (int)n_rec, 0, pbits, c->stream));
+    CHECK(scope.get(&d_rq, n_rec)); CHECK(scope.get(&d_rref, n_rec)); CHECK(scope.get(&d_roff, n_rec));
+    CHECK(scope.get(&d_rs, n_rec)); CHECK(scope.get(&d_rmm, n_rec));
+    {
+        LaunchScope ls(c, "k_genome_loci_finish", (double)n_rec);
+        hipLaunchKernelGGL(k_genome_loci_finish, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)n_rec, d_pos,
+                           d_meta, g->s_start, g->n_str, g->str_ref, g->str_off, d_rq, d_rref, d_roff, d_rs, d_rmm);
+    }
+    res->query.resize(n_rec); res->ref.resize(n_rec); res->off.resize(n_rec); res->strand.resize(n_rec); res->mm.resize(n_rec);
+    HIPOK(hipMemcpyAsync(res->query.data(), d_rq, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(res->ref.data(), d_rref, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(res->off.data(), d_roff, n_rec * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(res->strand.data(), d_rs, n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(res->mm.data(), d_rmm, n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    *out = res.release();
+    return 0;
 }
 
 extern "C" int mirge_genome_align_loci(mirge_ctx* c, const mirge_genome* g, const char* queries, const int64_t* offsets, int64_t n,
@@ -417,81 +407,69 @@ extern "C" int mirge_loci_cluster(mirge_ctx* c, int64_t n, const uint32_t* ref, 
     }
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     const uint32_t N = (uint32_t)n;
-    uint32_t *d_ref = nullptr, *d_query = nullptr, *d_vals = nullptr, *d_perm = nullptr, *d_flag = nullptr, *d_fsum = nullptr, *d_kept = nullptr,
-             *d_ksum = nullptr, *t_ref = nullptr, *t_members = nullptr;
-    uint64_t *d_off = nullptr, *d_keys = nullptr, *d_skeys = nullptr, *t_start = nullptr;
-    unsigned long long *t_end = nullptr, *t_reads = nullptr;
-    uint8_t *d_strand = nullptr, *d_skip = nullptr, *d_dropped = nullptr, *t_strand = nullptr;
-    int32_t *d_qlen = nullptr, *d_cluster = nullptr; int64_t* d_qcount = nullptr;
-    ClusterItem *d_items = nullptr, *d_scanned = nullptr; void* d_tmp = nullptr;
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_ref, N)); CHECK(dalloc(c, &d_query, N)); CHECK(dalloc(c, &d_off, N)); CHECK(dalloc(c, &d_strand, N));
-        CHECK(dalloc(c, &d_qlen, (size_t)n_queries)); CHECK(dalloc(c, &d_qcount, (size_t)n_queries)); CHECK(dalloc(c, &d_skip, (size_t)n_refs));
-        CHECK(dalloc(c, &d_keys, N)); CHECK(dalloc(c, &d_skeys, N)); CHECK(dalloc(c, &d_vals, N)); CHECK(dalloc(c, &d_perm, N));
-        CHECK(dalloc(c, &d_items, N)); CHECK(dalloc(c, &d_scanned, N));
-        CHECK(dalloc(c, &d_flag, N)); CHECK(dalloc(c, &d_fsum, N)); CHECK(dalloc(c, &d_kept, N)); CHECK(dalloc(c, &d_ksum, N));
-        CHECK(dalloc(c, &d_dropped, N)); CHECK(dalloc(c, &d_cluster, N));
-        CHECK(dalloc(c, &t_ref, N)); CHECK(dalloc(c, &t_members, N)); CHECK(dalloc(c, &t_start, N)); CHECK(dalloc(c, &t_end, N));
-        CHECK(dalloc(c, &t_reads, N)); CHECK(dalloc(c, &t_strand, N));
-        HIPOK(hipMemcpyAsync(d_ref, ref, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_query, query, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_off, off, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_strand, strand, (size_t)N, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_qlen, qlen, (size_t)n_queries * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_qcount, qcount, (size_t)n_queries * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_skip, ref_skip, (size_t)n_refs, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemsetAsync(t_end, 0, (size_t)N * 8, c->stream));
-        HIPOK(hipMemsetAsync(t_reads, 0, (size_t)N * 8, c->stream));
-        HIPOK(hipMemsetAsync(t_members, 0, (size_t)N * 4, c->stream));
-        size_t tb = 0, tb_sort = 0, tb_scan = 0, tb_sum = 0;
-        HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, d_keys, d_skeys, d_vals, d_perm, (int)N, 0, 33, c->stream));
-        HIPOK(hipcub::DeviceScan::InclusiveScan(nullptr, tb_scan, d_items, d_scanned, ClusterScanOp(), (int)N, c->stream));
-        HIPOK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_sum, d_flag, d_fsum, (int)N, c->stream));
-        tb = std::max(tb_sort, std::max(tb_scan, tb_sum));
-        CHECK(c->alloc(&d_tmp, tb));
-        const dim3 grid((N + 255) / 256), block(256);
-        { LaunchScope ls(c, "k_cluster_keys", (double)N);
-          hipLaunchKernelGGL(k_cluster_keys, grid, block, 0, c->stream, N, d_ref, d_strand, d_keys, d_vals); }
-        HIPOK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb_sort, d_keys, d_skeys, d_vals, d_perm, (int)N, 0, 33, c->stream));
-        { LaunchScope ls(c, "k_cluster_items", (double)N);
-          hipLaunchKernelGGL(k_cluster_items, grid, block, 0, c->stream, N, d_skeys, d_perm, d_off, d_query, d_qlen, d_items); }
-        HIPOK(hipcub::DeviceScan::InclusiveScan(d_tmp, tb_scan, d_items, d_scanned, ClusterScanOp(), (int)N, c->stream));
-        { LaunchScope ls(c, "k_cluster_flags", (double)N);
-          hipLaunchKernelGGL(k_cluster_flags, grid, block, 0, c->stream, N, d_scanned, d_perm, d_off, threshold, d_flag); }
-        HIPOK(hipcub::DeviceScan::InclusiveSum(d_tmp, tb_sum, d_flag, d_fsum, (int)N, c->stream));
-        { LaunchScope ls(c, "k_cluster_kept", (double)N);
-          hipLaunchKernelGGL(k_cluster_kept, grid, block, 0, c->stream, N, d_scanned, d_flag, d_fsum, d_skip, minus_first_only, d_kept, d_dropped); }
-        HIPOK(hipcub::DeviceScan::InclusiveSum(d_tmp, tb_sum, d_kept, d_ksum, (int)N, c->stream));
-        { LaunchScope ls(c, "k_cluster_assign", (double)N);
-          const ClusterTable tab{t_ref, t_strand, t_start, t_end, t_reads, t_members};
-          hipLaunchKernelGGL(k_cluster_assign, grid, block, 0, c->stream, N, d_scanned, d_perm, d_kept, d_ksum, d_dropped, d_off, d_query, d_qlen,
-                             d_qcount, d_cluster, tab); }
-        uint32_t nc = 0;
-        HIPOK(hipMemcpyAsync(&nc, d_ksum + (N - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(cluster, d_cluster, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t *d_ref, *d_query, *d_vals, *d_perm, *d_flag, *d_fsum, *d_kept, *d_ksum, *t_ref, *t_members, nc = 0;
+    uint64_t *d_off, *d_keys, *d_skeys, *t_start;
+    unsigned long long *t_end, *t_reads;
+    uint8_t *d_strand, *d_skip, *d_dropped, *t_strand;
+    int32_t *d_qlen, *d_cluster; int64_t* d_qcount;
+    ClusterItem *d_items, *d_scanned; void* d_tmp;
+    PoolScope scope(c);
+    CHECK(scope.get(&d_ref, N)); CHECK(scope.get(&d_query, N)); CHECK(scope.get(&d_off, N)); CHECK(scope.get(&d_strand, N));
+    CHECK(scope.get(&d_qlen, (size_t)n_queries)); CHECK(scope.get(&d_qcount, (size_t)n_queries)); CHECK(scope.get(&d_skip, (size_t)n_refs));
+    CHECK(scope.get(&d_keys, N)); CHECK(scope.get(&d_skeys, N)); CHECK(scope.get(&d_vals, N)); CHECK(scope.get(&d_perm, N));
+    CHECK(scope.get(&d_items, N)); CHECK(scope.get(&d_scanned, N));
+    CHECK(scope.get(&d_flag, N)); CHECK(scope.get(&d_fsum, N)); CHECK(scope.get(&d_kept, N)); CHECK(scope.get(&d_ksum, N));
+    CHECK(scope.get(&d_dropped, N)); CHECK(scope.get(&d_cluster, N));
+    CHECK(scope.get(&t_ref, N)); CHECK(scope.get(&t_members, N)); CHECK(scope.get(&t_start, N)); CHECK(scope.get(&t_end, N));
+    CHECK(scope.get(&t_reads, N)); CHECK(scope.get(&t_strand, N));
+    HIPOK(hipMemcpyAsync(d_ref, ref, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_query, query, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_off, off, (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_strand, strand, (size_t)N, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_qlen, qlen, (size_t)n_queries * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_qcount, qcount, (size_t)n_queries * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_skip, ref_skip, (size_t)n_refs, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(t_end, 0, (size_t)N * 8, c->stream));
+    HIPOK(hipMemsetAsync(t_reads, 0, (size_t)N * 8, c->stream));
+    HIPOK(hipMemsetAsync(t_members, 0, (size_t)N * 4, c->stream));
+    size_t tb = 0, tb_sort = 0, tb_scan = 0, tb_sum = 0;
+    HIPOK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, d_keys, d_skeys, d_vals, d_perm, (int)N, 0, 33, c->stream));
+    HIPOK(hipcub::DeviceScan::InclusiveScan(nullptr, tb_scan, d_items, d_scanned, ClusterScanOp(), (int)N, c->stream));
+    HIPOK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_sum, d_flag, d_fsum, (int)N, c->stream));
+    tb = std::max(tb_sort, std::max(tb_scan, tb_sum));
+    CHECK(scope.get((uint8_t**)&d_tmp, tb));
+    const dim3 grid((N + 255) / 256), block(256);
+    { LaunchScope ls(c, "k_cluster_keys", (double)N);
+      hipLaunchKernelGGL(k_cluster_keys, grid, block, 0, c->stream, N, d_ref, d_strand, d_keys, d_vals); }
+    HIPOK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb_sort, d_keys, d_skeys, d_vals, d_perm, (int)N, 0, 33, c->stream));
+    { LaunchScope ls(c, "k_cluster_items", (double)N);
+      hipLaunchKernelGGL(k_cluster_items, grid, block, 0, c->stream, N, d_skeys, d_perm, d_off, d_query, d_qlen, d_items); }
+    HIPOK(hipcub::DeviceScan::InclusiveScan(d_tmp, tb_scan, d_items, d_scanned, ClusterScanOp(), (int)N, c->stream));
+    { LaunchScope ls(c, "k_cluster_flags", (double)N);
+      hipLaunchKernelGGL(k_cluster_flags, grid, block, 0, c->stream, N, d_scanned, d_perm, d_off, threshold, d_flag); }
+    HIPOK(hipcub::DeviceScan::InclusiveSum(d_tmp, tb_sum, d_flag, d_fsum, (int)N, c->stream));
+    { LaunchScope ls(c, "k_cluster_kept", (double)N);
+      hipLaunchKernelGGL(k_cluster_kept, grid, block, 0, c->stream, N, d_scanned, d_flag, d_fsum, d_skip, minus_first_only, d_kept, d_dropped); }
+    HIPOK(hipcub::DeviceScan::InclusiveSum(d_tmp, tb_sum, d_kept, d_ksum, (int)N, c->stream));
+    { LaunchScope ls(c, "k_cluster_assign", (double)N);
+      const ClusterTable tab{t_ref, t_strand, t_start, t_end, t_reads, t_members};
+      hipLaunchKernelGGL(k_cluster_assign, grid, block, 0, c->stream, N, d_scanned, d_perm, d_kept, d_ksum, d_dropped, d_off, d_query, d_qlen,
+                         d_qcount, d_cluster, tab); }
+    HIPOK(hipMemcpyAsync(&nc, d_ksum + (N - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(cluster, d_cluster, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    if (nc) {
+        HIPOK(hipMemcpyAsync(c_ref, t_ref, (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(c_strand, t_strand, (size_t)nc, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(c_start, t_start, (size_t)nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(c_end, t_end, (size_t)nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(c_reads, t_reads, (size_t)nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(c_members, t_members, (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
         HIPOK(hipStreamSynchronize(c->stream));
-        if (nc) {
-            HIPOK(hipMemcpyAsync(c_ref, t_ref, (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipMemcpyAsync(c_strand, t_strand, (size_t)nc, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipMemcpyAsync(c_start, t_start, (size_t)nc * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipMemcpyAsync(c_end, t_end, (size_t)nc * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipMemcpyAsync(c_reads, t_reads, (size_t)nc * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipMemcpyAsync(c_members, t_members, (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipStreamSynchronize(c->stream));
-        }
-        HIPOK(hipGetLastError());
-        *n_clusters = nc;
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    for (void* p : {(void*)d_ref, (void*)d_query, (void*)d_vals, (void*)d_perm, (void*)d_flag, (void*)d_fsum, (void*)d_kept, (void*)d_ksum,
-                    (void*)t_ref, (void*)t_members, (void*)d_off, (void*)d_keys, (void*)d_skeys, (void*)t_start, (void*)t_end, (void*)t_reads,
-                    (void*)d_strand, (void*)d_skip, (void*)d_dropped, (void*)t_strand, (void*)d_qlen, (void*)d_cluster, (void*)d_qcount,
-                    (void*)d_items, (void*)d_scanned, d_tmp})
-        c->release(p);
-    return rc;
+    }
+    HIPOK(hipGetLastError());
+    *n_clusters = nc;
+    return 0;
 }
 
 // ---- windows of the genome as text (mirge_genome_fetch): templateSeq of calculateFeature and the precursor windows of
@@ -514,21 +492,15 @@ extern "C" int mirge_genome_fetch(mirge_ctx* c, const mirge_genome* g, int64_t n
     }
     if (out_off[n] == 0) return 0;
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
-    GenomeWindow* d_win = nullptr; char* d_out = nullptr;
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_win, (size_t)n)); CHECK(dalloc(c, &d_out, (size_t)out_off[n]));
-        HIPOK(hipMemcpyAsync(d_win, win.data(), (size_t)n * sizeof(GenomeWindow), hipMemcpyHostToDevice, c->stream));
-        { LaunchScope ls(c, "k_genome_fetch", (double)out_off[n]);
-          hipLaunchKernelGGL(k_genome_fetch, dim3((uint32_t)n), dim3(64), 0, c->stream, (uint32_t)n, d_win, g->text, g->s_start, g->n_str,
-                             g->str_ref, g->str_off, d_out); }
-        HIPOK(hipMemcpyAsync(out, d_out, (size_t)out_off[n], hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    c->release(d_win); c->release(d_out);
-    return rc;
+    GenomeWindow* d_win; char* d_out;
+    PoolScope scope(c);
+    CHECK(scope.get(&d_win, (size_t)n)); CHECK(scope.get(&d_out, (size_t)out_off[n]));
+    HIPOK(hipMemcpyAsync(d_win, win.data(), (size_t)n * sizeof(GenomeWindow), hipMemcpyHostToDevice, c->stream));
+    { LaunchScope ls(c, "k_genome_fetch", (double)out_off[n]);
+      hipLaunchKernelGGL(k_genome_fetch, dim3((uint32_t)n), dim3(64), 0, c->stream, (uint32_t)n, d_win, g->text, g->s_start, g->n_str,
+                         g->str_ref, g->str_off, d_out); }
+    HIPOK(hipMemcpyAsync(out, d_out, (size_t)out_off[n], hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    return 0;
 }

@@ -26,34 +26,27 @@ extern "C" int mirge_cluster_diagonals(mirge_ctx* c, const char* reads, const in
         if (row_cluster[i] >= (uint64_t)n_clusters) return fail(-1, w + ": a row names a cluster that does not exist");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     const uint32_t N = (uint32_t)n_rows;
-    char *d_reads = nullptr, *d_clu = nullptr; int64_t *d_roff = nullptr, *d_coff = nullptr; uint32_t* d_rc = nullptr;
-    int32_t *d_diag = nullptr, *d_score = nullptr, *d_id = nullptr; uint8_t* d_flag = nullptr;
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_reads, (size_t)r_off[n_rows])); CHECK(dalloc(c, &d_clu, (size_t)c_off[n_clusters]));
-        CHECK(dalloc(c, &d_roff, (size_t)n_rows + 1)); CHECK(dalloc(c, &d_coff, (size_t)n_clusters + 1)); CHECK(dalloc(c, &d_rc, N));
-        CHECK(dalloc(c, &d_diag, N)); CHECK(dalloc(c, &d_score, N)); CHECK(dalloc(c, &d_id, N)); CHECK(dalloc(c, &d_flag, N));
-        if (r_off[n_rows]) HIPOK(hipMemcpyAsync(d_reads, reads, (size_t)r_off[n_rows], hipMemcpyHostToDevice, c->stream));
-        if (c_off[n_clusters]) HIPOK(hipMemcpyAsync(d_clu, clusters, (size_t)c_off[n_clusters], hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_roff, r_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_coff, c_off, ((size_t)n_clusters + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_rc, row_cluster, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-        { LaunchScope ls(c, "k_cluster_diagonals", (double)N);
-          hipLaunchKernelGGL(k_cluster_diagonals, dim3((N + MIRGE_PILEUP_BLOCK - 1) / MIRGE_PILEUP_BLOCK), dim3(MIRGE_PILEUP_BLOCK), 0, c->stream,
-                             N, d_reads, d_roff, d_clu, d_coff, d_rc, d_diag, d_score, d_id, d_flag); }
-        HIPOK(hipMemcpyAsync(diag, d_diag, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(score, d_score, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(identity, d_id, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(flag, d_flag, (size_t)N, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    for (void* p : {(void*)d_reads, (void*)d_clu, (void*)d_roff, (void*)d_coff, (void*)d_rc, (void*)d_diag, (void*)d_score, (void*)d_id, (void*)d_flag})
-        c->release(p);
-    return rc;
+    char *d_reads, *d_clu; int64_t *d_roff, *d_coff; uint32_t* d_rc;
+    int32_t *d_diag, *d_score, *d_id; uint8_t* d_flag;
+    PoolScope scope(c);
+    CHECK(scope.get(&d_reads, (size_t)r_off[n_rows])); CHECK(scope.get(&d_clu, (size_t)c_off[n_clusters]));
+    CHECK(scope.get(&d_roff, (size_t)n_rows + 1)); CHECK(scope.get(&d_coff, (size_t)n_clusters + 1)); CHECK(scope.get(&d_rc, N));
+    CHECK(scope.get(&d_diag, N)); CHECK(scope.get(&d_score, N)); CHECK(scope.get(&d_id, N)); CHECK(scope.get(&d_flag, N));
+    if (r_off[n_rows]) HIPOK(hipMemcpyAsync(d_reads, reads, (size_t)r_off[n_rows], hipMemcpyHostToDevice, c->stream));
+    if (c_off[n_clusters]) HIPOK(hipMemcpyAsync(d_clu, clusters, (size_t)c_off[n_clusters], hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_roff, r_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_coff, c_off, ((size_t)n_clusters + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_rc, row_cluster, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    { LaunchScope ls(c, "k_cluster_diagonals", (double)N);
+      hipLaunchKernelGGL(k_cluster_diagonals, dim3((N + MIRGE_PILEUP_BLOCK - 1) / MIRGE_PILEUP_BLOCK), dim3(MIRGE_PILEUP_BLOCK), 0, c->stream,
+                         N, d_reads, d_roff, d_clu, d_coff, d_rc, d_diag, d_score, d_id, d_flag); }
+    HIPOK(hipMemcpyAsync(diag, d_diag, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(score, d_score, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(identity, d_id, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(flag, d_flag, (size_t)N, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    return 0;
 }
 
 // rows [row_start[k], row_start[k + 1]) are cluster k's.  col_off[n_clusters + 1] (out): where each cluster's columns start in
@@ -89,52 +82,44 @@ extern "C" int mirge_cluster_pileup(mirge_ctx* c, const char* reads, const int64
     }
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     const uint32_t NI = (uint32_t)items.size();
-    char* d_reads = nullptr; int64_t *d_roff = nullptr, *d_coff = nullptr, *d_count = nullptr, *d_col = nullptr;
-    int32_t *d_diag = nullptr, *d_head = nullptr, *d_tail = nullptr; PileupItem* d_items = nullptr; unsigned long long* d_tally = nullptr;
-    auto run = [&]() -> int {
-        const size_t nb = n_rows ? (size_t)r_off[n_rows] : 0;
-        CHECK(dalloc(c, &d_reads, nb)); CHECK(dalloc(c, &d_roff, (size_t)n_rows + 1)); CHECK(dalloc(c, &d_coff, (size_t)n_clusters + 1));
-        CHECK(dalloc(c, &d_count, (size_t)n_rows)); CHECK(dalloc(c, &d_col, (size_t)n_clusters + 1)); CHECK(dalloc(c, &d_diag, (size_t)n_rows));
-        CHECK(dalloc(c, &d_head, (size_t)n_clusters)); CHECK(dalloc(c, &d_tail, (size_t)n_clusters)); CHECK(dalloc(c, &d_items, (size_t)NI));
-        if (nb) HIPOK(hipMemcpyAsync(d_reads, reads, nb, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_roff, n_rows ? r_off : r0.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_coff, c_off.data(), ((size_t)n_clusters + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        if (n_rows) {
-            HIPOK(hipMemcpyAsync(d_count, count, (size_t)n_rows * 8, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_diag, diag, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        HIPOK(hipMemcpyAsync(d_items, items.data(), (size_t)NI * sizeof(PileupItem), hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemsetAsync(d_head, 0, (size_t)n_clusters * 4, c->stream));
-        HIPOK(hipMemsetAsync(d_tail, 0, (size_t)n_clusters * 4, c->stream));
-        { LaunchScope ls(c, "k_pileup_extent", (double)n_rows);
-          hipLaunchKernelGGL(k_pileup_extent, dim3(NI), dim3(64), 0, c->stream, NI, d_items, d_roff, d_coff, d_diag, d_head, d_tail); }
-        HIPOK(hipMemcpyAsync(head, d_head, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(tail, d_tail, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        for (int64_t k = 0; k < n_clusters; k++) {  // the paddings place every cluster's columns
-            if (head[k] < 0 || head[k] >= MIRGE_PILEUP_MAXREAD || tail[k] < 0 || tail[k] >= MIRGE_PILEUP_MAXREAD)
-                return fail(-3, w + ": a padding out of range came back from the device");
-            col_off[k + 1] = col_off[k] + head[k] + c_len[k] + tail[k];
-        }
-        const int64_t cols = col_off[n_clusters];
-        if (cols > cap_cols) return fail(-1, w + ": the tally array is too small for the columns");
-        if (cols == 0) return 0;
-        CHECK(dalloc(c, &d_tally, (size_t)cols * 5));
-        HIPOK(hipMemcpyAsync(d_col, col_off, ((size_t)n_clusters + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemsetAsync(d_tally, 0, (size_t)cols * 40, c->stream));
-        { LaunchScope ls(c, "k_pileup_tally", (double)n_rows);
-          hipLaunchKernelGGL(k_pileup_tally, dim3(NI), dim3(64), 0, c->stream, NI, d_items, d_reads, d_roff, d_coff, d_diag, d_count, d_head,
-                             d_tail, d_col, d_tally); }
-        HIPOK(hipMemcpyAsync(tally, d_tally, (size_t)cols * 40, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    for (void* p : {(void*)d_reads, (void*)d_roff, (void*)d_coff, (void*)d_count, (void*)d_col, (void*)d_diag, (void*)d_head, (void*)d_tail,
-                    (void*)d_items, (void*)d_tally})
-        c->release(p);
-    return rc;
+    char* d_reads; int64_t *d_roff, *d_coff, *d_count, *d_col;
+    int32_t *d_diag, *d_head, *d_tail; PileupItem* d_items; unsigned long long* d_tally;
+    PoolScope scope(c);  // (r0, c_off and items, which the copies read, outlive it)
+    const size_t nb = n_rows ? (size_t)r_off[n_rows] : 0;
+    CHECK(scope.get(&d_reads, nb)); CHECK(scope.get(&d_roff, (size_t)n_rows + 1)); CHECK(scope.get(&d_coff, (size_t)n_clusters + 1));
+    CHECK(scope.get(&d_count, (size_t)n_rows)); CHECK(scope.get(&d_col, (size_t)n_clusters + 1)); CHECK(scope.get(&d_diag, (size_t)n_rows));
+    CHECK(scope.get(&d_head, (size_t)n_clusters)); CHECK(scope.get(&d_tail, (size_t)n_clusters)); CHECK(scope.get(&d_items, (size_t)NI));
+    if (nb) HIPOK(hipMemcpyAsync(d_reads, reads, nb, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_roff, n_rows ? r_off : r0.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_coff, c_off.data(), ((size_t)n_clusters + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_rows) {
+        HIPOK(hipMemcpyAsync(d_count, count, (size_t)n_rows * 8, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_diag, diag, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPOK(hipMemcpyAsync(d_items, items.data(), (size_t)NI * sizeof(PileupItem), hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(d_head, 0, (size_t)n_clusters * 4, c->stream));
+    HIPOK(hipMemsetAsync(d_tail, 0, (size_t)n_clusters * 4, c->stream));
+    { LaunchScope ls(c, "k_pileup_extent", (double)n_rows);
+      hipLaunchKernelGGL(k_pileup_extent, dim3(NI), dim3(64), 0, c->stream, NI, d_items, d_roff, d_coff, d_diag, d_head, d_tail); }
+    HIPOK(hipMemcpyAsync(head, d_head, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(tail, d_tail, (size_t)n_clusters * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < n_clusters; k++) {  // the paddings place every cluster's columns
+        if (head[k] < 0 || head[k] >= MIRGE_PILEUP_MAXREAD || tail[k] < 0 || tail[k] >= MIRGE_PILEUP_MAXREAD)
+            return fail(-3, w + ": a padding out of range came back from the device");
+        col_off[k + 1] = col_off[k] + head[k] + c_len[k] + tail[k];
+    }
+    const int64_t cols = col_off[n_clusters];
+    if (cols > cap_cols) return fail(-1, w + ": the tally array is too small for the columns");
+    if (cols == 0) return 0;
+    CHECK(scope.get(&d_tally, (size_t)cols * 5));
+    HIPOK(hipMemcpyAsync(d_col, col_off, ((size_t)n_clusters + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(d_tally, 0, (size_t)cols * 40, c->stream));
+    { LaunchScope ls(c, "k_pileup_tally", (double)n_rows);
+      hipLaunchKernelGGL(k_pileup_tally, dim3(NI), dim3(64), 0, c->stream, NI, d_items, d_reads, d_roff, d_coff, d_diag, d_count, d_head,
+                         d_tail, d_col, d_tally); }
+    HIPOK(hipMemcpyAsync(tally, d_tally, (size_t)cols * 40, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    return 0;
 }

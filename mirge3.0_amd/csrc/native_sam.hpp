@@ -8,16 +8,18 @@
 #pragma once
 
 // What `--sam-out` and `--sorted-bam` share: the passes' lift tables on the device (ONE blob: 8-byte items first, then 4-byte, then
-// bytes) and the file's rows in class order (k_sam_select, one scan, k_sam_rows).  build() leaves the stream synchronised.
+// bytes) and the file's rows in class order (k_sam_select, one scan, k_sam_rows).  build() leaves the stream synchronised; the blocks are
+// the calling export's (its PoolScope).
 struct SamPrep {
     uint8_t* d_blob = nullptr;
     uint32_t *d_order = nullptr, *d_keep = nullptr, *d_pos = nullptr, *d_rows = nullptr, *d_flags = nullptr;
     void* tmp = nullptr;
     size_t tb = 0, n_rows = 0;
     SamTables t;
-    int build(mirge_ctx* c, const std::string& who, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+    int build(PoolScope& scope, const std::string& who, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
               const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass) {
-        if (!c || !U || !res || (U->n && !order) || !class_pass || n_class < 1 || n_class > MIRGE_SAM_NCLASS || !passes || n_pass < 1 ||
+        mirge_ctx* const c = scope.c;
+        if (!U || !res || (U->n && !order) || !class_pass || n_class < 1 || n_class > MIRGE_SAM_NCLASS || !passes || n_pass < 1 ||
             n_pass > MIRGE_MAX_PASSES || n_pass < res->n_pass || U->n_samples < 1 || sample < 0 || sample >= U->n_samples || res->n != U->n)
             return fail(-1, who + ": bad argument");
         // hipCUB's scans take an `int` item count, and the flag array holds one entry per class and frame row
@@ -75,18 +77,14 @@ struct SamPrep {
         if (bytes8) std::memcpy(blob.data(), b8.data(), bytes8);
         if (bytes4) std::memcpy(blob.data() + o4, b4.data(), bytes4);
         if (!b1.empty()) std::memcpy(blob.data() + o1, b1.data(), b1.size());
-        int rc = 0;
         const size_t nf = n * MIRGE_SAM_NCLASS;
         std::vector<uint32_t> o32(std::max<size_t>(n, 1));
         for (size_t k = 0; k < n; k++) {
             if (order[k] < 0 || order[k] >= U->n) return fail(-1, who + ": row index out of range");
             o32[k] = (uint32_t)order[k];
         }
-        if ((rc = dalloc(c, &d_blob, blob_bytes + 16))) return rc;
-        if ((rc = dalloc(c, &d_order, std::max<size_t>(n, 1)))) return rc;
-        if ((rc = dalloc(c, &d_keep, nf + 1))) return rc;
-        if ((rc = dalloc(c, &d_pos, nf + 1))) return rc;
-        if ((rc = dalloc(c, &d_flags, 16))) return rc;
+        CHECK(scope.get(&d_blob, blob_bytes + 16)); CHECK(scope.get(&d_order, std::max<size_t>(n, 1)));
+        CHECK(scope.get(&d_keep, nf + 1)); CHECK(scope.get(&d_pos, nf + 1)); CHECK(scope.get(&d_flags, 16));
         std::memset(&t, 0, sizeof(t));
         t.n_pass = n_pass; t.S = U->n_samples; t.sample = sample;
         for (int gi = 0; gi < MIRGE_NGROUPS; gi++) {
@@ -123,7 +121,8 @@ struct SamPrep {
             hipLaunchKernelGGL(k_sam_select, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_order, (uint32_t)n, d_keep, d_flags);
         }
         e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_keep, d_pos, (int)(nf + 1), c->stream);
-        if (e == hipSuccess && (rc = dalloc(c, (uint8_t**)&tmp, std::max<size_t>(tb, 16)))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        int rc = 0;
+        if (e == hipSuccess && (rc = scope.get((uint8_t**)&tmp, std::max<size_t>(tb, 16)))) { (void)hipStreamSynchronize(c->stream); return rc; }
         if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, d_keep, d_pos, (int)(nf + 1), c->stream);
         uint32_t n_rows32 = 0, hflag = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&n_rows32, d_pos + nf, 4, hipMemcpyDeviceToHost, c->stream);
@@ -133,14 +132,11 @@ struct SamPrep {
         if (e != hipSuccess) return fail(-2, who + ": " + hipGetErrorString(e));
         if (hflag) return fail(-1, who + ": pass, reference or offset out of range");
         n_rows = n_rows32;
-        if ((rc = dalloc(c, &d_rows, std::max<size_t>(n_rows, 1)))) return rc;
+        CHECK(scope.get(&d_rows, std::max<size_t>(n_rows, 1)));
         if (n_rows)
             hipLaunchKernelGGL(k_sam_rows, dim3(grid_for(c, nf)), dim3(MIRGE_BLOCK), 0, c->stream, (const uint32_t*)d_order, (uint32_t)n, (const uint32_t*)d_keep,
                                (const uint32_t*)d_pos, d_rows);
         return 0;
-    }
-    void release(mirge_ctx* c) {
-        c->release(d_blob); c->release(d_order); c->release(d_keep); c->release(d_pos); c->release(d_rows); c->release(d_flags); c->release(tmp);
     }
 };
 
@@ -159,78 +155,63 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
 
     SamPrep prep;
     uint8_t* d_text[2] = {nullptr, nullptr};
-    uint32_t* d_fixed = nullptr;
-    unsigned long long *d_total = nullptr, *d_off = nullptr, *d_nlines = nullptr;
-    int rc = 0;
-    int64_t n_lines = 0, n_bytes = 0;
-    OutFile out("mirge_sam_write_device");
-    do {
-        if ((rc = prep.build(c, "mirge_sam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass))) break;
-        const SamTables& t = prep.t;
-        uint32_t* const d_rows = prep.d_rows;
-        const size_t n_rows = prep.n_rows;
-        hc.lap("rows chosen");
-        if ((rc = dalloc(c, &d_nlines, 2))) break;
-        if ((rc = dalloc(c, &d_fixed, std::max<size_t>(n_rows, 1)))) break;
-        if ((rc = dalloc(c, &d_total, n_rows + 1))) break;
-        if ((rc = dalloc(c, &d_off, n_rows + 1))) break;
-        hipError_t e = hipMemsetAsync(d_total + n_rows, 0, 8, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_nlines, 0, 16, c->stream);
-        if (e == hipSuccess && n_rows) {
-            LaunchScope ls(c, "k_sam_measure", (double)n_rows);
-            hipLaunchKernelGGL(k_sam_measure, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n_rows, d_fixed,
-                               d_total, d_nlines);
-        }
-        size_t tb2 = 0;
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, d_total, d_off, (int)(n_rows + 1), c->stream);
-        if (e == hipSuccess && tb2 > prep.tb) { c->release(prep.tmp); prep.tmp = nullptr; if ((rc = dalloc(c, (uint8_t**)&prep.tmp, tb2))) break; }
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(prep.tmp, tb2, d_total, d_off, (int)(n_rows + 1), c->stream);
-        unsigned long long body = 0, lines = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&body, d_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&lines, d_nlines, 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e)); break; }
-        hc.lap("measured");
-        // ---- the file: header, then the body chunk by chunk
-        if ((rc = out.open(path))) break;
-        if (header_len && out.put(header, (size_t)header_len, 0)) { rc = fail(-8, std::string("cannot write ") + path); break; }
-        if (body) {
-            const size_t buf = (size_t)std::min<unsigned long long>(chunk, body);
-            StagePipe pipe(c, out.who);
-            if ((rc = pipe.ensure(buf))) break;
-            if ((rc = dalloc(c, &d_text[0], buf + 16))) break;
-            if (body > buf && (rc = dalloc(c, &d_text[1], buf + 16))) break;
-            auto queue = [&](unsigned long long ci) -> int {
-                const unsigned long long at0 = ci * chunk;
-                const uint32_t nn = (uint32_t)std::min<unsigned long long>(chunk, body - at0);
-                const size_t tiles = ((size_t)nn + tile - 1) / tile;
-                {
-                    LaunchScope ls(c, "k_sam_write", (double)nn);
-                    hipLaunchKernelGGL(k_sam_write, dim3((unsigned)std::min<size_t>(tiles, (size_t)c->n_cu * 32)), dim3(MIRGE_BLOCK), 0, c->stream, t,
-                                       (const uint32_t*)d_rows, (uint32_t)n_rows, (const uint32_t*)d_fixed, (const unsigned long long*)d_off, at0, nn,
-                                       (uint32_t)tile, d_text[ci & 1]);
-                }
-                e = hipMemcpyAsync(pipe.half(ci), d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream);
-                return e == hipSuccess ? 0 : fail(-2, std::string("mirge_sam_write_device: ") + hipGetErrorString(e));
-            };
-            auto take = [&](unsigned long long ci) -> int {  // chunk ci is in its half: write it at its place
-                const unsigned long long at0 = ci * chunk;
-                return out.put(pipe.half(ci), (size_t)std::min<unsigned long long>(chunk, body - at0), (unsigned long long)header_len + at0);
-            };
-            rc = pipe.run((body + chunk - 1) / chunk, queue, take);
-        }
-        if (rc) break;
-        n_lines = (int64_t)lines; n_bytes = (int64_t)body;
-        hc.lap("formatted + written");
-    } while (0);
-    (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    if (rc == 0) rc = out.commit();  // (an OutFile that is not committed takes its file with it)
-    prep.release(c);
-    c->release(d_text[0]); c->release(d_text[1]); c->release(d_fixed); c->release(d_total); c->release(d_off); c->release(d_nlines);
-    if (rc == 0) {
-        if (n_lines_out) *n_lines_out = n_lines;
-        if (n_bytes_out) *n_bytes_out = n_bytes;
+    uint32_t* d_fixed;
+    unsigned long long *d_total, *d_off, *d_nlines, body = 0, lines = 0;
+    OutFile out("mirge_sam_write_device");  // (not committed: it takes its file with it, behind the scope's wait)
+    PoolScope scope(c);
+    CHECK(prep.build(scope, "mirge_sam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass));
+    const SamTables& t = prep.t;
+    uint32_t* const d_rows = prep.d_rows;
+    const size_t n_rows = prep.n_rows;
+    hc.lap("rows chosen");
+    CHECK(scope.get(&d_nlines, 2)); CHECK(scope.get(&d_fixed, std::max<size_t>(n_rows, 1)));
+    CHECK(scope.get(&d_total, n_rows + 1)); CHECK(scope.get(&d_off, n_rows + 1));
+    HIPOK(hipMemsetAsync(d_total + n_rows, 0, 8, c->stream));
+    HIPOK(hipMemsetAsync(d_nlines, 0, 16, c->stream));
+    if (n_rows) {
+        LaunchScope ls(c, "k_sam_measure", (double)n_rows);
+        hipLaunchKernelGGL(k_sam_measure, dim3(grid_for(c, n_rows)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n_rows, d_fixed,
+                           d_total, d_nlines);
     }
-    return rc;
+    size_t tb2 = 0;
+    HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, d_total, d_off, (int)(n_rows + 1), c->stream));
+    if (tb2 > prep.tb) { scope.give(prep.tmp); CHECK(scope.get((uint8_t**)&prep.tmp, tb2)); }
+    HIPOK(hipcub::DeviceScan::ExclusiveSum(prep.tmp, tb2, d_total, d_off, (int)(n_rows + 1), c->stream));
+    HIPOK(hipMemcpyAsync(&body, d_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(&lines, d_nlines, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    hc.lap("measured");
+    // ---- the file: header, then the body chunk by chunk
+    CHECK(out.open(path));
+    if (header_len && out.put(header, (size_t)header_len, 0)) return fail(-8, std::string("cannot write ") + path);
+    if (body) {
+        const size_t buf = (size_t)std::min<unsigned long long>(chunk, body);
+        StagePipe pipe(c, out.who);
+        CHECK(pipe.ensure(buf));
+        CHECK(scope.get(&d_text[0], buf + 16));
+        if (body > buf) CHECK(scope.get(&d_text[1], buf + 16));
+        auto queue = [&](unsigned long long ci) -> int {
+            const unsigned long long at0 = ci * chunk;
+            const uint32_t nn = (uint32_t)std::min<unsigned long long>(chunk, body - at0);
+            const size_t tiles = ((size_t)nn + tile - 1) / tile;
+            {
+                LaunchScope ls(c, "k_sam_write", (double)nn);
+                hipLaunchKernelGGL(k_sam_write, dim3((unsigned)std::min<size_t>(tiles, (size_t)c->n_cu * 32)), dim3(MIRGE_BLOCK), 0, c->stream, t,
+                                   (const uint32_t*)d_rows, (uint32_t)n_rows, (const uint32_t*)d_fixed, (const unsigned long long*)d_off, at0, nn,
+                                   (uint32_t)tile, d_text[ci & 1]);
+            }
+            HIPOK(hipMemcpyAsync(pipe.half(ci), d_text[ci & 1], nn, hipMemcpyDeviceToHost, c->stream));
+            return 0;
+        };
+        auto take = [&](unsigned long long ci) -> int {  // chunk ci is in its half: write it at its place
+            const unsigned long long at0 = ci * chunk;
+            return out.put(pipe.half(ci), (size_t)std::min<unsigned long long>(chunk, body - at0), (unsigned long long)header_len + at0);
+        };
+        CHECK(pipe.run((body + chunk - 1) / chunk, queue, take));
+    }
+    hc.lap("formatted + written");
+    CHECK(out.commit());  // (every chunk has been taken: nothing of the file is still on its way)
+    if (n_lines_out) *n_lines_out = (int64_t)lines;
+    if (n_bytes_out) *n_bytes_out = (int64_t)body;
+    return 0;
 }

@@ -1,7 +1,7 @@
 // native_trf.hpp -- part of mirge_native.hip (one translation unit): the two device calls behind the tRNA fragment report
 // (kernels_trf.hpp).  mirge_trf_hits: the rows' probe tables made sure of, a counting pass, one exclusive scan, the writing pass into
 // every row's own stretch, one radix sort of (row, global position) keys, the records finished and copied to the host.
-// mirge_trf_assign: the predefined tRFs uploaded as one CSR, one kernel over the rows.
+// mirge_trf_assign: the predefined tRFs uploaded as one CSR, one kernel over the rows.  Every call's blocks: one PoolScope.
 // mirge_trf_cluster (--trf-clusters): the points packed to their templates' columns, then density, nearest denser point and border
 // over a tile list of (group, MIRGE_BLOCK points), with the O(n) steps of the reference's loop on the host between the launches.
 #pragma once
@@ -74,11 +74,11 @@ extern "C" int mirge_trf_hits_run(mirge_ctx* c, const mirge_reads* U, const mirg
     t.cls[0].pass = mature_pass; t.cls[1].pass = primary_pass;
 
     const size_t n = (size_t)n_rows;
-    uint32_t *d_rows = nullptr, *d_flags = nullptr, *d_row = nullptr, *d_ref = nullptr;
-    int32_t *d_ac = nullptr, *d_off = nullptr;
-    unsigned long long *d_cnt = nullptr, *d_start = nullptr, *d_keys = nullptr, *d_keys2 = nullptr;
-    uint8_t *d_mm = nullptr, *d_cls = nullptr, *d_type = nullptr;
-    void* d_tmp = nullptr;
+    uint32_t *d_rows, *d_flags, *d_row, *d_ref, flag = 0;
+    int32_t *d_ac, *d_off;
+    unsigned long long *d_cnt, *d_start, *d_keys = nullptr, *d_keys2, n_rec = 0;
+    uint8_t *d_mm, *d_cls, *d_type;
+    void* d_tmp;
     auto hits_pass = [&](bool write) {
         for (int W : {1, 2, 4, 8}) {
             bool present = false;
@@ -100,66 +100,55 @@ extern "C" int mirge_trf_hits_run(mirge_ctx* c, const mirge_reads* U, const mirg
 #undef MIRGE_TRF_LAUNCH
         }
     };
-    auto run = [&]() -> int {
-        const size_t n_ac = std::max<size_t>((size_t)mature_lib->n_refs, 1);
-        CHECK(dalloc(c, &d_rows, n)); CHECK(dalloc(c, &d_flags, 16)); CHECK(dalloc(c, &d_ac, n_ac));
-        CHECK(dalloc(c, &d_cnt, n + 1)); CHECK(dalloc(c, &d_start, n + 1));
-        HIPOK(hipMemcpyAsync(d_rows, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        if (mature_lib->n_refs) HIPOK(hipMemcpyAsync(d_ac, anticodon, (size_t)mature_lib->n_refs * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemsetAsync(d_flags, 0, 64, c->stream));
-        HIPOK(hipMemsetAsync(d_cnt, 0, (n + 1) * 8, c->stream));
-        t.anticodon = d_ac;
-        hits_pass(false);
-        size_t tb = 0;
-        HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt, d_start, (int)(n + 1), c->stream));
-        CHECK(c->alloc(&d_tmp, std::max<size_t>(tb, 16)));
-        HIPOK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_cnt, d_start, (int)(n + 1), c->stream));
-        unsigned long long n_rec = 0;
-        uint32_t flag = 0;
-        HIPOK(hipMemcpyAsync(&n_rec, d_start + n, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        if (flag & 1u) return fail(-1, who + ": a row is neither a mature-tRNA nor a primary-tRNA read");
-        if (flag & 4u) return fail(-1, who + ": a probe table is missing");
-        if (n_rec >= 0x7FFFFFF0ull) return fail(-5, who + ": " + std::to_string(n_rec) + " alignments to report in one call");
-        if (n_rec == 0) return 0;
-        CHECK(dalloc(c, &d_keys, (size_t)n_rec)); CHECK(dalloc(c, &d_keys2, (size_t)n_rec));
-        hits_pass(true);
-        // ---- (row, global position) ascending = (row, reference, offset)
-        int rbits = 1;
-        while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
-        size_t tb2 = 0;
-        HIPOK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb2, d_keys, d_keys2, (int)n_rec, 0, 32 + rbits, c->stream));
-        if (tb2 > std::max<size_t>(tb, 16)) { c->release(d_tmp); d_tmp = nullptr; CHECK(c->alloc(&d_tmp, tb2)); }
-        HIPOK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb2, d_keys, d_keys2, (int)n_rec, 0, 32 + rbits, c->stream));
-        CHECK(dalloc(c, &d_row, (size_t)n_rec)); CHECK(dalloc(c, &d_ref, (size_t)n_rec)); CHECK(dalloc(c, &d_off, (size_t)n_rec));
-        CHECK(dalloc(c, &d_mm, (size_t)n_rec)); CHECK(dalloc(c, &d_cls, (size_t)n_rec)); CHECK(dalloc(c, &d_type, (size_t)n_rec));
-        {
-            LaunchScope ls(c, "k_trf_finish", (double)n_rec);
-            hipLaunchKernelGGL(k_trf_finish, dim3(grid_for(c, (size_t)n_rec)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows,
-                               (const unsigned long long*)d_keys2, (uint32_t)n_rec, d_row, d_ref, d_off, d_mm, d_cls, d_type);
-        }
-        hits->row.resize(n_rec); hits->ref.resize(n_rec); hits->off.resize(n_rec); hits->mm.resize(n_rec); hits->cls.resize(n_rec); hits->type.resize(n_rec);
-        HIPOK(hipMemcpyAsync(hits->row.data(), d_row, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(hits->ref.data(), d_ref, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(hits->off.data(), d_off, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(hits->mm.data(), d_mm, n_rec, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(hits->cls.data(), d_cls, n_rec, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(hits->type.data(), d_type, n_rec, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        if (flag) return fail(-1, who + ": the writing pass and the counting pass disagree");
-        return 0;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    for (void* p : {(void*)d_rows, (void*)d_flags, (void*)d_row, (void*)d_ref, (void*)d_ac, (void*)d_off, (void*)d_cnt, (void*)d_start,
-                    (void*)d_keys, (void*)d_keys2, (void*)d_mm, (void*)d_cls, (void*)d_type, d_tmp})
-        c->release(p);
-    if (rc) return rc;
+    PoolScope scope(c);  // (behind r32, hits, n_rec and flag, which the copies read or fill: they outlive its wait)
+    const size_t n_ac = std::max<size_t>((size_t)mature_lib->n_refs, 1);
+    CHECK(scope.get(&d_rows, n)); CHECK(scope.get(&d_flags, 16)); CHECK(scope.get(&d_ac, n_ac));
+    CHECK(scope.get(&d_cnt, n + 1)); CHECK(scope.get(&d_start, n + 1));
+    HIPOK(hipMemcpyAsync(d_rows, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    if (mature_lib->n_refs) HIPOK(hipMemcpyAsync(d_ac, anticodon, (size_t)mature_lib->n_refs * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(d_flags, 0, 64, c->stream));
+    HIPOK(hipMemsetAsync(d_cnt, 0, (n + 1) * 8, c->stream));
+    t.anticodon = d_ac;
+    hits_pass(false);
+    size_t tb = 0;
+    HIPOK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt, d_start, (int)(n + 1), c->stream));
+    CHECK(scope.get((uint8_t**)&d_tmp, std::max<size_t>(tb, 16)));
+    HIPOK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_cnt, d_start, (int)(n + 1), c->stream));
+    HIPOK(hipMemcpyAsync(&n_rec, d_start + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    if (flag & 1u) return fail(-1, who + ": a row is neither a mature-tRNA nor a primary-tRNA read");
+    if (flag & 4u) return fail(-1, who + ": a probe table is missing");
+    if (n_rec >= 0x7FFFFFF0ull) return fail(-5, who + ": " + std::to_string(n_rec) + " alignments to report in one call");
+    if (n_rec == 0) { *out = hits.release(); return 0; }
+    CHECK(scope.get(&d_keys, (size_t)n_rec)); CHECK(scope.get(&d_keys2, (size_t)n_rec));
+    hits_pass(true);
+    // ---- (row, global position) ascending = (row, reference, offset)
+    int rbits = 1;
+    while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
+    size_t tb2 = 0;
+    HIPOK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb2, d_keys, d_keys2, (int)n_rec, 0, 32 + rbits, c->stream));
+    if (tb2 > std::max<size_t>(tb, 16)) { scope.give(d_tmp); CHECK(scope.get((uint8_t**)&d_tmp, tb2)); }
+    HIPOK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb2, d_keys, d_keys2, (int)n_rec, 0, 32 + rbits, c->stream));
+    CHECK(scope.get(&d_row, (size_t)n_rec)); CHECK(scope.get(&d_ref, (size_t)n_rec)); CHECK(scope.get(&d_off, (size_t)n_rec));
+    CHECK(scope.get(&d_mm, (size_t)n_rec)); CHECK(scope.get(&d_cls, (size_t)n_rec)); CHECK(scope.get(&d_type, (size_t)n_rec));
+    {
+        LaunchScope ls(c, "k_trf_finish", (double)n_rec);
+        hipLaunchKernelGGL(k_trf_finish, dim3(grid_for(c, (size_t)n_rec)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows,
+                           (const unsigned long long*)d_keys2, (uint32_t)n_rec, d_row, d_ref, d_off, d_mm, d_cls, d_type);
+    }
+    hits->row.resize(n_rec); hits->ref.resize(n_rec); hits->off.resize(n_rec); hits->mm.resize(n_rec); hits->cls.resize(n_rec); hits->type.resize(n_rec);
+    HIPOK(hipMemcpyAsync(hits->row.data(), d_row, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(hits->ref.data(), d_ref, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(hits->off.data(), d_off, n_rec * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(hits->mm.data(), d_mm, n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(hits->cls.data(), d_cls, n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(hits->type.data(), d_type, n_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    if (flag) return fail(-1, who + ": the writing pass and the counting pass disagree");
     *out = hits.release();
     return 0;
 }
@@ -192,43 +181,35 @@ extern "C" int mirge_trf_assign(mirge_ctx* c, const mirge_reads* U, const mirge_
     std::memset(&t, 0, sizeof(t));
     CHECK(trf_groups(who, U, res, t));
     const size_t n = (size_t)n_rows, nt = (size_t)n_trf;
-    uint32_t *d_read = nullptr, *d_ptr = nullptr, *d_soff = nullptr;
-    int32_t *d_tref = nullptr, *d_start = nullptr, *d_cs = nullptr, *d_ce = nullptr, *d_rank = nullptr, *d_dist = nullptr, *d_trf = nullptr;
-    uint8_t* d_str = nullptr;
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_read, n)); CHECK(dalloc(c, &d_tref, n)); CHECK(dalloc(c, &d_start, n)); CHECK(dalloc(c, &d_dist, n)); CHECK(dalloc(c, &d_trf, n));
-        CHECK(dalloc(c, &d_ptr, (size_t)n_tref + 1)); CHECK(dalloc(c, &d_soff, nt + 1)); CHECK(dalloc(c, &d_str, (size_t)n_str + 16));
-        CHECK(dalloc(c, &d_cs, nt + 1)); CHECK(dalloc(c, &d_ce, nt + 1)); CHECK(dalloc(c, &d_rank, nt + 1));
-        HIPOK(hipMemcpyAsync(d_read, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_tref, tref, n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_start, start, n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_ptr, p32.data(), ((size_t)n_tref + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_soff, o32.data(), (nt + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if (n_str) HIPOK(hipMemcpyAsync(d_str, str, (size_t)n_str, hipMemcpyHostToDevice, c->stream));
-        if (nt) {
-            HIPOK(hipMemcpyAsync(d_cs, c_start, nt * 4, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_ce, c_end, nt * 4, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(d_rank, rank, nt * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        TrfInfor f{d_ptr, d_soff, d_str, d_cs, d_ce, d_rank, (uint32_t)n_tref, (uint32_t)n_trf};
-        {
-            LaunchScope ls(c, "k_trf_assign", (double)n);
-            hipLaunchKernelGGL(k_trf_assign, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, f, (const uint32_t*)d_read, (const int32_t*)d_tref,
-                               (const int32_t*)d_start, (uint32_t)n, d_dist, d_trf);
-        }
-        HIPOK(hipMemcpyAsync(dist, d_dist, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(trf, d_trf, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(c->stream);  // (also when a call failed: the host vectors above leave scope)
-    c->drain();
-    for (void* p : {(void*)d_read, (void*)d_ptr, (void*)d_soff, (void*)d_tref, (void*)d_start, (void*)d_cs, (void*)d_ce, (void*)d_rank,
-                    (void*)d_dist, (void*)d_trf, (void*)d_str})
-        c->release(p);
-    return rc;
+    uint32_t *d_read, *d_ptr, *d_soff;
+    int32_t *d_tref, *d_start, *d_cs, *d_ce, *d_rank, *d_dist, *d_trf;
+    uint8_t* d_str;
+    PoolScope scope(c);  // (the host vectors above outlive its wait)
+    CHECK(scope.get(&d_read, n)); CHECK(scope.get(&d_tref, n)); CHECK(scope.get(&d_start, n)); CHECK(scope.get(&d_dist, n)); CHECK(scope.get(&d_trf, n));
+    CHECK(scope.get(&d_ptr, (size_t)n_tref + 1)); CHECK(scope.get(&d_soff, nt + 1)); CHECK(scope.get(&d_str, (size_t)n_str + 16));
+    CHECK(scope.get(&d_cs, nt + 1)); CHECK(scope.get(&d_ce, nt + 1)); CHECK(scope.get(&d_rank, nt + 1));
+    HIPOK(hipMemcpyAsync(d_read, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_tref, tref, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_start, start, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_ptr, p32.data(), ((size_t)n_tref + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_soff, o32.data(), (nt + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_str) HIPOK(hipMemcpyAsync(d_str, str, (size_t)n_str, hipMemcpyHostToDevice, c->stream));
+    if (nt) {
+        HIPOK(hipMemcpyAsync(d_cs, c_start, nt * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_ce, c_end, nt * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(d_rank, rank, nt * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    TrfInfor f{d_ptr, d_soff, d_str, d_cs, d_ce, d_rank, (uint32_t)n_tref, (uint32_t)n_trf};
+    {
+        LaunchScope ls(c, "k_trf_assign", (double)n);
+        hipLaunchKernelGGL(k_trf_assign, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, f, (const uint32_t*)d_read, (const int32_t*)d_tref,
+                           (const int32_t*)d_start, (uint32_t)n, d_dist, d_trf);
+    }
+    HIPOK(hipMemcpyAsync(dist, d_dist, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(trf, d_trf, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int mirge_trf_row_counts(mirge_ctx* c, const mirge_reads* U, const int64_t* rows, int64_t n_rows, uint32_t* out) {
@@ -246,25 +227,19 @@ extern "C" int mirge_trf_row_counts(mirge_ctx* c, const mirge_reads* U, const in
     std::memset(&t, 0, sizeof(t));
     CHECK(trf_groups(who, U, nullptr, t));
     const size_t n = (size_t)n_rows, total = n * (size_t)U->n_samples;
-    uint32_t *d_rows = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_rows, n)); CHECK(dalloc(c, &d_out, total));
-        HIPOK(hipMemcpyAsync(d_rows, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        {
-            LaunchScope ls(c, "k_trf_row_counts", (double)total);
-            hipLaunchKernelGGL(k_trf_row_counts, dim3(grid_for(c, total)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n,
-                               (int32_t)U->n_samples, d_out);
-        }
-        HIPOK(hipMemcpyAsync(out, d_out, total * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    c->release(d_rows); c->release(d_out);
-    return rc;
+    uint32_t *d_rows, *d_out;
+    PoolScope scope(c);
+    CHECK(scope.get(&d_rows, n)); CHECK(scope.get(&d_out, total));
+    HIPOK(hipMemcpyAsync(d_rows, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    {
+        LaunchScope ls(c, "k_trf_row_counts", (double)total);
+        hipLaunchKernelGGL(k_trf_row_counts, dim3(grid_for(c, total)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_rows, (uint32_t)n,
+                           (int32_t)U->n_samples, d_out);
+    }
+    HIPOK(hipMemcpyAsync(out, d_out, total * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    return 0;
 }
 
 // ---- density-peak clustering (kernels_trf.hpp: k_trf_cluster_pack, k_trf_density, k_trf_nearest, k_trf_border)
@@ -315,12 +290,11 @@ extern "C" int mirge_trf_cluster(mirge_ctx* c, const mirge_reads* U, int64_t n_g
     TrfTables t;
     std::memset(&t, 0, sizeof(t));
     CHECK(trf_groups(who, U, nullptr, t));
-    uint32_t *d_read = nullptr, *d_flags = nullptr, *d_ptr = nullptr, *d_tg = nullptr, *d_tf = nullptr;
-    int32_t *d_off = nullptr, *d_tlen = nullptr, *d_start = nullptr, *d_end = nullptr, *d_nn = nullptr, *d_ord = nullptr, *d_cl = nullptr, *d_cen = nullptr,
-            *d_ncl = nullptr, *d_dcen = nullptr;
-    uint64_t* d_words = nullptr;
-    double *d_rp = nullptr, *d_gauss = nullptr;
-    float *d_rho = nullptr, *d_delta = nullptr, *d_bmax = nullptr;
+    uint32_t *d_read, *d_flags, *d_ptr, *d_tg, *d_tf, flag = 0;
+    int32_t *d_off, *d_tlen, *d_start, *d_end, *d_nn, *d_ord, *d_cl, *d_cen, *d_ncl, *d_dcen;
+    uint64_t* d_words;
+    double *d_rp, *d_gauss;
+    float *d_rho, *d_delta, *d_bmax;
     std::vector<int32_t> cen(n, -1), dcen(n);
     std::vector<float> bmax(n);
     TrfClusterView v;
@@ -331,66 +305,56 @@ extern "C" int mirge_trf_cluster(mirge_ctx* c, const mirge_reads* U, int64_t n_g
             if (pass == 0) launch4(dim3(n_tile[0]), 0u); else launch8(dim3(n_tile[1]), n_tile[0]);
         }
     };
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &d_read, n)); CHECK(dalloc(c, &d_off, n)); CHECK(dalloc(c, &d_tlen, n)); CHECK(dalloc(c, &d_start, n)); CHECK(dalloc(c, &d_end, n));
-        CHECK(dalloc(c, &d_words, n * 2 * MIRGE_TRF_CL_MAXW)); CHECK(dalloc(c, &d_rp, n)); CHECK(dalloc(c, &d_gauss, ngauss)); CHECK(dalloc(c, &d_flags, 16));
-        CHECK(dalloc(c, &d_ptr, ng + 1)); CHECK(dalloc(c, &d_tg, nt)); CHECK(dalloc(c, &d_tf, nt)); CHECK(dalloc(c, &d_rho, n)); CHECK(dalloc(c, &d_delta, n));
-        CHECK(dalloc(c, &d_nn, n)); CHECK(dalloc(c, &d_ord, n)); CHECK(dalloc(c, &d_cl, n)); CHECK(dalloc(c, &d_cen, n)); CHECK(dalloc(c, &d_ncl, ng));
-        CHECK(dalloc(c, &d_bmax, n)); CHECK(dalloc(c, &d_dcen, n));
-        HIPOK(hipMemcpyAsync(d_read, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_off, off, n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_tlen, pt_tlen.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_rp, rp100k, n * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_gauss, gauss, ngauss * 8, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_ptr, p32.data(), (ng + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_tg, tile_grp.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_tf, tile_first.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemsetAsync(d_flags, 0, 64, c->stream));
-        {
-            LaunchScope ls(c, "k_trf_cluster_pack", (double)n);
-            hipLaunchKernelGGL(k_trf_cluster_pack, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_read, (const int32_t*)d_off,
-                               (const int32_t*)d_tlen, (uint32_t)n, d_words, d_start, d_end, d_flags);
-        }
-        uint32_t flag = 0;
-        HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        if (flag & 1u) return fail(-1, who + ": a point's read is of the long class");
-        if (flag & 2u) return fail(-1, who + ": a point does not fit its template");
-        v = TrfClusterView{d_words, d_start, d_end, d_rp, d_ptr, d_tg, d_tf, d_gauss, (int32_t)ngauss, 0};
-        tiles("k_trf_density",
-              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_density<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, d_rho); },
-              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_density<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, d_rho); });
-        tiles("k_trf_nearest",
-              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_nearest<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, d_delta, d_nn, d_ord); },
-              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_nearest<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, d_delta, d_nn, d_ord); });
-        HIPOK(hipMemcpyAsync(rho, d_rho, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(delta, d_delta, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(nneigh, d_nn, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(order, d_ord, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        if (trf_cluster_assign(n_grp, grp_ptr, rho, delta, nneigh, order, cl, centre, nclust, cen.data()))
-            return fail(-1, who + ": the density order is no permutation");
-        HIPOK(hipMemcpyAsync(d_cl, cl, n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_cen, cen.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(d_ncl, nclust, ng * 4, hipMemcpyHostToDevice, c->stream));
-        tiles("k_trf_border",
-              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_border<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, (const int32_t*)d_cl, (const int32_t*)d_cen, (const int32_t*)d_ncl, d_bmax, d_dcen); },
-              [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_border<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, (const int32_t*)d_cl, (const int32_t*)d_cen, (const int32_t*)d_ncl, d_bmax, d_dcen); });
-        HIPOK(hipMemcpyAsync(bmax.data(), d_bmax, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipMemcpyAsync(dcen.data(), d_dcen, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(hipStreamSynchronize(c->stream));
-        HIPOK(hipGetLastError());
-        trf_cluster_halo(n_grp, grp_ptr, rho, cl, nclust, bmax.data(), dcen.data(), halo);
-        return 0;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(c->stream);
-    c->drain();
-    for (void* p : {(void*)d_read, (void*)d_flags, (void*)d_ptr, (void*)d_tg, (void*)d_tf, (void*)d_off, (void*)d_tlen, (void*)d_start, (void*)d_end,
-                    (void*)d_nn, (void*)d_ord, (void*)d_cl, (void*)d_cen, (void*)d_ncl, (void*)d_dcen, (void*)d_words, (void*)d_rp, (void*)d_gauss,
-                    (void*)d_rho, (void*)d_delta, (void*)d_bmax})
-        c->release(p);
-    return rc;
+    PoolScope scope(c);  // (the host vectors and `flag` above outlive its wait)
+    CHECK(scope.get(&d_read, n)); CHECK(scope.get(&d_off, n)); CHECK(scope.get(&d_tlen, n)); CHECK(scope.get(&d_start, n)); CHECK(scope.get(&d_end, n));
+    CHECK(scope.get(&d_words, n * 2 * MIRGE_TRF_CL_MAXW)); CHECK(scope.get(&d_rp, n)); CHECK(scope.get(&d_gauss, ngauss)); CHECK(scope.get(&d_flags, 16));
+    CHECK(scope.get(&d_ptr, ng + 1)); CHECK(scope.get(&d_tg, nt)); CHECK(scope.get(&d_tf, nt)); CHECK(scope.get(&d_rho, n)); CHECK(scope.get(&d_delta, n));
+    CHECK(scope.get(&d_nn, n)); CHECK(scope.get(&d_ord, n)); CHECK(scope.get(&d_cl, n)); CHECK(scope.get(&d_cen, n)); CHECK(scope.get(&d_ncl, ng));
+    CHECK(scope.get(&d_bmax, n)); CHECK(scope.get(&d_dcen, n));
+    HIPOK(hipMemcpyAsync(d_read, r32.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_off, off, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_tlen, pt_tlen.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_rp, rp100k, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_gauss, gauss, ngauss * 8, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_ptr, p32.data(), (ng + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_tg, tile_grp.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_tf, tile_first.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemsetAsync(d_flags, 0, 64, c->stream));
+    {
+        LaunchScope ls(c, "k_trf_cluster_pack", (double)n);
+        hipLaunchKernelGGL(k_trf_cluster_pack, dim3(grid_for(c, n)), dim3(MIRGE_BLOCK), 0, c->stream, t, (const uint32_t*)d_read, (const int32_t*)d_off,
+                           (const int32_t*)d_tlen, (uint32_t)n, d_words, d_start, d_end, d_flags);
+    }
+    HIPOK(hipMemcpyAsync(&flag, d_flags, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    if (flag & 1u) return fail(-1, who + ": a point's read is of the long class");
+    if (flag & 2u) return fail(-1, who + ": a point does not fit its template");
+    v = TrfClusterView{d_words, d_start, d_end, d_rp, d_ptr, d_tg, d_tf, d_gauss, (int32_t)ngauss, 0};
+    tiles("k_trf_density",
+          [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_density<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, d_rho); },
+          [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_density<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, d_rho); });
+    tiles("k_trf_nearest",
+          [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_nearest<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, d_delta, d_nn, d_ord); },
+          [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_nearest<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, d_delta, d_nn, d_ord); });
+    HIPOK(hipMemcpyAsync(rho, d_rho, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(delta, d_delta, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(nneigh, d_nn, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(order, d_ord, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    if (trf_cluster_assign(n_grp, grp_ptr, rho, delta, nneigh, order, cl, centre, nclust, cen.data()))
+        return fail(-1, who + ": the density order is no permutation");
+    HIPOK(hipMemcpyAsync(d_cl, cl, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_cen, cen.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipMemcpyAsync(d_ncl, nclust, ng * 4, hipMemcpyHostToDevice, c->stream));
+    tiles("k_trf_border",
+          [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_border<4>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, (const int32_t*)d_cl, (const int32_t*)d_cen, (const int32_t*)d_ncl, d_bmax, d_dcen); },
+          [&](dim3 g, uint32_t t0) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trf_border<8>), g, dim3(MIRGE_BLOCK), 0, c->stream, v, t0, (const float*)d_rho, (const int32_t*)d_cl, (const int32_t*)d_cen, (const int32_t*)d_ncl, d_bmax, d_dcen); });
+    HIPOK(hipMemcpyAsync(bmax.data(), d_bmax, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipMemcpyAsync(dcen.data(), d_dcen, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
+    trf_cluster_halo(n_grp, grp_ptr, rho, cl, nclust, bmax.data(), dcen.data(), halo);
+    return 0;
 }

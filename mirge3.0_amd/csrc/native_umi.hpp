@@ -38,42 +38,35 @@ static int umi_cluster_device(mirge_ctx* c, const mirge_reads* T, int32_t front,
     while (slots < 2 * (uint64_t)v.n_nodes) slots <<= 1;
     v.tab_mask = slots - 1;
     const size_t n = v.n_nodes;
-    uint64_t *tab = nullptr, *label = nullptr;
-    uint32_t *state = nullptr, *words = nullptr;  // words[0] = a round changed a label; [1..3] = founders, eligible, linked
+    uint64_t *tab, *label;
+    uint32_t *state, *words;  // words[0] = a round changed a label; [1..3] = founders, eligible, linked
     int64_t rounds = 0;
-    uint32_t tally[4] = {0, 0, 0, 0};
-    auto run = [&]() -> int {
-        CHECK(dalloc(c, &tab, (size_t)slots)); CHECK(dalloc(c, &label, n)); CHECK(dalloc(c, &state, n)); CHECK(dalloc(c, &words, (size_t)4));
-        HIPOK(hipMemsetAsync(tab, 0xFF, (size_t)slots * 8, c->stream));
-        HIPOK(hipMemsetAsync(label, 0xFF, n * 8, c->stream));
-        HIPOK(hipMemsetAsync(state, 0, n * 4, c->stream));
-        HIPOK(hipMemsetAsync(words, 0, 16, c->stream));
-        const dim3 grid(grid_for(c, n)), block(MIRGE_BLOCK);
-        { LaunchScope ls(c, "k_umi_insert", (double)n); hipLaunchKernelGGL(k_umi_insert, grid, block, 0, c->stream, v, tab, state); }
-        { LaunchScope ls(c, "k_umi_edges", (double)n); hipLaunchKernelGGL(k_umi_edges, grid, block, 0, c->stream, v, (const uint64_t*)tab, state, label); }
-        for (;;) {
-            uint32_t changed = 0;
-            { LaunchScope ls(c, "k_umi_round", (double)n); hipLaunchKernelGGL(k_umi_round, grid, block, 0, c->stream, v, (const uint64_t*)tab, (const uint32_t*)state, label, words); }
-            HIPOK(hipMemcpyAsync(&changed, words, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(hipStreamSynchronize(c->stream));
-            HIPOK(hipGetLastError());
-            rounds++;
-            if (!changed) break;
-            // (labels only fall, and a round that changes something lowers one: more rounds than nodes cannot be)
-            if (rounds > (int64_t)n + 1) return fail(-3, who + ": the label propagation did not settle");
-            HIPOK(hipMemsetAsync(words, 0, 4, c->stream));
-        }
-        { LaunchScope ls(c, "k_umi_comp_big", (double)n); hipLaunchKernelGGL(k_umi_comp_big, grid, block, 0, c->stream, v, state, (const uint64_t*)label); }
-        { LaunchScope ls(c, "k_umi_founders", (double)n); hipLaunchKernelGGL(k_umi_founders, grid, block, 0, c->stream, v, (const uint32_t*)state, (const uint64_t*)label, d_founder, words); }
-        HIPOK(hipMemcpyAsync(tally, words, 16, hipMemcpyDeviceToHost, c->stream));
+    uint32_t tally[4] = {0, 0, 0, 0}, changed = 0;
+    PoolScope scope(c);
+    CHECK(scope.get(&tab, (size_t)slots)); CHECK(scope.get(&label, n)); CHECK(scope.get(&state, n)); CHECK(scope.get(&words, (size_t)4));
+    HIPOK(hipMemsetAsync(tab, 0xFF, (size_t)slots * 8, c->stream));
+    HIPOK(hipMemsetAsync(label, 0xFF, n * 8, c->stream));
+    HIPOK(hipMemsetAsync(state, 0, n * 4, c->stream));
+    HIPOK(hipMemsetAsync(words, 0, 16, c->stream));
+    const dim3 grid(grid_for(c, n)), block(MIRGE_BLOCK);
+    { LaunchScope ls(c, "k_umi_insert", (double)n); hipLaunchKernelGGL(k_umi_insert, grid, block, 0, c->stream, v, tab, state); }
+    { LaunchScope ls(c, "k_umi_edges", (double)n); hipLaunchKernelGGL(k_umi_edges, grid, block, 0, c->stream, v, (const uint64_t*)tab, state, label); }
+    for (;;) {
+        { LaunchScope ls(c, "k_umi_round", (double)n); hipLaunchKernelGGL(k_umi_round, grid, block, 0, c->stream, v, (const uint64_t*)tab, (const uint32_t*)state, label, words); }
+        HIPOK(hipMemcpyAsync(&changed, words, 4, hipMemcpyDeviceToHost, c->stream));
         HIPOK(hipStreamSynchronize(c->stream));
         HIPOK(hipGetLastError());
-        return 0;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    c->release(tab); c->release(label); c->release(state); c->release(words);
-    if (rc) return rc;
+        rounds++;
+        if (!changed) break;
+        // (labels only fall, and a round that changes something lowers one: more rounds than nodes cannot be)
+        if (rounds > (int64_t)n + 1) return fail(-3, who + ": the label propagation did not settle");
+        HIPOK(hipMemsetAsync(words, 0, 4, c->stream));
+    }
+    { LaunchScope ls(c, "k_umi_comp_big", (double)n); hipLaunchKernelGGL(k_umi_comp_big, grid, block, 0, c->stream, v, state, (const uint64_t*)label); }
+    { LaunchScope ls(c, "k_umi_founders", (double)n); hipLaunchKernelGGL(k_umi_founders, grid, block, 0, c->stream, v, (const uint32_t*)state, (const uint64_t*)label, d_founder, words); }
+    HIPOK(hipMemcpyAsync(tally, words, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipGetLastError());
     *n_founders = tally[1];
     g_umi_stats[0] = T->n; g_umi_stats[1] = tally[2]; g_umi_stats[2] = tally[3]; g_umi_stats[3] = rounds; g_umi_stats[4] = (int64_t)slots;
     return 0;
@@ -86,16 +79,13 @@ extern "C" int mirge_umi_cluster(mirge_ctx* c, const mirge_reads* tagged, int32_
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     *n_founders = 0;
     if (tagged->n == 0) { for (int64_t& s : g_umi_stats) s = 0; return 0; }
-    uint8_t* d = nullptr;
-    CHECK(dalloc(c, &d, (size_t)tagged->n));
-    int rc = umi_cluster_device(c, tagged, front, back, d, n_founders);
-    if (rc == 0) {
-        hipError_t e = hipMemcpyAsync(founder_out, d, (size_t)tagged->n, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(-2, who + ": " + hipGetErrorString(e));
-    }
-    c->release(d);
-    return rc;
+    PoolScope scope(c);
+    uint8_t* d;
+    CHECK(scope.get(&d, (size_t)tagged->n));
+    CHECK(umi_cluster_device(c, tagged, front, back, d, n_founders));
+    HIPOK(hipMemcpyAsync(founder_out, d, (size_t)tagged->n, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 // the last mirge_umi_cluster / clustering parse of this thread: out[0..4] = tagged reads, eligible reads, count-1 reads with a count-1
