@@ -189,6 +189,22 @@ int mirge_reads_parse_umi(mirge_ctx* ctx, const char* text, int64_t nbytes, int3
  * propagation and slots of the lookup table of this thread's last clustering. */
 int mirge_umi_cluster(mirge_ctx* ctx, const mirge_reads* tagged, int32_t front, int32_t back, uint8_t* founder_out, int64_t* n_founders);
 int mirge_umi_cluster_stats(int64_t* out);
+/* --kmer-correct: k-mer spectrum error correction of one sample's distinct reads.  uniq: a collapse result with one count column.
+ * Rounds run for k = k_start .. k_end (8 <= k_start <= k_end <= 31), each on the dictionary the round before left.  In a round a read is
+ * eligible iff it holds no N and has k .. 256 nt; S(x) = the sum of the counts of the eligible reads over every window that spells the
+ * k-mer x (forward strand, 64-bit); a window is weak iff S <= threshold (>= 1).  A read with a weak window is suspect; with lo = its last
+ * weak start and hi = its first weak start + k - 1 it is uncorrectable if lo > hi, else every (p, b), lo <= p <= hi, p < len, b != r[p],
+ * is a candidate: valid iff every window of the changed read that covers p is solid, scored by the smallest S among them.  The read is
+ * corrected iff exactly one valid candidate has the largest score (none: unsupported; several: ambiguous).  The corrected reads are
+ * regrouped: counts add, the first index is the smallest of the contributors'.  *out: the dictionary after the last round (a collapse
+ * result of its own, to be destroyed by the caller; its first indices are those of `uniq`).  final_of (host, [mirge_reads_count(uniq)],
+ * or NULL): the handle index in *out of every read of uniq; rounds_mask (the same shape, or NULL): bit (k - k_start) set iff the read,
+ * or the read it had become by then, was corrected in the round of k.  MIRGE_TEST_EC_HASH_BITS=N keeps N bits of the hashes (tests).
+ * mirge_kmer_correct_stats: out[8 r + 0..7] for round r of this thread's last call = eligible, suspect, corrected, uncorrectable,
+ * unsupported and ambiguous reads, distinct reads after the round, slots of the round's table; returns the number of rounds (<= 24). */
+int mirge_kmer_correct(mirge_ctx* ctx, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, mirge_reads** out,
+                       uint32_t* final_of, uint32_t* rounds_mask);
+int mirge_kmer_correct_stats(int64_t* out);
 /* Several raw read sets as one, in the order given (the samples of a run, one file each, before the joint collapse
  * that replaces the per-file dicts and their outer join, digest.py:133-163,243).  The parts stay valid. */
 int mirge_reads_concat(mirge_ctx* ctx, const mirge_reads* const* parts, int32_t n_parts, mirge_reads** out);

@@ -3,7 +3,7 @@
   python -m mirge3_amd.cli -s S1.fastq,S2.fastq -lib /path/Libs -on human -db miRBase -o out
 
 Same flag names as the reference (``mirge/libs/parse.py``) for what is implemented -- trimming (-a / -g / -q / -nxt / -NX /
--u), UMIs (-umi / --qiagenumi / -udd), -spk, -tcf, -spl / -rr, -ie, -gff, -ai --; switches of subsystems that are out of
+-u), UMIs (-umi / --qiagenumi / -udd), -spk, -tcf, -spl / -rr, -ie, -gff, -ai, --kmer-correct --; switches of subsystems that are out of
 scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignored.  Writes the reference's files:
 ``run.log``, ``mapped.csv``, ``unmapped.csv``, ``miR.Counts.csv``, ``miR.RPM.csv``, ``annotation.report.csv/html``
 (+ ``isomirs.csv`` / ``isomirs.samples.csv`` with ``-ie``, ``sample_miRge3.gff`` with ``-gff``, the three
@@ -58,6 +58,12 @@ def parse_args(argv=None):
     ap.add_argument("--umi-cluster", dest="umi_cluster", default="none", choices=("none", "directional"),
                     help="with -udd: 'directional' absorbs sequencing errors inside UMIs (UMI-tools' directional network method, Hamming "
                          "distance 1): a count is a number of founder UMIs; also writes <sample>_umiClusters.csv")
+    ap.add_argument("--kmer-correct", dest="kmer_correct", action="store_true",
+                    help="correct sequencing errors in every sample's distinct trimmed reads on the device before anything is counted: "
+                         "k-mer spectra for k = -ks .. -ke (defaults 15 .. 20, within 8 .. 31), a k-mer seen more than -kh times (default "
+                         "5) is solid, and per k a read with weak k-mers takes the one substitution that makes all of them solid, if "
+                         "exactly one scores best (README, '--kmer-correct: sequencing errors in reads, by k-mer spectra'); writes <sample>_kmerCorrected.csv.  Not together "
+                         "with -umi, -spl, -rr, --backend bowtie or a run sharded over ranks")
     ap.add_argument("-tcf", "--tcf-out", dest="tcf_out", action="store_true",
                     help="write <sample>.trim.collapse.fa")
     ap.add_argument("-ie", "--isoform-entropy", dest="isoform_entropy", action="store_true",
@@ -152,7 +158,8 @@ def parse_args(argv=None):
     # flags of mirge/libs/parse.py that the reference itself never reads (-M, -l, --gc-content, -cms, --compression-level,
     # -op, --numba-*), that only size its worker chunks (--buffer-size), that name tools or carry parameters of the
     # subsystems refused below (-psam, -prf, -mdt, -kh/-ks/-ke, -minl ... -clc), or that it fills in itself (-cuv, -buv):
-    # accepted and ignored, so that a reference command line keeps working
+    # accepted and ignored, so that a reference command line keeps working (-kh / -ks / -ke are read with --kmer-correct, and
+    # -minl ... -clc with --unmapped-clusters)
     for flags in (("-M", "--maximum-length"), ("-l", "--length"), ("--gc-content",), ("-cms", "--chunkmbs"), ("--compression-level",),
                   ("-op", "--output"), ("--buffer-size",), ("-cuv", "--cutadaptVersion"), ("-buv", "--bowtieVersion"),
                   ("-psam", "--samtools-path"), ("-prf", "--RNAfold-path"), ("-mdt", "--metadata"), ("-kh", "--threshold"),
@@ -191,6 +198,25 @@ def parse_args(argv=None):
             tag = []
         if len(tag) != 2 or min(tag) < 0 or not 1 <= sum(tag) <= 32:
             ap.error("--umi-cluster directional takes -umi f,b with 1 <= f + b <= 32")
+    args.kmer_range = None
+    if args.kmer_correct:
+        vals = {}
+        for k, default in (("kh", 5), ("ks", 15), ("ke", 20)):
+            v = getattr(args, "ignored_" + k)
+            if v is not None and not (str(v).isdigit() or (str(v)[:1] in "+-" and str(v)[1:].isdigit())):
+                ap.error(f"--kmer-correct: -{k} takes an integer")
+            vals[k] = default if v is None else int(v)
+        if vals["kh"] < 1:
+            ap.error("--kmer-correct: -kh is at least 1")
+        if vals["ks"] < 8 or vals["ke"] > 31 or vals["ks"] > vals["ke"]:
+            ap.error("--kmer-correct: 8 <= -ks <= -ke <= 31")
+        if args.uniq_mol_ids:
+            ap.error("--kmer-correct is not run together with -umi (as the reference's -mEC)")
+        if args.save_pkl or args.resume or args.backend == "bowtie":
+            ap.error("--kmer-correct runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--kmer-correct is a single-process option")
+        args.kmer_range = (vals["ks"], vals["ke"], vals["kh"])
     if args.qiagenumi and not (args.adapters and args.adapters[0][0] == "back"):
         ap.error("--qiagenumi reads the UMI behind the 3' adapter: give it with -a (first)")
     args.bowtieVersion = "True"

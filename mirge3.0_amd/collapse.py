@@ -810,16 +810,73 @@ def write_umi_clusters(path, tagged: "_ffi.DeviceReads", front: int, back: int, 
     return len(tagged), stats["eligible"], int(founder.sum())
 
 
-def write_tcf(path, raw: "_ffi.DeviceReads") -> None:
+KMER_TALLY_NAMES = ("eligible", "suspect", "corrected", "uncorrectable", "unsupported", "ambiguous")
+
+
+def kmer_corrected_csv(original: FlatSeqs, final: FlatSeqs, counts: np.ndarray, masks: np.ndarray, k_start: int) -> bytes:
+    """The text of ``<sample>_kmerCorrected.csv``: ``Original,Corrected,Count,Rounds``, one line per distinct read (rows in the order
+    given: first appearance) whose final sequence differs from it; ``Rounds`` = the k values of the bits of ``masks``, joined by ';'.
+    A read keeps its length, so the two sets share their offsets.  Assembled with numpy: no per-read Python object."""
+    head = b"Original,Corrected,Count,Rounds\n"
+    n = len(original)
+    if n == 0:
+        return head
+    rows = np.repeat(np.arange(n, dtype=np.int64), original.lengths)
+    changed = np.flatnonzero(np.bincount(rows[original.data != final.data], minlength=n) > 0)
+    if changed.shape[0] == 0:
+        return head
+    c = np.asarray(counts).reshape(-1)[changed].astype(np.int64)
+    m = np.asarray(masks).reshape(-1)[changed].astype(np.int64)
+    um, inv = np.unique(m, return_inverse=True)
+    texts = np.array([";".join(str(int(k_start) + b) for b in range(32) if (int(x) >> b) & 1).encode() for x in um]).astype("S")
+    cols = [original.take(changed), final.take(changed), FlatSeqs.from_fixed(np.char.mod("%d", c).astype("S")), FlatSeqs.from_fixed(texts[inv])]
+    return head + FlatSeqs.join_columns(cols, b",,,\n")
+
+
+def kmer_correct_log_lines(name, k_start: int, stats) -> List[str]:
+    """one ``run.log`` line per round of a sample's correction (``stats``: a dict per round, ``_ffi.kmer_correct_stats``)"""
+    return [f"kmer-correct {name} k={int(k_start) + r}: " + ", ".join(f"{key} {int(st[key])}" for key in KMER_TALLY_NAMES) +
+            f", distinct reads after the round {int(st['distinct'])}" for r, st in enumerate(stats)]
+
+
+def kmer_correct_sample(raw: "_ffi.DeviceReads", name, workDir, k_start: int, k_end: int, threshold: int) -> "_ffi.DeviceReads":
+    """``--kmer-correct`` for one parsed sample: its dictionary (one collapse), the rounds on the device (``mirge_kmer_correct``), and
+    ``<name>_kmerCorrected.csv`` plus the sample's ``run.log`` lines.  Returns the corrected dictionary: a collapse result with one count
+    column whose first indices are those of the reads' earliest contributors."""
+    d0 = raw.collapse()
+    try:
+        out, final_of, masks = d0.kmer_correct(k_start, k_end, threshold)
+        stats = _ffi.kmer_correct_stats()
+        if workDir is not None:
+            rows = np.flatnonzero(masks)  # the reads some round corrected, in the order they first appeared
+            if rows.shape[0]:  # (the two dictionaries come to the host only where a line is to be written)
+                cnt, first = d0.counts()
+                rows = rows[np.argsort(first[rows], kind="stable")]
+                before, after = d0.unpack().take(rows), out.unpack().take(final_of[rows].astype(np.int64))
+                text = kmer_corrected_csv(before, after, cnt[rows, 0], masks[rows], k_start)
+            else:
+                text = kmer_corrected_csv(FlatSeqs.from_list([]), FlatSeqs.from_list([]), np.zeros(0, np.uint32), np.zeros(0, np.uint32), k_start)
+            with open(Path(workDir) / (str(name) + "_kmerCorrected.csv"), "wb") as fh:
+                fh.write(text)
+            with open(Path(workDir) / "run.log", "a") as lf:
+                lf.write("".join(line + "\n" for line in kmer_correct_log_lines(name, k_start, stats)))
+        return out
+    finally:
+        d0.close()
+
+
+def write_tcf(path, raw: "_ffi.DeviceReads", dictionary: "_ffi.DeviceReads" = None) -> None:
     """``<sample>.trim.collapse.fa`` (``-tcf``, digest.py:219-229): the sample's own dictionary, most frequent first (Python's
     stable ``sorted(..., key=count, reverse=True)``: ties stay in dictionary order), ``>seq<k>_<count>``.  One collapse of the
-    sample's raw reads on the GPU, the text assembled with numpy."""
-    u1 = raw.collapse()
+    sample's raw reads on the GPU -- or ``dictionary``, the sample's corrected one (``--kmer-correct``) --, the text assembled with
+    numpy."""
+    u1 = raw.collapse() if dictionary is None else dictionary
     cnt, first = u1.counts()
     c = cnt[:, 0].astype(np.int64) if len(u1) else np.zeros(0, np.int64)
     order = np.lexsort((first, -c))
     seqs = u1.unpack().take(order)
-    u1.close()
+    if dictionary is None:
+        u1.close()
     n = len(order)
     head = FlatSeqs.from_fixed(np.char.add(b">seq", np.char.mod("%d", np.arange(1, n + 1)).astype("S")).astype("S")) if n else FlatSeqs.from_list([])
     num = FlatSeqs.from_fixed(np.char.mod("%d", c[order]).astype("S")) if n else FlatSeqs.from_list([])

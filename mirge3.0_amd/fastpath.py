@@ -22,7 +22,7 @@ import numpy as np
 
 from . import PASS_COLUMNS, _ffi
 from .cascade import PASSES, get_cascade
-from .collapse import parse_sample, read_text, read_texts, trim_from_args, umi_from_args, write_tcf
+from .collapse import kmer_correct_sample, parse_sample, read_text, read_texts, trim_from_args, umi_from_args, write_tcf
 from .countjoin import summarize_device
 from .seqio import FlatSeqs, load_merges
 
@@ -159,6 +159,11 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
     umi = umi_from_args(args)
     sampleReadCounts, trimmedReadCounts, trimmedReadCountsUnique = {}, {}, {}
     parsed = []
+    kmer = getattr(args, "kmer_range", None) if getattr(args, "kmer_correct", False) else None  # (k_start, k_end, threshold)
+    corrected = []
+    if kmer is not None and (getattr(args, "AtoI", False) or getattr(args, "gff_out", False)):
+        say("NOTE: --kmer-correct with -ai / -gff: a rare true variant whose k-mers are seen at most -kh times is indistinguishable from a "
+            "sequencing error and is corrected away")
     t_read = t_parse = 0.0
     from . import collapse as _collapse
     del _collapse.GZ_LOG[:]
@@ -173,8 +178,13 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
         del text
         t_parse += time.perf_counter() - t1
         sampleReadCounts[name], trimmedReadCounts[name] = n_rec, len(raw)
+        if kmer is not None:  # the sample's dictionary, corrected on the device, stands for its reads from here on
+            outlog.flush()
+            t_k = time.perf_counter()
+            corrected.append(kmer_correct_sample(raw, name, workDir, *kmer))
+            tm["kmer_correct_s"] = tm.get("kmer_correct_s", 0.0) + time.perf_counter() - t_k
         if getattr(args, "tcf_out", False):
-            write_tcf(workDir / (str(name) + ".trim.collapse.fa"), raw)
+            write_tcf(workDir / (str(name) + ".trim.collapse.fa"), raw, corrected[-1] if kmer is not None else None)
         if raw.iupac_seen:
             say(f"WARNING: {name} holds IUPAC ambiguity codes other than N (or '.'); they are aligned -- and printed -- as N")
         parsed.append(raw)
@@ -194,7 +204,15 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
             casc.prepare(p)
     tm["probe_tables_s"] = time.perf_counter() - t
     t = time.perf_counter()
-    if S == 1:
+    if kmer is not None:  # (--kmer-correct: the samples' corrected dictionaries, not their reads)
+        if S == 1:
+            uniq = corrected[0]
+        else:
+            uniq = _ffi.DeviceReads.merge(ctx, corrected)
+            for d in corrected:
+                d.close()
+        res = casc.run(uniq)
+    elif S == 1:
         uniq, res = casc.collapse_and_run(parsed[0])
     else:  # (round 6: every sample collapsed by itself, the dictionaries merged on the device -- collapse.collapse_parsed_samples)
         from .collapse import collapse_parsed_samples
