@@ -205,6 +205,18 @@ int mirge_umi_cluster_stats(int64_t* out);
 int mirge_kmer_correct(mirge_ctx* ctx, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, mirge_reads** out,
                        uint32_t* final_of, uint32_t* rounds_mask);
 int mirge_kmer_correct_stats(int64_t* out);
+/* --kmer-ratio R: mirge_kmer_correct with a relative threshold.  ratio == 0 is exactly mirge_kmer_correct; ratio == 1 and ratio < 0 are
+ * refused.  With ratio >= 2 a window has a second way to be weak, decided on the round's spectrum before anything else:
+ *   2a. a k-mer x with S(x) > threshold is DOMINATED iff a k-mer y that differs from x in exactly one letter has S(y) >= ratio * S(x)
+ *       (exact integers: the product is never formed where it would not fit 64 bits; floor(S(y) / ratio) >= S(x) is the same predicate);
+ *   2b. x is weak iff S(x) <= threshold or x is dominated; else solid.
+ * Domination is decided from the sums alone: y may itself be dominated; a k-mer no eligible read holds has sum 0 and dominates nothing.
+ * All else is as above; a candidate's score is still the smallest S among windows that are all solid.
+ * mirge_kmer_correct_ratio_stats: out[2 r + 0..1] for round r of this thread's last call = distinct k-mers with S > threshold, the
+ * dominated among them (zeros when that call had no ratio); returns the number of rounds (<= 24). */
+int mirge_kmer_correct_ratio(mirge_ctx* ctx, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, int32_t ratio,
+                             mirge_reads** out, uint32_t* final_of, uint32_t* rounds_mask);
+int mirge_kmer_correct_ratio_stats(int64_t* out);
 /* Several raw read sets as one, in the order given (the samples of a run, one file each, before the joint collapse
  * that replaces the per-file dicts and their outer join, digest.py:133-163,243).  The parts stay valid. */
 int mirge_reads_concat(mirge_ctx* ctx, const mirge_reads* const* parts, int32_t n_parts, mirge_reads** out);

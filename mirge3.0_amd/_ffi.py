@@ -32,7 +32,7 @@ EXPORTS = [
     "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
     "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device", "mirge_bam_huffman_probe",
     "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
-    "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats", "mirge_kmer_correct", "mirge_kmer_correct_stats", "mirge_coverage_runs", "mirge_coverage_write_device",
+    "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats", "mirge_kmer_correct", "mirge_kmer_correct_stats", "mirge_kmer_correct_ratio", "mirge_kmer_correct_ratio_stats", "mirge_coverage_runs", "mirge_coverage_write_device",
     "mirge_bigwig_from_intervals", "mirge_bigwig_write_device",
 ]
 
@@ -628,16 +628,19 @@ class DeviceReads:
             raise RuntimeError("mirge_umi_cluster: the founder count and the flags differ")
         return out
 
-    def kmer_correct(self, k_start: int, k_end: int, threshold: int):
-        """``mirge_kmer_correct`` on a one-column collapse result -> (the corrected dictionary, a collapse result whose first indices are
+    def kmer_correct(self, k_start: int, k_end: int, threshold: int, ratio: int = 0):
+        """``mirge_kmer_correct_ratio`` on a one-column collapse result -> (the corrected dictionary, a collapse result whose first indices are
         this one's; uint32 [U]: the handle index there of every read of this one; uint32 [U]: bit ``k - k_start`` set iff the read, or the
-        read it had become, was corrected in the round of ``k``)"""
+        read it had become, was corrected in the round of ``k``).  ``ratio`` >= 2: the relative threshold of ``--kmer-ratio``; 0: none,
+        exactly ``mirge_kmer_correct``"""
         n = len(self)
         final_of = np.zeros(max(n, 1), dtype=np.uint32)
         mask = np.zeros(max(n, 1), dtype=np.uint32)
         h = C.c_void_p()
-        _check(load().mirge_kmer_correct(self.ctx._h, self._h, C.c_int32(int(k_start)), C.c_int32(int(k_end)), C.c_int32(int(threshold)), C.byref(h),
-                                         _p(final_of), _p(mask)), "mirge_kmer_correct")
+        if not -2 ** 31 <= int(ratio) < 2 ** 31:
+            raise RuntimeError("mirge_kmer_correct_ratio: the ratio is 0 (none) or 2 .. 2^31 - 1")
+        _check(load().mirge_kmer_correct_ratio(self.ctx._h, self._h, C.c_int32(int(k_start)), C.c_int32(int(k_end)), C.c_int32(int(threshold)),
+                                               C.c_int32(int(ratio)), C.byref(h), _p(final_of), _p(mask)), "mirge_kmer_correct_ratio")
         return DeviceReads(self.ctx, h), final_of[:n], mask[:n]
 
     def first_appearance_order(self) -> np.ndarray:
@@ -715,6 +718,17 @@ def kmer_correct_stats() -> list:
     if rounds < 0:
         _check(rounds, "mirge_kmer_correct_stats")
     return [dict(zip(KMER_CORRECT_TALLIES, (int(x) for x in out[8 * r:8 * r + 8]))) for r in range(rounds)]
+
+
+def kmer_correct_ratio_stats() -> list:
+    """``mirge_kmer_correct_ratio_stats``: per round of this thread's last ``kmer_correct`` a dict ``above`` (distinct k-mers with a sum
+    above the threshold) and ``dominated`` (those of them a neighbouring k-mer dominates); zeros when that call had no ratio"""
+    out = np.zeros(2 * 24, dtype=np.int64)
+    load().mirge_kmer_correct_ratio_stats.restype = C.c_int
+    rounds = load().mirge_kmer_correct_ratio_stats(_p(out))
+    if rounds < 0:
+        _check(rounds, "mirge_kmer_correct_ratio_stats")
+    return [{"above": int(out[2 * r]), "dominated": int(out[2 * r + 1])} for r in range(rounds)]
 
 
 class CascadeResult:

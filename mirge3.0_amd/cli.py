@@ -3,7 +3,7 @@
   python -m mirge3_amd.cli -s S1.fastq,S2.fastq -lib /path/Libs -on human -db miRBase -o out
 
 Same flag names as the reference (``mirge/libs/parse.py``) for what is implemented -- trimming (-a / -g / -q / -nxt / -NX /
--u), UMIs (-umi / --qiagenumi / -udd), -spk, -tcf, -spl / -rr, -ie, -gff, -ai, --kmer-correct --; switches of subsystems that are out of
+-u), UMIs (-umi / --qiagenumi / -udd), -spk, -tcf, -spl / -rr, -ie, -gff, -ai, --kmer-correct (--kmer-ratio) --; switches of subsystems that are out of
 scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignored.  Writes the reference's files:
 ``run.log``, ``mapped.csv``, ``unmapped.csv``, ``miR.Counts.csv``, ``miR.RPM.csv``, ``annotation.report.csv/html``
 (+ ``isomirs.csv`` / ``isomirs.samples.csv`` with ``-ie``, ``sample_miRge3.gff`` with ``-gff``, the three
@@ -64,6 +64,11 @@ def parse_args(argv=None):
                          "5) is solid, and per k a read with weak k-mers takes the one substitution that makes all of them solid, if "
                          "exactly one scores best (README, '--kmer-correct: sequencing errors in reads, by k-mer spectra'); writes <sample>_kmerCorrected.csv.  Not together "
                          "with -umi, -spl, -rr, --backend bowtie or a run sharded over ranks")
+    ap.add_argument("--kmer-ratio", dest="kmer_ratio", default=None, metavar="R",
+                    help="with --kmer-correct: a k-mer seen more than -kh times is weak all the same when a k-mer one letter from it is seen at "
+                         "least R times as often (an integer, 2 .. 2^31 - 1; no default: without the flag only -kh decides).  Separates the "
+                         "errors of a deep template from it; a true variant below 1/R of a sibling one letter away is corrected into it; "
+                         "run.log gets a second line per sample and k")
     ap.add_argument("-tcf", "--tcf-out", dest="tcf_out", action="store_true",
                     help="write <sample>.trim.collapse.fa")
     ap.add_argument("-ie", "--isoform-entropy", dest="isoform_entropy", action="store_true",
@@ -199,6 +204,15 @@ def parse_args(argv=None):
         if len(tag) != 2 or min(tag) < 0 or not 1 <= sum(tag) <= 32:
             ap.error("--umi-cluster directional takes -umi f,b with 1 <= f + b <= 32")
     args.kmer_range = None
+    if args.kmer_ratio is not None:
+        if not args.kmer_correct:
+            ap.error("--kmer-ratio requires --kmer-correct")
+        v = str(args.kmer_ratio)
+        if not (v.isdigit() or (v[:1] in "+-" and v[1:].isdigit())):
+            ap.error("--kmer-ratio takes an integer")
+        args.kmer_ratio = int(v)
+        if not 2 <= args.kmer_ratio <= 2 ** 31 - 1:
+            ap.error("--kmer-ratio: 2 <= R <= 2^31 - 1")
     if args.kmer_correct:
         vals = {}
         for k, default in (("kh", 5), ("ks", 15), ("ke", 20)):

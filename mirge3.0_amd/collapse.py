@@ -839,14 +839,24 @@ def kmer_correct_log_lines(name, k_start: int, stats) -> List[str]:
             f", distinct reads after the round {int(st['distinct'])}" for r, st in enumerate(stats)]
 
 
-def kmer_correct_sample(raw: "_ffi.DeviceReads", name, workDir, k_start: int, k_end: int, threshold: int) -> "_ffi.DeviceReads":
-    """``--kmer-correct`` for one parsed sample: its dictionary (one collapse), the rounds on the device (``mirge_kmer_correct``), and
-    ``<name>_kmerCorrected.csv`` plus the sample's ``run.log`` lines.  Returns the corrected dictionary: a collapse result with one count
-    column whose first indices are those of the reads' earliest contributors."""
+def kmer_ratio_log_lines(name, k_start: int, ratio: int, ratio_stats) -> List[str]:
+    """the ``run.log`` line that follows a round's line with ``--kmer-ratio`` (``ratio_stats``: ``_ffi.kmer_correct_ratio_stats``)"""
+    return [f"kmer-correct {name} k={int(k_start) + r} ratio {int(ratio)}: k-mers above -kh {int(st['above'])}, dominated {int(st['dominated'])}"
+            for r, st in enumerate(ratio_stats)]
+
+
+def kmer_correct_sample(raw: "_ffi.DeviceReads", name, workDir, k_start: int, k_end: int, threshold: int, ratio: int = 0) -> "_ffi.DeviceReads":
+    """``--kmer-correct`` for one parsed sample: its dictionary (one collapse), the rounds on the device (``mirge_kmer_correct``; with
+    ``ratio`` >= 2 ``mirge_kmer_correct_ratio``), and ``<name>_kmerCorrected.csv`` plus the sample's ``run.log`` lines.  Returns the
+    corrected dictionary: a collapse result with one count column whose first indices are those of the reads' earliest contributors."""
     d0 = raw.collapse()
     try:
-        out, final_of, masks = d0.kmer_correct(k_start, k_end, threshold)
+        out, final_of, masks = d0.kmer_correct(k_start, k_end, threshold, ratio)
         stats = _ffi.kmer_correct_stats()
+        lines = kmer_correct_log_lines(name, k_start, stats)
+        if ratio:  # behind every round's line the line of its relative threshold
+            extra = kmer_ratio_log_lines(name, k_start, ratio, _ffi.kmer_correct_ratio_stats())
+            lines = [x for pair in zip(lines, extra) for x in pair]
         if workDir is not None:
             rows = np.flatnonzero(masks)  # the reads some round corrected, in the order they first appeared
             if rows.shape[0]:  # (the two dictionaries come to the host only where a line is to be written)
@@ -859,7 +869,7 @@ def kmer_correct_sample(raw: "_ffi.DeviceReads", name, workDir, k_start: int, k_
             with open(Path(workDir) / (str(name) + "_kmerCorrected.csv"), "wb") as fh:
                 fh.write(text)
             with open(Path(workDir) / "run.log", "a") as lf:
-                lf.write("".join(line + "\n" for line in kmer_correct_log_lines(name, k_start, stats)))
+                lf.write("".join(line + "\n" for line in lines))
         return out
     finally:
         d0.close()

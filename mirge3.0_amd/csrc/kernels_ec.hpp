@@ -14,6 +14,7 @@
 // lo <= hi go into a list), k_ec_correct (a WAVE per listed read: lanes take (candidate, window) pairs, a candidate's smallest sum is
 // a segmented wave minimum, the unique maximum a wave reduction of (score, how many, which)), then the regrouping around the
 // weighted collapse: k_ec_gather, k_ec_rep, k_ec_index, k_ec_find, k_ec_follow.
+// With a ratio (--kmer-ratio, mirge_kmer_correct_ratio) k_ec_dominate and k_ec_fold run between k_ec_count and k_ec_classify: see there.
 //
 // A sum is complete before anything reads it (kernel boundary), a lookup compares the whole key, and a read's outcome goes to the
 // read's own cell: nothing depends on where an insert landed, on the order of the list or on timing.
@@ -140,6 +141,54 @@ __global__ void __launch_bounds__(MIRGE_BLOCK) k_ec_count(EcView v, EcSlot* tab)
             }
         }
     }
+}
+
+// ---- the relative threshold (--kmer-ratio R, mirge_kmer_correct_ratio) ---------------------------------------------------------------
+// A k-mer x with S(x) > H is DOMINATED iff a k-mer y one letter from it has S(y) >= R S(x); a dominated k-mer is weak.  Two launches
+// between k_ec_count and k_ec_classify: k_ec_dominate decides every slot's flag from the complete sums (the table is read-only in it),
+// k_ec_fold then zeroes the flagged sums and keeps their keys (probe chains stay whole).  Behind them "S <= H" says "weak" for
+// k_ec_classify and k_ec_correct as they stand: a valid candidate's windows are all solid, so no zeroed sum enters a score.
+//
+// A thread per slot.  R S(x) is formed once per slot, and only where it fits 64 bits (S(x) <= (2^64 - 1) / R): beyond that no sum
+// reaches it.  The 3 k neighbours x ^ (d << 2 q), q < k, d = 1 .. 3, MIRGE_EC_BATCH home slots in flight together; the walk ends with the
+// batch that holds the first dominating one.  tally2[0] = slots with S > H, tally2[1] = the dominated among them.
+__global__ void __launch_bounds__(MIRGE_BLOCK) k_ec_dominate(EcView v, const EcSlot* __restrict__ tab, uint64_t slots, uint64_t ratio,
+                                                             uint8_t* __restrict__ flag, unsigned long long* __restrict__ tally2) {
+    unsigned long long n_above = 0, n_dom = 0;
+    const int n_nb = 3 * v.k;
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x) {
+        const EcSlot me = tab[s];
+        uint8_t f = 0;
+        if (me.key != MIRGE_EC_EMPTY && me.sum > v.H) {
+            n_above++;
+            if (me.sum <= ~0ull / ratio) {
+                const uint64_t need = me.sum * ratio;  // (no wrap: checked above)
+                for (int c0 = 0; c0 < n_nb && !f; c0 += MIRGE_EC_BATCH) {
+                    uint64_t xs[MIRGE_EC_BATCH];
+                    EcSlot e[MIRGE_EC_BATCH];
+#pragma unroll
+                    for (int u = 0; u < MIRGE_EC_BATCH; u++) {
+                        const int c = c0 + u < n_nb ? c0 + u : n_nb - 1;  // (behind the last neighbour: that one once more, its answer unused)
+                        xs[u] = me.key ^ ((uint64_t)(c % 3 + 1) << (2 * (c / 3)));
+                    }
+#pragma unroll
+                    for (int u = 0; u < MIRGE_EC_BATCH; u++) e[u] = tab[ec_home(v, xs[u])];
+#pragma unroll
+                    for (int u = 0; u < MIRGE_EC_BATCH; u++)
+                        if (c0 + u < n_nb && ec_sum(v, tab, xs[u], e[u]) >= need) f = 1;
+                }
+            }
+            n_dom += f;
+        }
+        flag[s] = f;
+    }
+    if (n_above) atomicAdd(&tally2[0], n_above);
+    if (n_dom) atomicAdd(&tally2[1], n_dom);
+}
+
+__global__ void __launch_bounds__(MIRGE_BLOCK) k_ec_fold(EcSlot* __restrict__ tab, uint64_t slots, const uint8_t* __restrict__ flag) {
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x)
+        if (flag[s]) tab[s].sum = 0;
 }
 
 // range[i] = lo | hi << 16, fix[i] = none; the reads with lo <= hi into list[] (in no order: every listed read's outcome goes

@@ -1,5 +1,6 @@
 // native_ec.hpp -- part of mirge_native.hip (one translation unit): --kmer-correct (kernels_ec.hpp): the rounds of mirge_kmer_correct, each
-// one the spectrum, the classification, the wave kernel and, where a read changed, the regrouping through the weighted collapse.
+// one the spectrum, with a ratio (mirge_kmer_correct_ratio) the relative threshold's two launches, the classification, the wave kernel
+// and, where a read changed, the regrouping through the weighted collapse.
 #pragma once
 
 #define MIRGE_EC_MAX_ROUNDS (MIRGE_EC_MAXK - 8 + 1)
@@ -8,6 +9,8 @@
 // after the round, slots of the round's table
 static thread_local int64_t g_ec_stats[MIRGE_EC_MAX_ROUNDS * MIRGE_EC_STAT_WORDS];
 static thread_local int32_t g_ec_rounds = 0;
+// with a ratio, per round: distinct k-mers with S > H, the dominated among them (zeros without one)
+static thread_local int64_t g_ec_ratio_stats[MIRGE_EC_MAX_ROUNDS * 2];
 
 static int ec_check(const std::string& who, int32_t k_start, int32_t k_end, int32_t threshold) {
     if (threshold < 1) return fail(-1, who + ": the threshold is at least 1");
@@ -147,16 +150,20 @@ static int ec_clone(mirge_ctx* c, const mirge_reads* D, mirge_reads** out) {
     return 0;
 }
 
-extern "C" int mirge_kmer_correct(mirge_ctx* c, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, mirge_reads** out,
-                                  uint32_t* final_of, uint32_t* rounds_mask) {
-    const std::string who = "mirge_kmer_correct";
+// ratio == 0: no relative threshold (mirge_kmer_correct); ratio >= 2: a k-mer above the threshold is weak too when a k-mer one letter
+// from it has at least `ratio` times its sum (k_ec_dominate, k_ec_fold between the spectrum and the classification)
+extern "C" int mirge_kmer_correct_ratio(mirge_ctx* c, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, int32_t ratio,
+                                        mirge_reads** out, uint32_t* final_of, uint32_t* rounds_mask) {
+    const std::string who = ratio ? "mirge_kmer_correct_ratio" : "mirge_kmer_correct";
     if (!c || !uniq || uniq->ctx != c || !out) return fail(-1, who + ": bad argument");
     CHECK(ec_check(who, k_start, k_end, threshold));
+    if (ratio == 1 || ratio < 0) return fail(-1, who + ": the ratio is 0 (none) or at least 2");
     if (uniq->n && uniq->n_samples != 1) return fail(-1, who + ": the reads must be a collapse result with one count column");
     if (uniq->n >= 0x7FFFFFF0ll) return fail(-5, who + ": too many reads for one call");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     g_ec_rounds = k_end - k_start + 1;
     for (int64_t& s : g_ec_stats) s = 0;
+    for (int64_t& s : g_ec_ratio_stats) s = 0;
     *out = nullptr;
     const size_t U = (size_t)uniq->n;
     if (U == 0) {
@@ -202,15 +209,26 @@ extern "C" int mirge_kmer_correct(mirge_ctx* c, const mirge_reads* uniq, int32_t
             EcSlot* tab;
             uint32_t *range, *fix, *list, *words, *next;
             uint32_t tally[MIRGE_EC_T_WORDS];
+            uint8_t* flag = nullptr;
+            unsigned long long *words2 = nullptr, tally2[2] = {0, 0};
+            if (ratio && ((rc = scope.get(&flag, (size_t)slots)) || (rc = scope.get(&words2, (size_t)2)))) break;
             if ((rc = scope.get(&tab, (size_t)slots)) || (rc = scope.get(&range, n)) || (rc = scope.get(&fix, n)) ||
                 (rc = scope.get(&list, n)) || (rc = scope.get(&words, (size_t)MIRGE_EC_T_WORDS)))
                 break;
             hipError_t e = hipMemsetAsync(words, 0, MIRGE_EC_T_WORDS * 4, c->stream);
+            if (e == hipSuccess && ratio) e = hipMemsetAsync(words2, 0, sizeof(tally2), c->stream);
             const dim3 grid(grid_for(c, n)), block(MIRGE_BLOCK);
             { LaunchScope ls(c, "k_ec_clear", (double)slots); hipLaunchKernelGGL(k_ec_clear, dim3(grid_for(c, (size_t)slots)), block, 0, c->stream, tab, slots); }
             { LaunchScope ls(c, "k_ec_count", (double)n); hipLaunchKernelGGL(k_ec_count, grid, block, 0, c->stream, v, tab); }
+            if (ratio) {  // flags from the complete sums, then the flagged sums to 0: two launches
+                const dim3 tgrid(grid_for(c, (size_t)slots));
+                { LaunchScope ls(c, "k_ec_dominate", (double)slots);
+                  hipLaunchKernelGGL(k_ec_dominate, tgrid, block, 0, c->stream, v, (const EcSlot*)tab, slots, (uint64_t)ratio, flag, words2); }
+                { LaunchScope ls(c, "k_ec_fold", (double)slots); hipLaunchKernelGGL(k_ec_fold, tgrid, block, 0, c->stream, tab, slots, (const uint8_t*)flag); }
+            }
             { LaunchScope ls(c, "k_ec_classify", (double)n); hipLaunchKernelGGL(k_ec_classify, grid, block, 0, c->stream, v, (const EcSlot*)tab, range, fix, list, words); }
             if (e == hipSuccess) e = hipMemcpyAsync(tally, words, sizeof(tally), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && ratio) e = hipMemcpyAsync(tally2, words2, sizeof(tally2), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess && tally[MIRGE_EC_T_LIST]) {
@@ -226,6 +244,7 @@ extern "C" int mirge_kmer_correct(mirge_ctx* c, const mirge_reads* uniq, int32_t
             st[0] = tally[MIRGE_EC_T_ELIG]; st[1] = tally[MIRGE_EC_T_SUSPECT]; st[2] = tally[MIRGE_EC_T_CORRECTED];
             st[3] = tally[MIRGE_EC_T_UNCORRECTABLE]; st[4] = tally[MIRGE_EC_T_UNSUPPORTED]; st[5] = tally[MIRGE_EC_T_AMBIGUOUS];
             st[6] = D->n;
+            g_ec_ratio_stats[2 * (k - k_start)] = (int64_t)tally2[0]; g_ec_ratio_stats[2 * (k - k_start) + 1] = (int64_t)tally2[1];
             if (tally[MIRGE_EC_T_CORRECTED]) {  // (no read changed: the dictionary stands, every read is its own successor)
                 if ((rc = scope.get(&next, n))) break;
                 if ((rc = ec_regroup(c, D, fix, &R, next))) break;
@@ -257,10 +276,23 @@ extern "C" int mirge_kmer_correct(mirge_ctx* c, const mirge_reads* uniq, int32_t
     return 0;
 }
 
+extern "C" int mirge_kmer_correct(mirge_ctx* c, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, mirge_reads** out,
+                                  uint32_t* final_of, uint32_t* rounds_mask) {
+    return mirge_kmer_correct_ratio(c, uniq, k_start, k_end, threshold, 0, out, final_of, rounds_mask);
+}
+
 // the last mirge_kmer_correct of this thread: out[8 r + 0..7] for round r (k = k_start + r) = eligible, suspect, corrected, uncorrectable,
 // unsupported, ambiguous reads, distinct reads after the round, slots of the round's table; returns the number of rounds
 extern "C" int mirge_kmer_correct_stats(int64_t* out) {
     if (!out) return fail(-1, "mirge_kmer_correct_stats: bad argument");
     for (int k = 0; k < g_ec_rounds * MIRGE_EC_STAT_WORDS; k++) out[k] = g_ec_stats[k];
+    return g_ec_rounds;
+}
+
+// out[2 r + 0..1] for round r of this thread's last call = distinct k-mers with a sum above the threshold, the dominated among them (zeros
+// when the call had no ratio); returns the number of rounds
+extern "C" int mirge_kmer_correct_ratio_stats(int64_t* out) {
+    if (!out) return fail(-1, "mirge_kmer_correct_ratio_stats: bad argument");
+    for (int k = 0; k < g_ec_rounds * 2; k++) out[k] = g_ec_ratio_stats[k];
     return g_ec_rounds;
 }

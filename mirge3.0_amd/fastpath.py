@@ -160,10 +160,14 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
     sampleReadCounts, trimmedReadCounts, trimmedReadCountsUnique = {}, {}, {}
     parsed = []
     kmer = getattr(args, "kmer_range", None) if getattr(args, "kmer_correct", False) else None  # (k_start, k_end, threshold)
+    kmer_ratio = int(getattr(args, "kmer_ratio", None) or 0) if kmer is not None else 0
     corrected = []
     if kmer is not None and (getattr(args, "AtoI", False) or getattr(args, "gff_out", False)):
         say("NOTE: --kmer-correct with -ai / -gff: a rare true variant whose k-mers are seen at most -kh times is indistinguishable from a "
             "sequencing error and is corrected away")
+        if kmer_ratio:
+            say(f"NOTE: --kmer-ratio {kmer_ratio} with -ai / -gff: a true variant one letter from a k-mer at least {kmer_ratio} times as abundant "
+                "(a minor member of a miRNA family below that share of its sibling) is corrected into it")
     t_read = t_parse = 0.0
     from . import collapse as _collapse
     del _collapse.GZ_LOG[:]
@@ -181,7 +185,7 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
         if kmer is not None:  # the sample's dictionary, corrected on the device, stands for its reads from here on
             outlog.flush()
             t_k = time.perf_counter()
-            corrected.append(kmer_correct_sample(raw, name, workDir, *kmer))
+            corrected.append(kmer_correct_sample(raw, name, workDir, *kmer, ratio=kmer_ratio))
             tm["kmer_correct_s"] = tm.get("kmer_correct_s", 0.0) + time.perf_counter() - t_k
         if getattr(args, "tcf_out", False):
             write_tcf(workDir / (str(name) + ".trim.collapse.fa"), raw, corrected[-1] if kmer is not None else None)

@@ -10,6 +10,13 @@ the timing: per round of k the table's slots and the suspect share, distinct rea
 planted error that end as their template, and the share of error-free raw reads that were changed (false corrections).
 
   python tools/kmer_correct_time.py --rounds 5 --out profiles/kmer_correct.md
+
+``--ratio R`` (may be given several times): in every round, behind the call without a ratio, ``mirge_kmer_correct_ratio`` with each R on
+the same dictionary (interleaved: a round holds one call of each); the report then carries a time, the shares against the truth and per
+round of k the k-mers above H and the dominated among them for every R, and -- from one more call each with the launches bracketed by
+events, outside the timing -- the device time of every ``k_ec_*`` kernel.
+
+  python tools/kmer_correct_time.py --rounds 5 --ratio 8 --ratio 50 --out profiles/kmer_ratio.md
 """
 import argparse
 import os
@@ -62,6 +69,7 @@ def main():
     ap.add_argument("--kh", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--scale", default="full", choices=["ci", "small", "full"], help="size of the synthetic libraries of the cascade")
+    ap.add_argument("--ratio", type=int, action="append", default=[], help="also time mirge_kmer_correct_ratio with this R (repeatable)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ctx = _ffi.Context(0)
@@ -70,6 +78,8 @@ def main():
     casc = Cascade(ctx, synth.make_libraries(seed=20260101, scale=a.scale).libs)  # (bench.py's libraries)
     fig = {k: [] for k in ("parse_s", "collapse_cascade_s", "kmer_correct_s")}
     info, per_k = {}, []
+    ratio_s = {R: [] for R in a.ratio}
+    ratio_info, ratio_per_k, kernel_ms = {}, {}, {}
     for rnd in range(a.rounds + 1):
         tm = {}
         t = time.perf_counter()
@@ -84,6 +94,11 @@ def main():
         out, final_of, masks = d0.kmer_correct(a.ks, a.ke, a.kh)
         tm["kmer_correct_s"] = time.perf_counter() - t
         stats = _ffi.kmer_correct_stats()
+        for R in a.ratio:
+            t = time.perf_counter()
+            o2, _, _ = d0.kmer_correct(a.ks, a.ke, a.kh, ratio=R)
+            tm[R] = time.perf_counter() - t
+            o2.close()
         t = time.perf_counter()
         uniq, res = casc.collapse_and_run(raw)
         ctx.sync()
@@ -97,6 +112,23 @@ def main():
             final = after[final_of[handle]]
             is_template = final == truth.view(f"S{WIDTH}").reshape(-1)
             changed = final != reads.view(f"S{WIDTH}").reshape(-1)
+            for R in a.ratio:  # the same against the truth for every ratio, and the kernels' device times
+                o2, f2, m2 = d0.kmer_correct(a.ks, a.ke, a.kh, ratio=R)
+                ratio_per_k[R] = list(zip(_ffi.kmer_correct_stats(), _ffi.kmer_correct_ratio_stats()))
+                fin2 = rows_of(o2.unpack())[f2[handle]]
+                tpl2, chg2 = fin2 == truth.view(f"S{WIDTH}").reshape(-1), fin2 != reads.view(f"S{WIDTH}").reshape(-1)
+                ratio_info[R] = dict(distinct_after=len(o2), distinct_reads_changed=int((m2 != 0).sum()),
+                                     planted_errors_restored_share=round(float(tpl2[planted].mean()), 4),
+                                     planted_errors_changed_to_something_else_share=round(float((chg2 & ~tpl2)[planted].mean()), 4),
+                                     error_free_reads_changed_share=round(float(chg2[~planted].mean()), 6))
+                o2.close()
+            for R in ([0] + a.ratio if a.ratio else []):
+                ctx.profile(True); ctx.profile_only("k_ec_"); ctx.profile_reset()
+                o2, _, _ = d0.kmer_correct(a.ks, a.ke, a.kh, ratio=R)
+                ctx.sync()
+                kernel_ms[R] = {name: (launches, ms) for name, launches, ms, _ in ctx.profile_records()}
+                ctx.profile(False); ctx.profile_only("")
+                o2.close()
             info = dict(raw_reads=a.reads, raw_reads_with_a_planted_error=int(planted.sum()), distinct_before=len(d0), distinct_after=len(out),
                         distinct_reads_changed=int((masks != 0).sum()),
                         planted_errors_restored_share=round(float(is_template[planted].mean()), 4),
@@ -107,6 +139,8 @@ def main():
         if rnd:
             for k in fig:
                 fig[k].append(tm[k])
+            for R in a.ratio:
+                ratio_s[R].append(tm[R])
     lines = ["# --kmer-correct on one MI355X (tools/kmer_correct_time.py)", "",
              f"`--reads {a.reads} --templates {a.templates} --error {a.error} --ks {a.ks} --ke {a.ke} --kh {a.kh} --rounds {a.rounds}`", "",
              ", ".join(f"{k} = {v}" for k, v in info.items()), "",
@@ -119,6 +153,24 @@ def main():
         share = st["suspect"] / st["eligible"] if st["eligible"] else 0.0
         lines.append(f"| {a.ks + r} | {st['slots']} | {st['eligible']} | {st['suspect']} | {share:.4f} | {st['corrected']} | {st['uncorrectable']} | "
                      f"{st['unsupported']} | {st['ambiguous']} | {st['distinct']} |")
+    if a.ratio:
+        lines += ["", "## --kmer-ratio", "", "| call | median s | min .. max | planted errors restored | changed to something else | error-free reads changed | distinct after |",
+                  "|---|---|---|---|---|---|---|"]
+        rows = [("ratio 0", fig["kmer_correct_s"], info)] + [(f"ratio {R}", ratio_s[R], ratio_info[R]) for R in a.ratio]
+        for name, v, i in rows:
+            lines.append(f"| {name} | {statistics.median(v):.4f} | {min(v):.4f} .. {max(v):.4f} | {i['planted_errors_restored_share']} | "
+                         f"{i['planted_errors_changed_to_something_else_share']} | {i['error_free_reads_changed_share']} | {i['distinct_after']} |")
+        for R in a.ratio:
+            lines += ["", f"ratio {R}:", "", "| k | k-mers above -kh (A) | dominated (D) | suspect | corrected | uncorrectable | unsupported | ambiguous | distinct after |",
+                      "|---|---|---|---|---|---|---|---|---|"]
+            for r, (st, rs) in enumerate(ratio_per_k[R]):
+                lines.append(f"| {a.ks + r} | {rs['above']} | {rs['dominated']} | {st['suspect']} | {st['corrected']} | {st['uncorrectable']} | {st['unsupported']} | "
+                             f"{st['ambiguous']} | {st['distinct']} |")
+        names = sorted({n for rec in kernel_ms.values() for n in rec})
+        lines += ["", "device time of the kernels over one call's rounds (event-bracketed launches, one call each, outside the timing), ms (launches):", "",
+                  "| kernel | " + " | ".join(f"ratio {R}" for R in kernel_ms) + " |", "|---|" + "---|" * len(kernel_ms)]
+        for n in names:
+            lines.append(f"| {n} | " + " | ".join(f"{rec[n][1]:.3f} ({rec[n][0]})" if n in rec else "-" for rec in kernel_ms.values()) + " |")
     lines.append("")
     text_out = "\n".join(lines)
     print(text_out)
