@@ -7,8 +7,10 @@ MI355X is visible, the first call raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import weakref
 import os
+import re
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -19,22 +21,133 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MIRGE_NATIVE_SO: A/B builds of the same library when tuning kernels (never a different backend)
 SO_PATH = os.environ.get("MIRGE_NATIVE_SO") or os.path.join(_HERE, "csrc", "libmirge_native.so")
 
-EXPORTS = [
-    "mirge_last_error", "mirge_device_count", "mirge_gz_inflate", "mirge_gz_inflate_progress", "mirge_ctx_create", "mirge_ctx_destroy", "mirge_ctx_sync", "mirge_ctx_pool_stats",
-    "mirge_lib_create", "mirge_lib_create_packed", "mirge_lib_packed_sizes", "mirge_lib_packed_copy", "mirge_lib_destroy", "mirge_lib_n_refs", "mirge_lib_device_bytes", "mirge_lib_prepare",
-    "mirge_reads_pack", "mirge_reads_parse", "mirge_reads_parse_trim", "mirge_reads_parse_umi", "mirge_reads_concat", "mirge_reads_destroy", "mirge_reads_count", "mirge_reads_total_bases",
-    "mirge_reads_n_samples", "mirge_reads_group_counts", "mirge_reads_iupac_seen", "mirge_reads_unpack", "mirge_collapse", "mirge_collapse_weighted", "mirge_collapse_merge", "mirge_collapse_fetch", "mirge_collapse_order", "mirge_collapse_order_sorted", "mirge_collapse_nonzero",
-    "mirge_reads_set_counts", "mirge_cascade_run", "mirge_collapse_cascade", "mirge_result_fetch", "mirge_result_destroy",
-    "mirge_count_join", "mirge_count_join_host", "mirge_annotation_csv", "mirge_annotation_csv_device", "mirge_variant_tally", "mirge_isomir_type", "mirge_gff_write", "mirge_gff_write_device", "mirge_ctx_timer_start", "mirge_ctx_timer_stop", "mirge_ctx_profile_enable",
-    "mirge_reads_range_sample", "mirge_reads_range_split", "mirge_annotation_csv_device_sizes", "mirge_annotation_csv_device_at",
-    "mirge_cascade_prepare", "mirge_cascade_walks", "mirge_cascade_wg_times", "mirge_ctx_profile_only", "mirge_ctx_profile_units", "mirge_ctx_profile_reset", "mirge_ctx_profile_count", "mirge_ctx_profile_get",
-    "mirge_genome_create", "mirge_genome_create_packed", "mirge_genome_destroy", "mirge_genome_align_counts",
-    "mirge_genome_align_loci", "mirge_genome_align_loci_strata", "mirge_loci_count", "mirge_loci_fetch", "mirge_loci_destroy", "mirge_loci_cluster",
-    "mirge_cluster_diagonals", "mirge_cluster_pileup", "mirge_genome_fetch", "mirge_sam_write_device", "mirge_bam_write_device", "mirge_bam_huffman_probe",
-    "mirge_trf_hits_run", "mirge_trf_hits_count", "mirge_trf_hits_fetch", "mirge_trf_hits_destroy", "mirge_trf_assign", "mirge_trf_row_counts",
-    "mirge_trf_cluster", "mirge_umi_cluster", "mirge_umi_cluster_stats", "mirge_kmer_correct", "mirge_kmer_correct_stats", "mirge_kmer_correct_ratio", "mirge_kmer_correct_ratio_stats", "mirge_coverage_runs", "mirge_coverage_write_device",
-    "mirge_bigwig_from_intervals", "mirge_bigwig_write_device",
-]
+# Every entry point of include/mirge_native.h, in the header's order and spelling without the parameter names (tests/test_ffi_signatures.py
+# holds the two together): the one statement of the ABI on this side.  bind() turns it into restype / argtypes.
+_PROTOTYPES = """
+const char* mirge_last_error();
+int mirge_device_count();
+int mirge_ctx_create(int, void*, mirge_ctx**);
+void mirge_ctx_destroy(mirge_ctx*);
+int mirge_ctx_sync(mirge_ctx*);
+int mirge_ctx_pool_stats(mirge_ctx*, int64_t*);
+int mirge_lib_create(mirge_ctx*, const char*, const int64_t*, int64_t, mirge_lib**);
+int mirge_lib_create_packed(mirge_ctx*, const uint64_t*, int64_t, const uint64_t*, int64_t, const uint32_t*, int64_t, uint64_t, int32_t, uint64_t, mirge_lib**);
+int mirge_lib_packed_sizes(const mirge_lib*, int64_t*, int32_t*);
+int mirge_lib_packed_copy(const mirge_lib*, uint64_t*, uint64_t*, uint32_t*);
+void mirge_lib_destroy(mirge_lib*);
+int64_t mirge_lib_n_refs(const mirge_lib*);
+int64_t mirge_lib_device_bytes(const mirge_lib*);
+int mirge_lib_prepare(mirge_lib*, int32_t);
+int mirge_gz_inflate(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*, int32_t);
+int mirge_gz_inflate_progress(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*, int32_t, int64_t*);
+int mirge_reads_pack(mirge_ctx*, const char*, const int64_t*, int64_t, mirge_reads**);
+int mirge_reads_parse(mirge_ctx*, const char*, int64_t, int32_t, int32_t, mirge_reads**, int64_t*);
+int32_t mirge_reads_iupac_seen(const mirge_reads*);
+int mirge_reads_parse_trim(mirge_ctx*, const char*, int64_t, int32_t, int32_t, const mirge_trim*, mirge_reads**, int64_t*);
+int mirge_reads_parse_umi(mirge_ctx*, const char*, int64_t, int32_t, int32_t, const mirge_trim*, const mirge_umi*, mirge_reads**, int64_t*, mirge_reads**);
+int mirge_umi_cluster(mirge_ctx*, const mirge_reads*, int32_t, int32_t, uint8_t*, int64_t*);
+int mirge_umi_cluster_stats(int64_t*);
+int mirge_kmer_correct(mirge_ctx*, const mirge_reads*, int32_t, int32_t, int32_t, mirge_reads**, uint32_t*, uint32_t*);
+int mirge_kmer_correct_stats(int64_t*);
+int mirge_kmer_correct_ratio(mirge_ctx*, const mirge_reads*, int32_t, int32_t, int32_t, int32_t, mirge_reads**, uint32_t*, uint32_t*);
+int mirge_kmer_correct_ratio_stats(int64_t*);
+int mirge_reads_concat(mirge_ctx*, const mirge_reads* const*, int32_t, mirge_reads**);
+void mirge_reads_destroy(mirge_reads*);
+int64_t mirge_reads_count(const mirge_reads*);
+int64_t mirge_reads_total_bases(const mirge_reads*);
+int32_t mirge_reads_n_samples(const mirge_reads*);
+int32_t mirge_reads_group_counts(const mirge_reads*, int64_t*, int32_t);
+int mirge_reads_unpack(mirge_ctx*, const mirge_reads*, char*, int64_t*);
+int mirge_collapse(mirge_ctx*, const mirge_reads*, const int32_t*, int32_t, mirge_reads**, int64_t*);
+int mirge_collapse_weighted(mirge_ctx*, const mirge_reads*, const int32_t*, int32_t, const uint32_t*, mirge_reads**, int64_t*);
+int mirge_collapse_merge(mirge_ctx*, const mirge_reads* const*, int32_t, mirge_reads**, int64_t*);
+int mirge_collapse_fetch(mirge_ctx*, const mirge_reads*, uint32_t*, int64_t*);
+int mirge_collapse_order(mirge_ctx*, const mirge_reads*, int64_t*);
+int mirge_collapse_order_sorted(mirge_ctx*, const mirge_reads*, int64_t*);
+int mirge_collapse_nonzero(mirge_ctx*, const mirge_reads*, int64_t*);
+int mirge_reads_set_counts(mirge_ctx*, mirge_reads*, const uint32_t*, int32_t);
+int mirge_cascade_run(mirge_ctx*, const mirge_reads*, const mirge_lib* const*, const mirge_policy*, int32_t, mirge_result**);
+int mirge_cascade_prepare(mirge_ctx*, const mirge_reads*, const mirge_lib* const*, const mirge_policy*, int32_t);
+int mirge_cascade_walks(mirge_ctx*, int32_t*);
+int mirge_cascade_wg_times(mirge_ctx*, uint32_t*, int32_t, int32_t*, int32_t*);
+int mirge_collapse_cascade(mirge_ctx*, const mirge_reads*, const mirge_lib* const*, const mirge_policy*, int32_t, mirge_reads**, int64_t*, mirge_result**);
+int mirge_result_fetch(mirge_ctx*, const mirge_result*, int8_t*, int32_t*, int32_t*, int8_t*);
+void mirge_result_destroy(mirge_result*);
+int mirge_count_join(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, int32_t, int64_t, int64_t*, int64_t*, int64_t*);
+int mirge_count_join_host(mirge_ctx*, const int8_t*, const int32_t*, const uint32_t*, int64_t, int32_t, int32_t, int32_t, int32_t, int64_t, int64_t*, int64_t*, int64_t*);
+int mirge_annotation_csv(const char*, const char*, const char*, const char*, const int64_t*, const int8_t*, const int32_t*, const uint32_t*, int32_t, const int64_t*,
+    int64_t, int32_t, const int32_t*, int32_t, const char* const*, const int64_t* const*, const int64_t*);
+int mirge_annotation_csv_device(mirge_ctx*, const mirge_reads*, const mirge_result*, const char*, const char*, const char*, const int64_t*, int64_t, int32_t,
+    const int32_t*, int32_t, const char* const*, const int64_t* const*, const int64_t*);
+int mirge_reads_range_sample(mirge_ctx*, const mirge_reads*, int32_t, uint64_t*);
+int mirge_reads_range_split(mirge_ctx*, const mirge_reads*, const uint64_t*, int32_t, char*, int64_t*, uint32_t*, int64_t*);
+int mirge_annotation_csv_device_sizes(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int64_t, int32_t, const int32_t*, int32_t, const char* const*,
+    const int64_t* const*, const int64_t*, int64_t*);
+int mirge_annotation_csv_device_at(mirge_ctx*, const mirge_reads*, const mirge_result*, const char*, const char*, int64_t, int64_t, const int64_t*, int64_t, int32_t,
+    const int32_t*, int32_t, const char* const*, const int64_t* const*, const int64_t*);
+int mirge_variant_tally(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, int32_t, const int32_t*, int64_t, const char*, const int64_t*, int64_t,
+    const uint8_t*, const double*, int64_t*, int64_t*, int8_t*, int8_t*);
+int mirge_isomir_type(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, int32_t, const int32_t*, int64_t, const char*, const int32_t*, const int32_t*,
+    const int32_t*, int64_t, const char*, const int32_t*, int64_t, const int32_t*, int64_t, void*);
+int mirge_gff_write(const char*, const char*, const char*, const void*, int64_t, const char*, const int64_t*, const uint32_t*, int32_t, const int32_t*, const char*,
+    const int64_t*, int64_t, const int32_t*, const char*, const int64_t*, int64_t, const int64_t*, int64_t);
+int mirge_gff_write_device(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, int32_t, const int32_t*, int64_t, const char*, const int32_t*, const int32_t*,
+    const int32_t*, int64_t, const char*, const int32_t*, int64_t, const int32_t*, const char*, const int64_t*, int64_t, const int32_t*, const char*, const int64_t*,
+    int64_t, const int64_t*, const char*, const char*, const char*, int64_t*);
+int mirge_genome_create(mirge_ctx*, const char*, const int64_t*, int64_t, mirge_genome**);
+int mirge_genome_create_packed(mirge_ctx*, const uint8_t*, int64_t, const uint64_t*, const uint64_t*, const uint8_t*, int64_t, mirge_genome**);
+void mirge_genome_destroy(mirge_genome*);
+int mirge_genome_align_counts(mirge_ctx*, const mirge_genome*, const char*, const int64_t*, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint32_t*);
+int mirge_genome_align_loci(mirge_ctx*, const mirge_genome*, const char*, const int64_t*, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, int32_t,
+    uint64_t*, mirge_loci**);
+int mirge_genome_align_loci_strata(mirge_ctx*, const mirge_genome*, const char*, const int64_t*, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, int32_t,
+    int32_t, uint64_t*, mirge_loci**);
+int64_t mirge_loci_count(const mirge_loci*);
+int mirge_loci_fetch(const mirge_loci*, uint32_t*, uint32_t*, uint64_t*, uint8_t*, uint8_t*);
+void mirge_loci_destroy(mirge_loci*);
+int mirge_loci_cluster(mirge_ctx*, int64_t, const uint32_t*, const uint64_t*, const uint8_t*, const uint32_t*, int64_t, const int32_t*, const int64_t*, int64_t,
+    const uint8_t*, int32_t, int32_t, int32_t*, int64_t*, uint32_t*, uint8_t*, uint64_t*, uint64_t*, int64_t*, uint32_t*);
+int mirge_cluster_diagonals(mirge_ctx*, const char*, const int64_t*, int64_t, const char*, const int64_t*, int64_t, const uint32_t*, int32_t*, int32_t*, int32_t*,
+    uint8_t*);
+int mirge_cluster_pileup(mirge_ctx*, const char*, const int64_t*, int64_t, const int64_t*, const int64_t*, int64_t, const int32_t*, const int64_t*, int32_t*, int32_t*,
+    int64_t*, int64_t*, int64_t);
+int mirge_genome_fetch(mirge_ctx*, const mirge_genome*, int64_t, const uint32_t*, const int64_t*, const int64_t*, const uint8_t*, const uint8_t*, const int64_t*, char*);
+int mirge_sam_write_device(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*, int32_t,
+    const char*, const char*, int64_t, int64_t*, int64_t*);
+int mirge_bam_write_device(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*, int32_t,
+    const int32_t*, const int64_t*, int32_t, const char*, const char*, const char*, int64_t, int32_t, int64_t*, int64_t*, int64_t*);
+int mirge_bam_huffman_probe(mirge_ctx*, const uint32_t*, int32_t, int32_t, uint8_t*);
+int mirge_coverage_runs(mirge_ctx*, int64_t, const int32_t*, const int64_t*, const int32_t*, const uint32_t*, const uint8_t*, int32_t, uint8_t*, int32_t*, int64_t*,
+    int64_t*, int64_t*, int64_t*);
+int mirge_coverage_write_device(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*, int32_t,
+    const int32_t*, const int64_t*, int32_t, const char*, const int64_t*, int32_t, const char*, const char*, int64_t*, int64_t*, int64_t*, int64_t*, int64_t*);
+int mirge_bigwig_from_intervals(mirge_ctx*, int64_t, const int32_t*, const int64_t*, const int32_t*, const uint32_t*, const uint8_t*, int32_t, int32_t, const char*,
+    const int64_t*, const int64_t*, const int32_t*, const char*, const char*, int64_t*, int64_t*);
+int mirge_bigwig_write_device(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*, int32_t,
+    const int32_t*, const int64_t*, int32_t, const char*, const int64_t*, const int64_t*, const int32_t*, int32_t, const char*, const char*, int64_t*, int64_t*);
+int mirge_trf_hits_run(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, const mirge_lib*, const mirge_policy*, int32_t, const mirge_lib*,
+    const mirge_policy*, const int64_t*, int64_t, const int32_t*, mirge_trf_hits**);
+int64_t mirge_trf_hits_count(const mirge_trf_hits*);
+int mirge_trf_hits_fetch(const mirge_trf_hits*, uint32_t*, uint32_t*, int32_t*, uint8_t*, uint8_t*, uint8_t*);
+void mirge_trf_hits_destroy(mirge_trf_hits*);
+int mirge_trf_assign(mirge_ctx*, const mirge_reads*, const mirge_result*, int64_t, const int64_t*, const int32_t*, const int32_t*, int64_t, const int64_t*, int64_t,
+    const int64_t*, const char*, const int32_t*, const int32_t*, const int32_t*, int32_t*, int32_t*);
+int mirge_trf_row_counts(mirge_ctx*, const mirge_reads*, const int64_t*, int64_t, uint32_t*);
+int mirge_trf_cluster(mirge_ctx*, const mirge_reads*, int64_t, const int64_t*, const int64_t*, const int32_t*, const double*, const int32_t*, int64_t, const double*,
+    float*, float*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*);
+int mirge_ctx_timer_start(mirge_ctx*);
+int mirge_ctx_timer_stop(mirge_ctx*, double*);
+int mirge_ctx_profile_enable(mirge_ctx*, int32_t);
+int mirge_ctx_profile_only(mirge_ctx*, const char*);
+int mirge_ctx_profile_units(mirge_ctx*, int32_t);
+int mirge_ctx_profile_reset(mirge_ctx*);
+int32_t mirge_ctx_profile_count(mirge_ctx*);
+int mirge_ctx_profile_get(mirge_ctx*, int32_t, char*, int32_t, int64_t*, double*, double*);
+"""
+# name -> (return type, parameter types)
+SIGNATURES = {name: (ret, tuple(params.split(", ")) if params else ())
+              for ret, name, params in re.findall(r"(\S[^;()]*?) (mirge_\w+)\(([^)]*)\);", " ".join(_PROTOTYPES.split()))}
+EXPORTS = list(SIGNATURES)
 
 
 class MirgePolicy(C.Structure):
@@ -108,6 +221,62 @@ class MirgeUmi(C.Structure):
         return "directional" if self.dedup == 2 else None
 
 
+class SamPass(C.Structure):
+    """``mirge_sam_pass`` of include/mirge_native.h"""
+    _fields_ = [("lib", C.c_void_p), ("trim5", C.c_int32), ("trim3", C.c_int32), ("n_refs", C.c_int64), ("chrom_of_ref", C.c_void_p),
+                ("minus", C.c_void_p), ("seg_ptr", C.c_void_p), ("seg_s", C.c_void_p), ("seg_e", C.c_void_p), ("cds_lo", C.c_void_p),
+                ("cds_hi", C.c_void_p), ("n_chrom", C.c_int64), ("chrom_data", C.c_void_p), ("chrom_off", C.c_void_p)]
+
+
+_SCALARS = {"void": None, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
+_STRUCTS = {"mirge_policy": MirgePolicy, "mirge_trim": MirgeTrim, "mirge_umi": MirgeUmi, "mirge_sam_pass": SamPass}
+_ELEMENTS = {"char": "uint8", "void": None, "float": "float32", "double": "float64",
+             **{t + "_t": t for t in ("int8", "uint8", "int32", "uint32", "int64", "uint64")}}  # C element type -> dtype (None: any)
+
+
+class _ArrayPtr:
+    """The ``argtypes`` entry of a pointer to numbers or bytes: None (NULL); a numpy array of exactly the element type (``void``: any),
+    C-contiguous and, unless the pointer is const, writeable; ``bytes`` for a const pointer to bytes; else whatever ``c_void_p``
+    takes -- a ``c_void_p``, ``byref(x)``, a ctypes array -- unchecked."""
+
+    def __init__(self, ctype: str, elem: str, const: bool):
+        self.ctype, self.dtype, self.const = ctype, _ELEMENTS[elem] and np.dtype(_ELEMENTS[elem]), const
+        self.bytes_ok = const and elem in ("char", "uint8_t", "void")
+
+    def from_param(self, a):
+        if isinstance(a, np.ndarray):
+            flags = a.flags
+            if (self.dtype is not None and a.dtype != self.dtype) or not flags.c_contiguous or not (self.const or flags.writeable):
+                raise TypeError(f"{self.ctype} takes a C-contiguous{'' if self.const else ', writeable'} array of dtype "
+                                f"{'any' if self.dtype is None else self.dtype.name}; this one is {a.dtype.name}")
+            return C.c_void_p(a.ctypes.data)
+        if isinstance(a, str) or (isinstance(a, bytes) and not self.bytes_ok):
+            raise TypeError(f"{self.ctype} takes no {type(a).__name__}")
+        return C.c_void_p.from_param(a)
+
+
+@functools.lru_cache(maxsize=None)
+def _ctype(t: str):
+    """the ctypes type of a parameter or return type as the header spells it (one object per spelling)"""
+    elem = t.replace("const ", "").split("*")[0]
+    if "*" not in t:
+        return _SCALARS[t]
+    if t.count("*") > 1 or (elem.startswith("mirge_") and elem not in _STRUCTS):
+        return C.c_void_p  # opaque handles, out-handles and arrays of pointers
+    return C.POINTER(_STRUCTS[elem]) if elem in _STRUCTS else _ArrayPtr(t, elem, t.startswith("const "))  # (KeyError: a type of no kind)
+
+
+def bind(lib: C.CDLL) -> C.CDLL:
+    """Declare ``restype`` and ``argtypes`` of every entry point of SIGNATURES that ``lib`` has; one it lacks (an older A/B build named
+    by MIRGE_NATIVE_SO) is skipped and fails when it is called."""
+    for name, (ret, params) in SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = C.c_char_p if ret == "const char*" else _ctype(ret)
+            fn.argtypes = [_ctype(t) for t in params]
+    return lib
+
+
 _lib = None
 _live = []  # weak references to every wrapper, closed in dependency order at interpreter exit
 
@@ -121,20 +290,8 @@ def load() -> C.CDLL:
         raise RuntimeError(
             f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  mirge3.0_amd has no CPU fallback.")
-    lib = C.CDLL(SO_PATH)
-    lib.mirge_last_error.restype = C.c_char_p
-    for name in ("mirge_lib_n_refs", "mirge_lib_device_bytes", "mirge_reads_count", "mirge_reads_total_bases"):
-        getattr(lib, name).restype = C.c_int64
-    for name in ("mirge_lib_destroy", "mirge_reads_destroy", "mirge_result_destroy", "mirge_ctx_destroy", "mirge_genome_destroy"):
-        getattr(lib, name).restype = None
-    if hasattr(lib, "mirge_loci_count"):  # absent from an older A/B build (MIRGE_NATIVE_SO)
-        lib.mirge_loci_count.restype = C.c_int64
-        lib.mirge_loci_destroy.restype = None
-    if hasattr(lib, "mirge_trf_hits_count"):
-        lib.mirge_trf_hits_count.restype = C.c_int64
-        lib.mirge_trf_hits_destroy.restype = None
-    _lib = lib
-    return lib
+    _lib = bind(C.CDLL(SO_PATH))
+    return _lib
 
 
 def _track(obj):
@@ -167,10 +324,6 @@ def _check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
-def _p(a: Optional[np.ndarray]):
-    return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
-
-
 def gz_inflate(data, threads: int = 0) -> Optional[np.ndarray]:
     """The text of a whole .gz file (``data``: its bytes) inflated on all host cores (``mirge_gz_inflate``), or None when the
     file is not of a kind that route takes -- the caller then inflates it serially.  Verified against the file's CRC-32."""
@@ -189,7 +342,7 @@ def gz_inflate(data, threads: int = 0) -> Optional[np.ndarray]:
     except MemoryError:  # (a host that does not overcommit): the streamed route needs pieces only
         return None
     n = C.c_int64(0)
-    rc = load().mirge_gz_inflate(_p(buf), C.c_int64(buf.size), _p(out), C.c_int64(cap), C.byref(n), C.c_int32(threads or gz_threads()))
+    rc = load().mirge_gz_inflate(buf, buf.size, out, cap, C.byref(n), threads or gz_threads())
     if rc != 0:
         return None
     return out[: n.value]
@@ -252,8 +405,8 @@ class GzInflation:
         lib = load()
 
         def run():
-            rc = lib.mirge_gz_inflate_progress(_p(self.buf), C.c_int64(self.buf.size), _p(self.out), C.c_int64(cap), C.byref(self._n),
-                                               C.c_int32(threads or gz_threads()), C.byref(self._progress))
+            rc = lib.mirge_gz_inflate_progress(self.buf, self.buf.size, self.out, cap, C.byref(self._n), threads or gz_threads(),
+                                               C.byref(self._progress))
             self.ok = rc == 0
 
         # (not a daemon: the interpreter waits for it at exit -- a fraction of a second -- instead of freeing the buffers under it)
@@ -294,7 +447,7 @@ class Context:
         if lib.mirge_device_count() <= 0:
             raise RuntimeError("no HIP device visible: mirge3.0_amd needs an MI355X (no CPU fallback)")
         self._h = C.c_void_p()
-        _check(lib.mirge_ctx_create(C.c_int(device), C.c_void_p(stream), C.byref(self._h)), "mirge_ctx_create")
+        _check(lib.mirge_ctx_create(device, C.c_void_p(stream), C.byref(self._h)), "mirge_ctx_create")
         self.device = device
         _track(self)
 
@@ -336,7 +489,7 @@ class Context:
         return ms.value
 
     def profile(self, on: bool):
-        _check(load().mirge_ctx_profile_enable(self._h, C.c_int32(1 if on else 0)), "profile_enable")
+        _check(load().mirge_ctx_profile_enable(self._h, bool(on)), "profile_enable")
 
     def profile_only(self, substr: str = ""):
         """bracket only the launches whose name contains ``substr`` ('' = all)"""
@@ -344,7 +497,7 @@ class Context:
 
     def profile_units(self, on: bool):
         """False: bracketed cascade launches are timed, their per-pass read counts are not copied back any more"""
-        _check(load().mirge_ctx_profile_units(self._h, C.c_int32(1 if on else 0)), "profile_units")
+        _check(load().mirge_ctx_profile_units(self._h, bool(on)), "profile_units")
 
     def profile_reset(self):
         _check(load().mirge_ctx_profile_reset(self._h), "profile_reset")
@@ -356,8 +509,7 @@ class Context:
         for i in range(lib.mirge_ctx_profile_count(self._h)):
             name = C.create_string_buffer(64)
             launches, ms, units = C.c_int64(), C.c_double(), C.c_double()
-            _check(lib.mirge_ctx_profile_get(self._h, C.c_int32(i), name, C.c_int32(64), C.byref(launches),
-                                             C.byref(ms), C.byref(units)), "profile_get")
+            _check(lib.mirge_ctx_profile_get(self._h, i, name, 64, C.byref(launches), C.byref(ms), C.byref(units)), "profile_get")
             out.append((name.value.decode(), launches.value, ms.value, units.value))
         return out
 
@@ -373,14 +525,12 @@ class DeviceLibrary:
             T = np.ascontiguousarray(packed["T"], dtype=np.uint64)
             inv = np.ascontiguousarray(packed["inv"], dtype=np.uint64)
             rs = np.ascontiguousarray(packed["ref_start"], dtype=np.uint32)
-            _check(load().mirge_lib_create_packed(ctx._h, _p(T), C.c_int64(T.shape[0]), _p(inv), C.c_int64(inv.shape[0]), _p(rs),
-                                                  C.c_int64(len(seqs)), C.c_uint64(int(packed["total"])), C.c_int32(int(packed["kmax"])),
-                                                  C.c_uint64(int(packed["valid_positions"])), C.byref(self._h)), "mirge_lib_create_packed")
+            _check(load().mirge_lib_create_packed(ctx._h, T, T.shape[0], inv, inv.shape[0], rs, len(seqs), packed["total"], packed["kmax"],
+                                                  packed["valid_positions"], C.byref(self._h)), "mirge_lib_create_packed")
         else:
             data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
             off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
-            _check(load().mirge_lib_create(ctx._h, _p(data), _p(off), C.c_int64(len(seqs)), C.byref(self._h)),
-                   "mirge_lib_create")
+            _check(load().mirge_lib_create(ctx._h, data, off, len(seqs), C.byref(self._h)), "mirge_lib_create")
         _track(self)
 
     def packed_image(self) -> dict:
@@ -391,7 +541,7 @@ class DeviceLibrary:
         T = np.empty(int(sizes[0]), dtype=np.uint64)
         inv = np.empty(int(sizes[1]), dtype=np.uint64)
         rs = np.empty(self.n_refs + 1, dtype=np.uint32)
-        _check(load().mirge_lib_packed_copy(self._h, _p(T), _p(inv), _p(rs)), "mirge_lib_packed_copy")
+        _check(load().mirge_lib_packed_copy(self._h, T, inv, rs), "mirge_lib_packed_copy")
         return {"T": T, "inv": inv, "ref_start": rs, "total": int(sizes[2]), "kmax": int(kmax.value), "valid_positions": int(sizes[3])}
 
     @property
@@ -403,7 +553,7 @@ class DeviceLibrary:
         return load().mirge_lib_device_bytes(self._h)
 
     def prepare(self, k: int):
-        _check(load().mirge_lib_prepare(self._h, C.c_int32(k)), "mirge_lib_prepare")
+        _check(load().mirge_lib_prepare(self._h, k), "mirge_lib_prepare")
 
     def close(self):
         if self._h:
@@ -428,12 +578,12 @@ class DeviceGenome:
         if seqs is not None:
             data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
             off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
-            _check(load().mirge_genome_create(ctx._h, _p(data), _p(off), C.c_int64(len(seqs)), C.byref(self._h)), "mirge_genome_create")
+            _check(load().mirge_genome_create(ctx._h, data, off, len(seqs), C.byref(self._h)), "mirge_genome_create")
         else:
             pk = np.ascontiguousarray(packed, dtype=np.uint8)
             ro, rl, rf = (np.ascontiguousarray(a, dtype=t) for a, t in zip(records, (np.uint64, np.uint64, np.uint8)))
-            _check(load().mirge_genome_create_packed(ctx._h, _p(pk), C.c_int64(pk.shape[0]), _p(ro), _p(rl), _p(rf),
-                                                     C.c_int64(ro.shape[0]), C.byref(self._h)), "mirge_genome_create_packed")
+            _check(load().mirge_genome_create_packed(ctx._h, pk, pk.shape[0], ro, rl, rf, ro.shape[0], C.byref(self._h)),
+                   "mirge_genome_create_packed")
         _track(self)
 
     def align_counts(self, seqs: FlatSeqs, n_mm: int, seedlen: int = 28, maxtotal: int = 2, trim5: int = 0, trim3: int = 2) -> np.ndarray:
@@ -442,9 +592,8 @@ class DeviceGenome:
         out = np.zeros((max(n, 1), 3), dtype=np.uint32)
         data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
         off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
-        _check(load().mirge_genome_align_counts(self.ctx._h, self._h, _p(data) if data.size else C.c_void_p(0), _p(off), C.c_int64(n),
-                                                C.c_int32(n_mm), C.c_int32(seedlen), C.c_int32(maxtotal), C.c_int32(trim5),
-                                                C.c_int32(trim3), _p(out)), "mirge_genome_align_counts")
+        _check(load().mirge_genome_align_counts(self.ctx._h, self._h, data if data.size else None, off, n, n_mm, seedlen, maxtotal, trim5,
+                                                trim3, out), "mirge_genome_align_counts")
         return out[:n]
 
     def align_loci(self, seqs: FlatSeqs, n_mm: int, seedlen: int = 28, maxtotal: int = 2, trim5: int = 0, trim3: int = 0,
@@ -460,18 +609,17 @@ class DeviceGenome:
         data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
         off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
         h = C.c_void_p()
-        head = (self.ctx._h, self._h, _p(data) if data.size else C.c_void_p(0), _p(off), C.c_int64(n), C.c_int32(n_mm), C.c_int32(seedlen),
-                C.c_int32(maxtotal), C.c_int32(trim5), C.c_int32(trim3), C.c_int64(max_loci), C.c_int32(1 if norc else 0))
+        head = (self.ctx._h, self._h, data if data.size else None, off, n, n_mm, seedlen, maxtotal, trim5, trim3, max_loci, bool(norc))
         if strata:
-            _check(lib.mirge_genome_align_loci_strata(*head, C.c_int32(1), _p(totals), C.byref(h)), "mirge_genome_align_loci_strata")
+            _check(lib.mirge_genome_align_loci_strata(*head, 1, totals, C.byref(h)), "mirge_genome_align_loci_strata")
         else:
-            _check(lib.mirge_genome_align_loci(*head, _p(totals), C.byref(h)), "mirge_genome_align_loci")
+            _check(lib.mirge_genome_align_loci(*head, totals, C.byref(h)), "mirge_genome_align_loci")
         try:
-            m = int(lib.mirge_loci_count(h))
+            m = lib.mirge_loci_count(h)
             out = dict(query=np.zeros(m, np.uint32), ref=np.zeros(m, np.uint32), off=np.zeros(m, np.uint64),
                        strand=np.zeros(m, np.uint8), mm=np.zeros(m, np.uint8))
             if m:
-                _check(lib.mirge_loci_fetch(h, *(_p(out[k]) for k in ("query", "ref", "off", "strand", "mm"))), "mirge_loci_fetch")
+                _check(lib.mirge_loci_fetch(h, *(out[k] for k in ("query", "ref", "off", "strand", "mm"))), "mirge_loci_fetch")
         finally:
             lib.mirge_loci_destroy(h)
         out["totals"] = totals[:n]
@@ -487,8 +635,7 @@ class DeviceGenome:
         off = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(length, out=off[1:])
         out = np.zeros(max(int(off[n]), 1), dtype=np.uint8)
-        _check(load().mirge_genome_fetch(self.ctx._h, self._h, C.c_int64(n), _p(ref), _p(start), _p(length), _p(minus), _p(rna), _p(off),
-                                         _p(out)), "mirge_genome_fetch")
+        _check(load().mirge_genome_fetch(self.ctx._h, self._h, n, ref, start, length, minus, rna, off, out), "mirge_genome_fetch")
         text = out.tobytes().decode("ascii")
         return [text[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
 
@@ -517,8 +664,7 @@ class DeviceReads:
         data = np.ascontiguousarray(reads.data, dtype=np.uint8)
         off = np.ascontiguousarray(reads.offsets, dtype=np.int64)
         h = C.c_void_p()
-        _check(load().mirge_reads_pack(ctx._h, _p(data), _p(off), C.c_int64(len(reads)), C.byref(h)),
-               "mirge_reads_pack")
+        _check(load().mirge_reads_pack(ctx._h, data, off, len(reads), C.byref(h)), "mirge_reads_pack")
         return DeviceReads(ctx, h)
 
     @staticmethod
@@ -530,9 +676,8 @@ class DeviceReads:
             np.ascontiguousarray(text, dtype=np.uint8)
         h = C.c_void_p()
         nrec = C.c_int64()
-        _check(load().mirge_reads_parse_trim(ctx._h, _p(buf) if buf.size else C.c_void_p(0), C.c_int64(buf.size), C.c_int32(fmt),
-                                             C.c_int32(min_len), C.byref(trim) if trim is not None else C.c_void_p(0),
-                                             C.byref(h), C.byref(nrec)), "mirge_reads_parse")
+        _check(load().mirge_reads_parse_trim(ctx._h, buf if buf.size else None, buf.size, fmt, min_len, trim, C.byref(h), C.byref(nrec)),
+               "mirge_reads_parse")
         return DeviceReads(ctx, h), int(nrec.value)
 
     @staticmethod
@@ -544,9 +689,8 @@ class DeviceReads:
             np.ascontiguousarray(text, dtype=np.uint8)
         h, ht = C.c_void_p(), C.c_void_p()
         nrec = C.c_int64()
-        _check(load().mirge_reads_parse_umi(ctx._h, _p(buf) if buf.size else C.c_void_p(0), C.c_int64(buf.size), C.c_int32(fmt),
-                                            C.c_int32(min_len), C.byref(trim) if trim is not None else C.c_void_p(0),
-                                            C.byref(umi), C.byref(h), C.byref(nrec), C.byref(ht)), "mirge_reads_parse_umi")
+        _check(load().mirge_reads_parse_umi(ctx._h, buf if buf.size else None, buf.size, fmt, min_len, trim, umi, C.byref(h), C.byref(nrec),
+                                            C.byref(ht)), "mirge_reads_parse_umi")
         return DeviceReads(ctx, h), int(nrec.value), (DeviceReads(ctx, ht) if ht.value else None)
 
     @staticmethod
@@ -554,7 +698,7 @@ class DeviceReads:
         """Raw read sets appended in the order given (one per sample, before the joint collapse)."""
         arr = (C.c_void_p * len(parts))(*[p._h for p in parts])
         h = C.c_void_p()
-        _check(load().mirge_reads_concat(ctx._h, arr, C.c_int32(len(parts)), C.byref(h)), "mirge_reads_concat")
+        _check(load().mirge_reads_concat(ctx._h, arr, len(parts), C.byref(h)), "mirge_reads_concat")
         return DeviceReads(ctx, h)
 
     def __len__(self) -> int:
@@ -567,7 +711,7 @@ class DeviceReads:
     def group_counts(self) -> np.ndarray:
         """reads per storage group: width classes (up to 31, 64, 128, 255 nt, longer) without an ambiguous call, then the same with an N"""
         out = np.zeros(16, dtype=np.int64)
-        n = load().mirge_reads_group_counts(self._h, _p(out), C.c_int32(16))
+        n = load().mirge_reads_group_counts(self._h, out, 16)
         return out[:n]
 
     @property
@@ -581,14 +725,14 @@ class DeviceReads:
         union, one count column per part, all on the device."""
         arr = (C.c_void_p * len(parts))(*[p._h for p in parts])
         h, nu = C.c_void_p(), C.c_int64()
-        _check(load().mirge_collapse_merge(ctx._h, arr, C.c_int32(len(parts)), C.byref(h), C.byref(nu)), "mirge_collapse_merge")
+        _check(load().mirge_collapse_merge(ctx._h, arr, len(parts), C.byref(h), C.byref(nu)), "mirge_collapse_merge")
         return DeviceReads(ctx, h)
 
     def unpack(self) -> FlatSeqs:
         n = len(self)
         off = np.zeros(n + 1, dtype=np.int64)
         data = np.empty(max(load().mirge_reads_total_bases(self._h), 1), dtype=np.uint8)
-        _check(load().mirge_reads_unpack(self.ctx._h, self._h, _p(data), _p(off)), "mirge_reads_unpack")
+        _check(load().mirge_reads_unpack(self.ctx._h, self._h, data, off), "mirge_reads_unpack")
         return FlatSeqs(data[:off[-1]].copy(), off)
 
     def collapse(self, sample_ids: Optional[np.ndarray] = None, n_samples: int = 1,
@@ -598,14 +742,12 @@ class DeviceReads:
         h = C.c_void_p()
         nu = C.c_int64()
         if weights is None:
-            _check(load().mirge_collapse(self.ctx._h, self._h, _p(sid), C.c_int32(n_samples), C.byref(h),
-                                         C.byref(nu)), "mirge_collapse")
+            _check(load().mirge_collapse(self.ctx._h, self._h, sid, n_samples, C.byref(h), C.byref(nu)), "mirge_collapse")
         else:
             w = np.ascontiguousarray(weights, dtype=np.uint32)
             if w.shape[0] != len(self):
                 raise ValueError("one weight per read")
-            _check(load().mirge_collapse_weighted(self.ctx._h, self._h, _p(sid), C.c_int32(n_samples), _p(w), C.byref(h),
-                                                  C.byref(nu)), "mirge_collapse_weighted")
+            _check(load().mirge_collapse_weighted(self.ctx._h, self._h, sid, n_samples, w, C.byref(h), C.byref(nu)), "mirge_collapse_weighted")
         return DeviceReads(self.ctx, h)
 
     def counts(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -613,7 +755,7 @@ class DeviceReads:
         n, S = len(self), self.n_samples
         cnt = np.zeros((n, max(S, 1)), dtype=np.uint32)
         first = np.zeros(n, dtype=np.int64)
-        _check(load().mirge_collapse_fetch(self.ctx._h, self._h, _p(cnt), _p(first)), "mirge_collapse_fetch")
+        _check(load().mirge_collapse_fetch(self.ctx._h, self._h, cnt, first), "mirge_collapse_fetch")
         return cnt, first
 
     def umi_cluster(self, front: int, back: int) -> np.ndarray:
@@ -622,7 +764,7 @@ class DeviceReads:
         n = len(self)
         out = np.zeros(max(n, 1), dtype=np.uint8)
         nf = C.c_int64()
-        _check(load().mirge_umi_cluster(self.ctx._h, self._h, C.c_int32(int(front)), C.c_int32(int(back)), _p(out), C.byref(nf)), "mirge_umi_cluster")
+        _check(load().mirge_umi_cluster(self.ctx._h, self._h, front, back, out, C.byref(nf)), "mirge_umi_cluster")
         out = out[:n]
         if int(out.sum()) != nf.value:
             raise RuntimeError("mirge_umi_cluster: the founder count and the flags differ")
@@ -639,28 +781,28 @@ class DeviceReads:
         h = C.c_void_p()
         if not -2 ** 31 <= int(ratio) < 2 ** 31:
             raise RuntimeError("mirge_kmer_correct_ratio: the ratio is 0 (none) or 2 .. 2^31 - 1")
-        _check(load().mirge_kmer_correct_ratio(self.ctx._h, self._h, C.c_int32(int(k_start)), C.c_int32(int(k_end)), C.c_int32(int(threshold)),
-                                               C.c_int32(int(ratio)), C.byref(h), _p(final_of), _p(mask)), "mirge_kmer_correct_ratio")
+        _check(load().mirge_kmer_correct_ratio(self.ctx._h, self._h, k_start, k_end, threshold, ratio, C.byref(h), final_of, mask),
+               "mirge_kmer_correct_ratio")
         return DeviceReads(self.ctx, h), final_of[:n], mask[:n]
 
     def first_appearance_order(self) -> np.ndarray:
         """Indices of the unique reads in the order their first copy appeared in the raw reads (``mirge_collapse_order``)."""
         order = np.zeros(len(self), dtype=np.int64)
-        _check(load().mirge_collapse_order(self.ctx._h, self._h, _p(order)), "mirge_collapse_order")
+        _check(load().mirge_collapse_order(self.ctx._h, self._h, order), "mirge_collapse_order")
         return order
 
     def sorted_order(self) -> np.ndarray:
         """Indices of the unique reads in the order of the sorted sequences (Python string order: the index of the reference's
         outer-joined sample matrix, digest.py:243), from a radix sort on the device (``mirge_collapse_order_sorted``)."""
         order = np.zeros(len(self), dtype=np.int64)
-        _check(load().mirge_collapse_order_sorted(self.ctx._h, self._h, _p(order)), "mirge_collapse_order_sorted")
+        _check(load().mirge_collapse_order_sorted(self.ctx._h, self._h, order), "mirge_collapse_order_sorted")
         return order
 
     def range_sample(self, k: int = 256) -> np.ndarray:
         """k evenly spaced quantiles of the dictionary's first-word sort keys (``mirge_reads_range_sample``): what a rank puts
         into the pool the sharded run's range splitters are chosen from (``multigpu.choose_splitters``)"""
-        out = np.zeros(int(k), dtype=np.uint64)
-        _check(load().mirge_reads_range_sample(self.ctx._h, self._h, C.c_int32(int(k)), _p(out)), "mirge_reads_range_sample")
+        out = np.zeros(k, dtype=np.uint64)
+        _check(load().mirge_reads_range_sample(self.ctx._h, self._h, k, out), "mirge_reads_range_sample")
         return out
 
     def range_split(self, splitters: np.ndarray):
@@ -673,20 +815,19 @@ class DeviceReads:
         data = np.empty(max(load().mirge_reads_total_bases(self._h), 1), dtype=np.uint8)
         cnt = np.zeros((n, S), dtype=np.uint32)
         bounds = np.zeros(n_parts + 1, dtype=np.int64)
-        _check(load().mirge_reads_range_split(self.ctx._h, self._h, _p(sp) if sp.size else C.c_void_p(0), C.c_int32(n_parts), _p(data),
-                                              _p(off), _p(cnt) if cnt.size else C.c_void_p(0), _p(bounds)), "mirge_reads_range_split")
+        _check(load().mirge_reads_range_split(self.ctx._h, self._h, sp if sp.size else None, n_parts, data, off, cnt if cnt.size else None,
+                                              bounds), "mirge_reads_range_split")
         return FlatSeqs(data[:off[-1]], off), cnt, bounds
 
     def nonzero_per_sample(self) -> np.ndarray:
         """unique reads with a count, per sample column (``mirge_collapse_nonzero``)"""
         out = np.zeros(max(self.n_samples, 1), dtype=np.int64)
-        _check(load().mirge_collapse_nonzero(self.ctx._h, self._h, _p(out)), "mirge_collapse_nonzero")
+        _check(load().mirge_collapse_nonzero(self.ctx._h, self._h, out), "mirge_collapse_nonzero")
         return out
 
     def set_counts(self, counts: np.ndarray):
         counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(len(self), -1)
-        _check(load().mirge_reads_set_counts(self.ctx._h, self._h, _p(counts), C.c_int32(counts.shape[1])),
-               "mirge_reads_set_counts")
+        _check(load().mirge_reads_set_counts(self.ctx._h, self._h, counts, counts.shape[1]), "mirge_reads_set_counts")
 
     def close(self):
         if self._h:
@@ -703,7 +844,7 @@ class DeviceReads:
 def umi_cluster_stats() -> dict:
     """``mirge_umi_cluster_stats``: what this thread's last directional clustering saw"""
     out = np.zeros(5, dtype=np.int64)
-    _check(load().mirge_umi_cluster_stats(_p(out)), "mirge_umi_cluster_stats")
+    _check(load().mirge_umi_cluster_stats(out), "mirge_umi_cluster_stats")
     return dict(zip(("tagged", "eligible", "linked", "rounds", "slots"), (int(x) for x in out)))
 
 
@@ -713,8 +854,7 @@ KMER_CORRECT_TALLIES = ("eligible", "suspect", "corrected", "uncorrectable", "un
 def kmer_correct_stats() -> list:
     """``mirge_kmer_correct_stats``: one dict per round of this thread's last ``mirge_kmer_correct``"""
     out = np.zeros(8 * 24, dtype=np.int64)
-    load().mirge_kmer_correct_stats.restype = C.c_int
-    rounds = load().mirge_kmer_correct_stats(_p(out))
+    rounds = load().mirge_kmer_correct_stats(out)
     if rounds < 0:
         _check(rounds, "mirge_kmer_correct_stats")
     return [dict(zip(KMER_CORRECT_TALLIES, (int(x) for x in out[8 * r:8 * r + 8]))) for r in range(rounds)]
@@ -724,8 +864,7 @@ def kmer_correct_ratio_stats() -> list:
     """``mirge_kmer_correct_ratio_stats``: per round of this thread's last ``kmer_correct`` a dict ``above`` (distinct k-mers with a sum
     above the threshold) and ``dominated`` (those of them a neighbouring k-mer dominates); zeros when that call had no ratio"""
     out = np.zeros(2 * 24, dtype=np.int64)
-    load().mirge_kmer_correct_ratio_stats.restype = C.c_int
-    rounds = load().mirge_kmer_correct_ratio_stats(_p(out))
+    rounds = load().mirge_kmer_correct_ratio_stats(out)
     if rounds < 0:
         _check(rounds, "mirge_kmer_correct_ratio_stats")
     return [{"above": int(out[2 * r]), "dominated": int(out[2 * r + 1])} for r in range(rounds)]
@@ -745,8 +884,7 @@ class CascadeResult:
         ref = np.empty(n, dtype=np.int32)
         off = np.empty(n, dtype=np.int32)
         mm = np.empty(n, dtype=np.int8)
-        _check(load().mirge_result_fetch(self.ctx._h, self._h, _p(ps), _p(ref), _p(off), _p(mm)),
-               "mirge_result_fetch")
+        _check(load().mirge_result_fetch(self.ctx._h, self._h, ps, ref, off, mm), "mirge_result_fetch")
         return ps, ref, off, mm
 
     def close(self):
@@ -767,7 +905,7 @@ def cascade_args(libs: Sequence[Optional[DeviceLibrary]], policies: Sequence[Mir
     n_pass = len(policies)
     arr = (C.c_void_p * n_pass)(*[(lb._h if lb is not None else C.c_void_p(0)) for lb in libs])
     pol = (MirgePolicy * n_pass)(*policies)
-    return arr, pol, C.c_int32(n_pass)
+    return arr, pol, n_pass
 
 
 def cascade_run(ctx: Context, reads: DeviceReads, libs: Sequence[Optional[DeviceLibrary]],
@@ -775,7 +913,7 @@ def cascade_run(ctx: Context, reads: DeviceReads, libs: Sequence[Optional[Device
     arr, pol, n_pass = prepared if prepared is not None else cascade_args(libs, policies)
     h = C.c_void_p()
     _check(load().mirge_cascade_run(ctx._h, reads._h, arr, pol, n_pass, C.byref(h)), "mirge_cascade_run")
-    return CascadeResult(ctx, h, reads, n_pass.value)
+    return CascadeResult(ctx, h, reads, n_pass)
 
 
 def cascade_prepare(ctx: Context, reads: DeviceReads, libs: Sequence[Optional[DeviceLibrary]],
@@ -800,7 +938,7 @@ def cascade_wg_times(ctx: "Context"):
     if g.value <= 0:
         return None
     t = np.zeros(g.value, dtype=np.uint32)
-    _check(load().mirge_cascade_wg_times(ctx._h, _p(t), C.c_int32(g.value), C.byref(g), C.byref(khz)), "mirge_cascade_wg_times")
+    _check(load().mirge_cascade_wg_times(ctx._h, t, g.value, C.byref(g), C.byref(khz)), "mirge_cascade_wg_times")
     return t.astype(np.float64) / max(khz.value, 1)
 
 
@@ -813,7 +951,7 @@ def collapse_cascade(ctx: Context, raw: DeviceReads, libs: Sequence[Optional[Dev
     _check(load().mirge_collapse_cascade(ctx._h, raw._h, arr, pol, n_pass, C.byref(hu), C.byref(nu), C.byref(hr)),
            "mirge_collapse_cascade")
     uniq = DeviceReads(ctx, hu)
-    return uniq, CascadeResult(ctx, hr, uniq, n_pass.value)
+    return uniq, CascadeResult(ctx, hr, uniq, n_pass)
 
 
 def count_join(ctx: Context, uniq: DeviceReads, res: CascadeResult, exact_pass: int, iso_pass: int,
@@ -823,8 +961,7 @@ def count_join(ctx: Context, uniq: DeviceReads, res: CascadeResult, exact_pass: 
     cls = np.zeros((res.n_pass, S), dtype=np.int64)
     ex = np.zeros((max(n_mirna, 1), S), dtype=np.int64)
     iso = np.zeros((max(n_mirna, 1), S), dtype=np.int64)
-    _check(load().mirge_count_join(ctx._h, uniq._h, res._h, C.c_int32(exact_pass), C.c_int32(iso_pass),
-                                   C.c_int64(n_mirna), _p(cls), _p(ex), _p(iso)), "mirge_count_join")
+    _check(load().mirge_count_join(ctx._h, uniq._h, res._h, exact_pass, iso_pass, n_mirna, cls, ex, iso), "mirge_count_join")
     return cls, ex[:n_mirna], iso[:n_mirna]
 
 
@@ -838,9 +975,8 @@ def count_join_host(ctx: Context, ps: np.ndarray, ref: np.ndarray, counts: np.nd
     cls = np.zeros((n_pass, S), dtype=np.int64)
     ex = np.zeros((max(n_mirna, 1), S), dtype=np.int64)
     iso = np.zeros((max(n_mirna, 1), S), dtype=np.int64)
-    _check(load().mirge_count_join_host(ctx._h, _p(ps), _p(ref), _p(counts), C.c_int64(ps.shape[0]), C.c_int32(S),
-                                        C.c_int32(n_pass), C.c_int32(exact_pass), C.c_int32(iso_pass),
-                                        C.c_int64(n_mirna), _p(cls), _p(ex), _p(iso)), "mirge_count_join_host")
+    _check(load().mirge_count_join_host(ctx._h, ps, ref, counts, ps.shape[0], S, n_pass, exact_pass, iso_pass, n_mirna, cls, ex, iso),
+           "mirge_count_join_host")
     return cls, ex[:n_mirna], iso[:n_mirna]
 
 
@@ -868,10 +1004,9 @@ def variant_tally(ctx: Context, uniq: DeviceReads, res: CascadeResult, exact_pas
     state = np.empty(max(n, 1), dtype=np.int8) if per_read else None
     if n_fam == 0:
         tabs = np.zeros((5, 0, S), dtype=np.int64)
-    _check(load().mirge_variant_tally(ctx._h, uniq._h, res._h, C.c_int32(exact_pass), C.c_int32(iso_pass), _p(fam_of_ref),
-                                      C.c_int64(fam_of_ref.shape[0]), _p(tdata) if tdata.size else C.c_void_p(0), _p(toff),
-                                      C.c_int64(n_fam), _p(ret), _p(freq), _p(tabs) if n_fam else _p(np.zeros(1, np.int64)),
-                                      _p(cen), _p(diag), _p(state)), "mirge_variant_tally")
+    _check(load().mirge_variant_tally(ctx._h, uniq._h, res._h, exact_pass, iso_pass, fam_of_ref, fam_of_ref.shape[0],
+                                      tdata if tdata.size else None, toff, n_fam, ret, freq, tabs if n_fam else np.zeros(1, np.int64),
+                                      cen, diag, state), "mirge_variant_tally")
     out = dict(zip(("n_seqs", "seq_true", "count_true", "canon", "kept_exact"), tabs[:, :n_fam]))
     out["census"] = cen[:n_fam]
     if per_read:
@@ -884,30 +1019,16 @@ def annotation_csv(mapped_path, unmapped_path, header: str, seqs: FlatSeqs, ps: 
                    names_by_pass: Sequence[Optional[FlatSeqs]]):
     """``mapped.csv`` / ``unmapped.csv`` (mirge/__main__.py:164-173) from flat arrays; ``names_by_pass[p]`` = the
     reference names of pass p's library as a FlatSeqs (None: the pass has none)."""
-    n_pass = len(col_of_pass)
+    n_pass, col, nd, no, nn, keep = _name_tables(col_of_pass, names_by_pass)
     data = np.ascontiguousarray(seqs.data, dtype=np.uint8)
     off = np.ascontiguousarray(seqs.offsets, dtype=np.int64)
     ps = np.ascontiguousarray(ps, dtype=np.int8)
     ref = np.ascontiguousarray(ref, dtype=np.int32)
     counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(ps.shape[0], -1)
     rows = np.ascontiguousarray(rows, dtype=np.int64)
-    col = (C.c_int32 * n_pass)(*[int(x) for x in col_of_pass])
-    keep = []
-    nd, no, nn = (C.c_void_p * n_pass)(), (C.c_void_p * n_pass)(), (C.c_int64 * n_pass)()
-    for p in range(n_pass):
-        fs = names_by_pass[p]
-        if fs is None:
-            nd[p], no[p], nn[p] = None, None, 0
-            continue
-        d = np.ascontiguousarray(fs.data, dtype=np.uint8)
-        o = np.ascontiguousarray(fs.offsets, dtype=np.int64)
-        keep += [d, o]
-        nd[p], no[p], nn[p] = d.ctypes.data if d.size else None, o.ctypes.data, len(fs)
     enc = lambda x: None if x is None else str(x).encode()
-    _check(load().mirge_annotation_csv(enc(mapped_path), enc(unmapped_path), header.encode(), _p(data) if data.size else C.c_void_p(0),
-                                       _p(off), _p(ps), _p(ref), _p(counts), C.c_int32(counts.shape[1]), _p(rows),
-                                       C.c_int64(rows.shape[0]), C.c_int32(n_pass), col, C.c_int32(n_name_cols), nd, no, nn),
-           "mirge_annotation_csv")
+    _check(load().mirge_annotation_csv(enc(mapped_path), enc(unmapped_path), header.encode(), data if data.size else None, off, ps, ref, counts,
+                                       counts.shape[1], rows, rows.shape[0], n_pass, col, n_name_cols, nd, no, nn), "mirge_annotation_csv")
 
 
 def _name_tables(col_of_pass, names_by_pass):
@@ -935,8 +1056,8 @@ def annotation_csv_device_sizes(ctx: "Context", uniq: "DeviceReads", res: "Casca
     n_pass, col, nd, no, nn, keep = _name_tables(col_of_pass, names_by_pass)
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     out = np.zeros(2, dtype=np.int64)
-    rc = load().mirge_annotation_csv_device_sizes(ctx._h, uniq._h, res._h, _p(rows) if rows.size else C.c_void_p(0), C.c_int64(rows.shape[0]),
-                                                  C.c_int32(n_pass), col, C.c_int32(n_name_cols), nd, no, nn, _p(out))
+    rc = load().mirge_annotation_csv_device_sizes(ctx._h, uniq._h, res._h, rows if rows.size else None, rows.shape[0], n_pass, col, n_name_cols,
+                                                  nd, no, nn, out)
     if rc == -4:
         return None
     _check(rc, "mirge_annotation_csv_device_sizes")
@@ -949,10 +1070,9 @@ def annotation_csv_device_at(ctx: "Context", uniq: "DeviceReads", res: "CascadeR
     """The listed rows' text at the given byte offsets of the two EXISTING files (``mirge_annotation_csv_device_at``)."""
     n_pass, col, nd, no, nn, keep = _name_tables(col_of_pass, names_by_pass)
     rows = np.ascontiguousarray(rows, dtype=np.int64)
-    _check(load().mirge_annotation_csv_device_at(ctx._h, uniq._h, res._h, str(mapped_path).encode(), str(unmapped_path).encode(),
-                                                 C.c_int64(int(mapped_off)), C.c_int64(int(unmapped_off)),
-                                                 _p(rows) if rows.size else C.c_void_p(0), C.c_int64(rows.shape[0]), C.c_int32(n_pass), col,
-                                                 C.c_int32(n_name_cols), nd, no, nn), "mirge_annotation_csv_device_at")
+    _check(load().mirge_annotation_csv_device_at(ctx._h, uniq._h, res._h, str(mapped_path).encode(), str(unmapped_path).encode(), mapped_off,
+                                                 unmapped_off, rows if rows.size else None, rows.shape[0], n_pass, col, n_name_cols, nd, no, nn),
+           "mirge_annotation_csv_device_at")
 
 
 def annotation_csv_device(ctx: "Context", uniq: "DeviceReads", res: "CascadeResult", mapped_path, unmapped_path, header: str,
@@ -964,8 +1084,7 @@ def annotation_csv_device(ctx: "Context", uniq: "DeviceReads", res: "CascadeResu
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     enc = lambda x: None if x is None else str(x).encode()
     rc = load().mirge_annotation_csv_device(ctx._h, uniq._h, res._h, enc(mapped_path), enc(unmapped_path), header.encode(),
-                                            _p(rows) if rows.size else C.c_void_p(0), C.c_int64(rows.shape[0]), C.c_int32(n_pass),
-                                            col, C.c_int32(n_name_cols), nd, no, nn)
+                                            rows if rows.size else None, rows.shape[0], n_pass, col, n_name_cols, nd, no, nn)
     if rc == -4:
         return False
     _check(rc, "mirge_annotation_csv_device")
@@ -986,10 +1105,9 @@ def loci_cluster(ctx: Context, ref, off, strand, query, qlen, qcount, ref_skip, 
     tab = dict(ref=np.zeros(m, np.uint32), strand=np.zeros(m, np.uint8), start=np.zeros(m, np.uint64), end=np.zeros(m, np.uint64),
                reads=np.zeros(m, np.int64), members=np.zeros(m, np.uint32))
     nc = C.c_int64(0)
-    _check(load().mirge_loci_cluster(ctx._h, C.c_int64(n), _p(ref), _p(off), _p(strand), _p(query), C.c_int64(qlen.shape[0]), _p(qlen),
-                                     _p(qcount), C.c_int64(ref_skip.shape[0]), _p(ref_skip), C.c_int32(threshold),
-                                     C.c_int32(1 if minus_first_only else 0), _p(cluster), C.byref(nc),
-                                     *(_p(tab[k]) for k in ("ref", "strand", "start", "end", "reads", "members"))), "mirge_loci_cluster")
+    _check(load().mirge_loci_cluster(ctx._h, n, ref, off, strand, query, qlen.shape[0], qlen, qcount, ref_skip.shape[0], ref_skip, threshold,
+                                     bool(minus_first_only), cluster, C.byref(nc),
+                                     *(tab[k] for k in ("ref", "strand", "start", "end", "reads", "members"))), "mirge_loci_cluster")
     out = {k: v[:nc.value] for k, v in tab.items()}
     out["cluster"] = cluster[:n]
     return out
@@ -1010,16 +1128,15 @@ def trf_hits(ctx: Context, uniq: DeviceReads, res: CascadeResult, mature_pass: i
     if anticodon.shape[0] != mature_lib.n_refs:
         raise ValueError("one anticodon start per mature reference")
     h = C.c_void_p()
-    _check(lib.mirge_trf_hits_run(ctx._h, uniq._h, res._h, C.c_int32(mature_pass), mature_lib._h, C.byref(mature_pol),
-                                  C.c_int32(primary_pass), primary_lib._h, C.byref(primary_pol),
-                                  _p(rows) if rows.size else C.c_void_p(0), C.c_int64(rows.shape[0]),
-                                  _p(anticodon) if anticodon.size else C.c_void_p(0), C.byref(h)), "mirge_trf_hits_run")
+    _check(lib.mirge_trf_hits_run(ctx._h, uniq._h, res._h, mature_pass, mature_lib._h, mature_pol, primary_pass, primary_lib._h, primary_pol,
+                                  rows if rows.size else None, rows.shape[0], anticodon if anticodon.size else None, C.byref(h)),
+           "mirge_trf_hits_run")
     try:
-        m = int(lib.mirge_trf_hits_count(h))
+        m = lib.mirge_trf_hits_count(h)
         out = dict(row=np.zeros(m, np.uint32), ref=np.zeros(m, np.uint32), off=np.zeros(m, np.int32), mm=np.zeros(m, np.uint8),
                    cls=np.zeros(m, np.uint8), type=np.zeros(m, np.uint8))
         if m:
-            _check(lib.mirge_trf_hits_fetch(h, *(_p(out[k]) for k in ("row", "ref", "off", "mm", "cls", "type"))), "mirge_trf_hits_fetch")
+            _check(lib.mirge_trf_hits_fetch(h, *(out[k] for k in ("row", "ref", "off", "mm", "cls", "type"))), "mirge_trf_hits_fetch")
     finally:
         lib.mirge_trf_hits_destroy(h)
     return out
@@ -1038,9 +1155,8 @@ def trf_assign(ctx: Context, uniq: DeviceReads, res: CascadeResult, read, tref, 
     np.cumsum([len(s) for s in strings], out=str_off[1:])
     blob = np.frombuffer(b"".join(strings) or b"\0", dtype=np.uint8)
     dist, trf = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-    _check(load().mirge_trf_assign(ctx._h, uniq._h, res._h, C.c_int64(n), _p(read), _p(tref), _p(start), C.c_int64(max(ref_ptr.shape[0] - 1, 0)),
-                                   _p(ref_ptr), C.c_int64(n_trf), _p(str_off), _p(blob), _p(c_start), _p(c_end), _p(rank), _p(dist),
-                                   _p(trf)), "mirge_trf_assign")
+    _check(load().mirge_trf_assign(ctx._h, uniq._h, res._h, n, read, tref, start, max(ref_ptr.shape[0] - 1, 0), ref_ptr, n_trf, str_off, blob,
+                                   c_start, c_end, rank, dist, trf), "mirge_trf_assign")
     return dist[:n], trf[:n]
 
 
@@ -1071,9 +1187,8 @@ def trf_cluster(ctx: Context, uniq: DeviceReads, grp_ptr, read, off, rp100k, tle
     for k in ("nneigh", "order", "cl", "halo", "centre"):
         out[k] = np.zeros(max(n, 1), np.int32)
     out["nclust"] = np.zeros(max(n_grp, 1), np.int32)
-    _check(load().mirge_trf_cluster(ctx._h, uniq._h, C.c_int64(n_grp), _p(grp_ptr), _p(read), _p(off), _p(rp100k), _p(tlen),
-                                    C.c_int64(gauss.shape[0]), _p(gauss), *(_p(out[k]) for k in ("rho", "delta", "nneigh", "order", "cl", "halo",
-                                                                                                 "nclust", "centre"))), "mirge_trf_cluster")
+    _check(load().mirge_trf_cluster(ctx._h, uniq._h, n_grp, grp_ptr, read, off, rp100k, tlen, gauss.shape[0], gauss,
+                                    *(out[k] for k in ("rho", "delta", "nneigh", "order", "cl", "halo", "nclust", "centre"))), "mirge_trf_cluster")
     return {k: (a[:n_grp] if k == "nclust" else a[:n]) for k, a in out.items()}
 
 
@@ -1082,7 +1197,7 @@ def trf_row_counts(ctx: Context, uniq: DeviceReads, rows) -> np.ndarray:
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     out = np.zeros((rows.shape[0], max(uniq.n_samples, 1)), dtype=np.uint32)
     if rows.size:
-        _check(load().mirge_trf_row_counts(ctx._h, uniq._h, _p(rows), C.c_int64(rows.shape[0]), _p(out)), "mirge_trf_row_counts")
+        _check(load().mirge_trf_row_counts(ctx._h, uniq._h, rows, rows.shape[0], out), "mirge_trf_row_counts")
     return out
 
 
@@ -1091,7 +1206,7 @@ def bam_huffman_probe(ctx: Context, counts, max_bits: int) -> np.ndarray:
     under the limit ``max_bits``"""
     counts = np.ascontiguousarray(counts, dtype=np.uint32)
     out = np.zeros(max(counts.shape[0], 1), dtype=np.uint8)
-    _check(load().mirge_bam_huffman_probe(ctx._h, _p(counts), C.c_int32(counts.shape[0]), C.c_int32(max_bits), _p(out)), "mirge_bam_huffman_probe")
+    _check(load().mirge_bam_huffman_probe(ctx._h, counts, counts.shape[0], max_bits, out), "mirge_bam_huffman_probe")
     return out[:counts.shape[0]]
 
 
@@ -1109,9 +1224,8 @@ def cluster_diagonals(ctx: Context, reads: FlatSeqs, clusters: FlatSeqs, row_clu
     out = dict(diag=np.zeros(m, np.int32), score=np.zeros(m, np.int32), identity=np.zeros(m, np.int32), flag=np.zeros(m, np.uint8))
     rd, ro = np.ascontiguousarray(reads.data, dtype=np.uint8), np.ascontiguousarray(reads.offsets, dtype=np.int64)
     cd, co = np.ascontiguousarray(clusters.data, dtype=np.uint8), np.ascontiguousarray(clusters.offsets, dtype=np.int64)
-    _check(load().mirge_cluster_diagonals(ctx._h, _p(rd) if rd.size else C.c_void_p(0), _p(ro), C.c_int64(n),
-                                          _p(cd) if cd.size else C.c_void_p(0), _p(co), C.c_int64(len(clusters)), _p(row_cluster),
-                                          *(_p(out[k]) for k in ("diag", "score", "identity", "flag"))), "mirge_cluster_diagonals")
+    _check(load().mirge_cluster_diagonals(ctx._h, rd if rd.size else None, ro, n, cd if cd.size else None, co, len(clusters), row_cluster,
+                                          *(out[k] for k in ("diag", "score", "identity", "flag"))), "mirge_cluster_diagonals")
     return {k: v[:n] for k, v in out.items()}
 
 
@@ -1134,7 +1248,6 @@ def cluster_pileup(ctx: Context, reads: FlatSeqs, c_len, row_start, diag, count)
     col_off = np.zeros(nc + 1, np.int64)
     tally = np.empty((max(cap, 1), 5), np.int64)
     rd, ro = np.ascontiguousarray(reads.data, dtype=np.uint8), np.ascontiguousarray(reads.offsets, dtype=np.int64)
-    _check(load().mirge_cluster_pileup(ctx._h, _p(rd) if rd.size else C.c_void_p(0), _p(ro), C.c_int64(len(reads)), _p(c_len), _p(row_start),
-                                       C.c_int64(nc), _p(diag), _p(count), _p(head), _p(tail), _p(col_off), _p(tally), C.c_int64(cap)),
-           "mirge_cluster_pileup")
+    _check(load().mirge_cluster_pileup(ctx._h, rd if rd.size else None, ro, len(reads), c_len, row_start, nc, diag, count, head, tail, col_off,
+                                       tally, cap), "mirge_cluster_pileup")
     return dict(head=head[:nc], tail=tail[:nc], col_off=col_off, tally=tally[:int(col_off[nc])])

@@ -211,9 +211,8 @@ def write_sample(casc, uniq, res, order: np.ndarray, sample: int, bam_path, bai_
     flat, off = refid_tables(casc, organism, refs)
     n_rec, n_stream, n_file = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     _ffi._check(_ffi.load().mirge_bam_write_device(
-        casc.ctx._h, uniq._h, res._h, _ffi._p(order) if order.size else C.c_void_p(0), C.c_int32(sample), _ffi._p(classes),
-        C.c_int32(classes.size), arr, C.c_int32(casc.n_pass), _ffi._p(flat), _ffi._p(off), C.c_int32(len(refs)), str(bam_path).encode(),
-        str(bai_path).encode(), blob, C.c_int64(len(blob)), C.c_int32(threads if threads else _ffi.gz_threads()), C.byref(n_rec),
+        casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, flat, off, len(refs),
+        str(bam_path).encode(), str(bai_path).encode(), blob, len(blob), threads if threads else _ffi.gz_threads(), C.byref(n_rec),
         C.byref(n_stream), C.byref(n_file)), "mirge_bam_write_device")
     return int(n_rec.value), int(n_stream.value), int(n_file.value)
 

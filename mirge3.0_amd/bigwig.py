@@ -50,7 +50,6 @@ device); the device route is ``csrc/kernels_bw.hpp`` + ``csrc/native_bw.hpp`` wi
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import struct
 import time
@@ -347,11 +346,9 @@ def from_intervals(ctx, intervals: Dict[str, np.ndarray], names: Sequence[str], 
     ln = np.ascontiguousarray(np.asarray(sizes, dtype=np.int64))
     nm_data, nm_off = _name_arrays(names)
     st, err = np.zeros(32, dtype=np.int64), np.zeros(4, dtype=np.int64)
-    p = (lambda a: _ffi._p(a)) if n else (lambda a: C.c_void_p(0))
     rc = _ffi.load().mirge_bigwig_from_intervals(
-        ctx._h, C.c_int64(n), p(iv["rank"]), p(iv["start"]), p(iv["len"]), p(iv["weight"]), p(iv["minus"]), C.c_int32(1 if stranded else 0),
-        C.c_int32(len(names)), _ffi._p(nm_data), _ffi._p(nm_off), _ffi._p(ln), _ffi._p(cid), paths[0].encode(),
-        paths[1].encode() if stranded else None, _ffi._p(st), _ffi._p(err))
+        ctx._h, n, *((iv[k] if n else None) for k in ("rank", "start", "len", "weight", "minus")), bool(stranded), len(names), nm_data, nm_off,
+        ln, cid, paths[0].encode(), paths[1].encode() if stranded else None, st, err)
     _raise(rc, err, names, "mirge_bigwig_from_intervals")
     return _stats(st, len(paths))
 
@@ -381,10 +378,8 @@ def write_sample(casc, uniq, res, order: np.ndarray, sample: int, paths: Sequenc
     nm_data, nm_off = _name_arrays(names)
     st, err = np.zeros(32, dtype=np.int64), np.zeros(4, dtype=np.int64)
     rc = _ffi.load().mirge_bigwig_write_device(
-        casc.ctx._h, uniq._h, res._h, _ffi._p(order) if order.size else C.c_void_p(0), C.c_int32(sample), _ffi._p(classes),
-        C.c_int32(classes.size), arr, C.c_int32(casc.n_pass), _ffi._p(flat), _ffi._p(off), C.c_int32(len(names)), _ffi._p(nm_data),
-        _ffi._p(nm_off), _ffi._p(ln), _ffi._p(cid), C.c_int32(1 if stranded else 0), paths[0].encode(),
-        paths[1].encode() if stranded else None, _ffi._p(st), _ffi._p(err))
+        casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, flat, off, len(names),
+        nm_data, nm_off, ln, cid, bool(stranded), paths[0].encode(), paths[1].encode() if stranded else None, st, err)
     if rc != 0 and int(err[0]) == 2:
         read = uniq.unpack().to_list()[int(err[1])]
         raise ValueError(f"--coverage-bigwig: read {read} on reference {coverage._reference_name(casc, int(err[2]), int(err[3]))} lies "

@@ -126,11 +126,9 @@ def runs_device(ctx, intervals: Dict[str, np.ndarray], stranded: bool) -> Dict[s
     out = dict(strand=np.zeros(cap, np.uint8), chrom=np.zeros(cap, np.int32), start=np.zeros(cap, np.int64), end=np.zeros(cap, np.int64),
                depth=np.zeros(cap, np.int64))
     n_runs = C.c_int64(0)
-    p = (lambda a: _ffi._p(a)) if n else (lambda a: C.c_void_p(0))
     _ffi._check(_ffi.load().mirge_coverage_runs(
-        ctx._h, C.c_int64(n), p(iv["rank"]), p(iv["start"]), p(iv["len"]), p(iv["weight"]), p(iv["minus"]), C.c_int32(1 if stranded else 0),
-        _ffi._p(out["strand"]), _ffi._p(out["chrom"]), _ffi._p(out["start"]), _ffi._p(out["end"]), _ffi._p(out["depth"]), C.byref(n_runs)),
-        "mirge_coverage_runs")
+        ctx._h, n, *((iv[k] if n else None) for k in ("rank", "start", "len", "weight", "minus")), bool(stranded),
+        out["strand"], out["chrom"], out["start"], out["end"], out["depth"], C.byref(n_runs)), "mirge_coverage_runs")
     return {k: v[:int(n_runs.value)].copy() for k, v in out.items()}
 
 
@@ -199,10 +197,9 @@ def write_sample(casc, uniq, res, order: np.ndarray, sample: int, paths: Sequenc
     outs = [C.c_int64(0) for _ in range(4)]
     err = np.zeros(4, dtype=np.int64)
     rc = _ffi.load().mirge_coverage_write_device(
-        casc.ctx._h, uniq._h, res._h, _ffi._p(order) if order.size else C.c_void_p(0), C.c_int32(sample), _ffi._p(classes),
-        C.c_int32(classes.size), arr, C.c_int32(casc.n_pass), _ffi._p(flat), _ffi._p(off), C.c_int32(len(names)), _ffi._p(nm_data),
-        _ffi._p(nm_off), C.c_int32(1 if stranded else 0), paths[0].encode(), paths[1].encode() if stranded else None,
-        C.byref(outs[0]), C.byref(outs[1]), C.byref(outs[2]), C.byref(outs[3]), _ffi._p(err))
+        casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, flat, off, len(names),
+        nm_data, nm_off, bool(stranded), paths[0].encode(), paths[1].encode() if stranded else None,
+        C.byref(outs[0]), C.byref(outs[1]), C.byref(outs[2]), C.byref(outs[3]), err)
     if rc != 0 and int(err[0]) == 2:
         read = uniq.unpack().to_list()[int(err[1])]
         raise ValueError(f"--coverage: read {read} on reference {_reference_name(casc, int(err[2]), int(err[3]))} lies outside "

@@ -137,10 +137,8 @@ def isomir_records(casc: Cascade, uniq, res, tables: dict, rows: np.ndarray) -> 
     mof = np.ascontiguousarray(tables["master_of_ref"], dtype=np.int32)
     pom = np.ascontiguousarray(tables["pre_of_master"], dtype=np.int32) if len(m) else np.zeros(1, np.int32)
     s0 = np.ascontiguousarray(tables["start0"], dtype=np.int32) if len(m) else np.zeros(1, np.int32)
-    _ffi._check(lib.mirge_isomir_type(casc.ctx._h, uniq._h, res._h, C.c_int32(EXACT_PASS), C.c_int32(ISO_PASS), _ffi._p(mof),
-                                      C.c_int64(mof.shape[0]), _ffi._p(mdata), _ffi._p(moff), _ffi._p(pom), _ffi._p(s0),
-                                      C.c_int64(len(m)), _ffi._p(pdata), _ffi._p(poff), C.c_int64(len(p)), _ffi._p(slot),
-                                      C.c_int64(rows.shape[0]), _ffi._p(out)), "mirge_isomir_type")
+    _ffi._check(lib.mirge_isomir_type(casc.ctx._h, uniq._h, res._h, EXACT_PASS, ISO_PASS, mof, mof.shape[0], mdata, moff, pom, s0, len(m),
+                                      pdata, poff, len(p), slot, rows.shape[0], out), "mirge_isomir_type")
     return out[:rows.shape[0]]
 
 
@@ -203,11 +201,9 @@ def write_gff_device_with(tables: dict, path, ref_db, base_names, casc: Cascade,
     order = np.ascontiguousarray(order, dtype=np.int64)
     n_lines = C.c_int64(0)
     _ffi._check(_ffi.load().mirge_gff_write_device(
-        casc.ctx._h, uniq._h, res._h, C.c_int32(EXACT_PASS), C.c_int32(ISO_PASS), _ffi._p(mof), C.c_int64(mof.shape[0]), _ffi._p(mdata),
-        _ffi._p(moff), _ffi._p(pom), _ffi._p(s0), C.c_int64(len(m)), _ffi._p(pdata), _ffi._p(poff), C.c_int64(len(p)), _ffi._p(nof), _ffi._p(nd),
-        _ffi._p(noff), C.c_int64(len(names)), _ffi._p(pof), _ffi._p(pd_), _ffi._p(paroff), C.c_int64(len(parents)),
-        _ffi._p(order) if order.size else C.c_void_p(0), str(path).encode(), head.encode(), version_db.encode(),
-        C.byref(n_lines)), "mirge_gff_write_device")
+        casc.ctx._h, uniq._h, res._h, EXACT_PASS, ISO_PASS, mof, mof.shape[0], mdata, moff, pom, s0, len(m), pdata, poff, len(p), nof, nd,
+        noff, len(names), pof, pd_, paroff, len(parents), order if order.size else None, str(path).encode(), head.encode(),
+        version_db.encode(), C.byref(n_lines)), "mirge_gff_write_device")
     tm["device_call_s"] = time.perf_counter() - t0
     return dict(records=None, rows=None, tables=tables, lines=int(n_lines.value), timing={k: round(v, 4) for k, v in tm.items()})
 
@@ -243,10 +239,9 @@ def write_gff(args, workDir, ref_db, base_names, casc: Cascade, uniq, res, seqs:
     tm["rows_of_the_file_s"] = time.perf_counter() - t0
     t0 = time.perf_counter()
     _ffi._check(_ffi.load().mirge_gff_write(str(Path(workDir) / "sample_miRge3.gff").encode(), head.encode(), version_db.encode(),
-                                            _ffi._p(recs), C.c_int64(rows.shape[0]), _ffi._p(sdata), _ffi._p(soff), _ffi._p(cnt),
-                                            C.c_int32(len(base_names)), _ffi._p(nrow), _ffi._p(nd),
-                                            _ffi._p(np.ascontiguousarray(names.offsets, dtype=np.int64)), C.c_int64(len(names)),
-                                            _ffi._p(prow), _ffi._p(pd_), _ffi._p(np.ascontiguousarray(parents.offsets, dtype=np.int64)),
-                                            C.c_int64(len(parents)), _ffi._p(rows_c), C.c_int64(len(seqs))), "mirge_gff_write")
+                                            recs, rows.shape[0], sdata, soff, cnt, len(base_names), nrow, nd,
+                                            np.ascontiguousarray(names.offsets, dtype=np.int64), len(names), prow, pd_,
+                                            np.ascontiguousarray(parents.offsets, dtype=np.int64), len(parents), rows_c, len(seqs)),
+                "mirge_gff_write")
     tm["write_s"] = time.perf_counter() - t0
     return dict(records=recs, rows=rows, tables=tables, timing={k: round(v, 4) for k, v in tm.items()})

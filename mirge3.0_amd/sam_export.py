@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _ffi
+from ._ffi import SamPass
 from .cascade import PASSES
 from .seqio import FlatSeqs
 
@@ -184,13 +185,6 @@ def host_passes(casc) -> Dict[int, dict]:
     return out
 
 
-class SamPass(C.Structure):
-    """``mirge_sam_pass`` of include/mirge_native.h"""
-    _fields_ = [("lib", C.c_void_p), ("trim5", C.c_int32), ("trim3", C.c_int32), ("n_refs", C.c_int64), ("chrom_of_ref", C.c_void_p),
-                ("minus", C.c_void_p), ("seg_ptr", C.c_void_p), ("seg_s", C.c_void_p), ("seg_e", C.c_void_p), ("cds_lo", C.c_void_p),
-                ("cds_hi", C.c_void_p), ("n_chrom", C.c_int64), ("chrom_data", C.c_void_p), ("chrom_off", C.c_void_p)]
-
-
 def pass_tables(casc, organism: str):
     """(class order, the C array of ``mirge_sam_pass``, the numpy arrays it points into) for a cascade; built once per cascade and
     organism: a human library set holds ~0.2 M header lines"""
@@ -234,9 +228,8 @@ def write_sample(casc, uniq, res, order: np.ndarray, sample: int, path, header: 
         return 0, 0
     n_lines, n_bytes = C.c_int64(0), C.c_int64(0)
     _ffi._check(_ffi.load().mirge_sam_write_device(
-        casc.ctx._h, uniq._h, res._h, _ffi._p(order) if order.size else C.c_void_p(0), C.c_int32(sample), _ffi._p(classes),
-        C.c_int32(classes.size), arr, C.c_int32(casc.n_pass), str(path).encode(), header, C.c_int64(len(header)), C.byref(n_lines),
-        C.byref(n_bytes)), "mirge_sam_write_device")
+        casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, str(path).encode(),
+        header, len(header), C.byref(n_lines), C.byref(n_bytes)), "mirge_sam_write_device")
     return int(n_lines.value), int(n_bytes.value)
 
 

@@ -74,7 +74,7 @@ def test_host_uid_rule_equals_the_restatement_on_every_last_stretch(tmp_path):
     counts = np.arange(1, n + 1, dtype=np.uint32).reshape(n, 1)
     zero = np.zeros(n, dtype=np.int32)
     path = tmp_path / "uid.gff"
-    p = _ffi._p
+    p = lambda a: C.c_void_p(a.ctypes.data)  # hand-wrapped, as an outside caller of _ffi.load() would: passes the binding unchecked
     _ffi._check(_ffi.load().mirge_gff_write(
         str(path).encode(), b"# head\n", b"miRBase22", p(recs), C.c_int64(n), p(np.ascontiguousarray(seqs.data)),
         p(np.ascontiguousarray(seqs.offsets, dtype=np.int64)), p(counts), C.c_int32(1), p(zero), p(np.ascontiguousarray(names.data)),
