@@ -588,6 +588,29 @@ int mirge_bigwig_write_device(mirge_ctx* ctx, const mirge_reads* uniq, const mir
                               const int64_t* rank_name_off, const int64_t* chrom_size, const int32_t* chrom_id, int32_t stranded,
                               const char* path, const char* path_minus, int64_t* stats_out, int64_t* err_out);
 
+/* ---- `--bgzf-out`: the text of `--sam-out` and `--coverage` as BGZF, deflated on the device where it is produced (the format, the
+ * member rule and the `.gzi` layout: mirge3_amd/bgzf.py).  The stream is cut into blocks of block_bytes (64 .. 65280; <= 0:
+ * MIRGE_BGZF_BLOCK_BYTES, default 65280); the file is a function of the stream and the block size alone.  Every file is written as
+ * `<path>.tmp` and renamed when all files of the call are whole; any failure leaves no file.  MIRGE_BGZF_DEFLATE=device (the default) |
+ * host (zlib level 6 on MIRGE_GZ_THREADS threads); any other value fails the call before a file is opened.
+ * stats_out[8] per file: file bytes, members stored, fixed, dynamic, members, stream bytes, 0, 0.
+ * mirge_bgzf_write                  n bytes from the host -> `path` and its index `gzi_path` (MIRGE_BGZF_CHUNK_BYTES: bytes per chunk).
+ * mirge_sam_write_device_bgzf       mirge_sam_write_device's arguments; `path` is the .sam.gz (the header is the front of the stream).
+ * mirge_coverage_write_device_bgzf  mirge_coverage_write_device's arguments; each strand's file is a stream of its own; stats_out[16]. */
+int mirge_bgzf_write(mirge_ctx* ctx, const uint8_t* bytes, int64_t n, int64_t block_bytes, const char* path, const char* gzi_path,
+                     int64_t* stats_out);
+int mirge_sam_write_device_bgzf(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
+                                const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass, const char* path,
+                                const char* header, int64_t header_len, int64_t* n_lines_out, int64_t* n_bytes_out, const char* gzi_path,
+                                int64_t block_bytes, int64_t* stats_out);
+int mirge_coverage_write_device_bgzf(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const int64_t* order, int32_t sample,
+                                     const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                     const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                                     const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
+                                     int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
+                                     int64_t* err_out, const char* gzi_path, const char* gzi_path_minus, int64_t block_bytes,
+                                     int64_t* stats_out);
+
 /* ---- the sequence work behind the tRNA fragment report (the reference's -trf: summary.py:1060-1220, mirge2_tRF_a2i.py:22-62)
  * mirge_trf_hits_run  every best-stratum alignment (bowtie -a --best --strata) of the tRNA reads rows[n_rows] (handle indices of `uniq`;
  *                     a record's row is the index INTO rows).  A read the cascade gave to mature_pass: every forward window of

@@ -125,6 +125,12 @@ int mirge_bigwig_from_intervals(mirge_ctx*, int64_t, const int32_t*, const int64
     const int64_t*, const int64_t*, const int32_t*, const char*, const char*, int64_t*, int64_t*);
 int mirge_bigwig_write_device(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*, int32_t,
     const int32_t*, const int64_t*, int32_t, const char*, const int64_t*, const int64_t*, const int32_t*, int32_t, const char*, const char*, int64_t*, int64_t*);
+int mirge_bgzf_write(mirge_ctx*, const uint8_t*, int64_t, int64_t, const char*, const char*, int64_t*);
+int mirge_sam_write_device_bgzf(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*, int32_t,
+    const char*, const char*, int64_t, int64_t*, int64_t*, const char*, int64_t, int64_t*);
+int mirge_coverage_write_device_bgzf(mirge_ctx*, const mirge_reads*, const mirge_result*, const int64_t*, int32_t, const int32_t*, int32_t, const mirge_sam_pass*,
+    int32_t, const int32_t*, const int64_t*, int32_t, const char*, const int64_t*, int32_t, const char*, const char*, int64_t*, int64_t*, int64_t*, int64_t*, int64_t*,
+    const char*, const char*, int64_t, int64_t*);
 int mirge_trf_hits_run(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, const mirge_lib*, const mirge_policy*, int32_t, const mirge_lib*,
     const mirge_policy*, const int64_t*, int64_t, const int32_t*, mirge_trf_hits**);
 int64_t mirge_trf_hits_count(const mirge_trf_hits*);

@@ -139,6 +139,11 @@ def parse_args(argv=None):
                     help="with --coverage: also write the same runs as bigWig, sections, zoom levels and their deflate computed on the "
                          "device: <sample>.bw, or <sample>.plus.bw and <sample>.minus.bw when stranded; needs --sam-header FILE whose "
                          "@SQ SN:/LN: lines give the chromosome sizes (all of them are listed, in byte order)")
+    ap.add_argument("--bgzf-out", dest="bgzf_out", action="store_true",
+                    help="with --sam-out and/or --coverage: write their text as BGZF, deflated on the device where it is formatted: "
+                         "<sample>.sam.gz and <sample>.bedgraph.gz (or .plus. / .minus.bedgraph.gz) in place of the plain files, each "
+                         "with a block index <name>.gz.gzi; the decompressed bytes are those of the plain file (bigWig and BAM "
+                         "outputs are untouched)")
     ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "tight", "host"),
                     help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
                          "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
@@ -264,6 +269,15 @@ def parse_args(argv=None):
         ap.error("--sorted-bam requires --sam-header FILE with the @SQ SN:/LN: lines of the genome the libraries were built on")
     if args.bam_deflate and not args.sorted_bam:
         ap.error("--bam-deflate requires --sorted-bam")
+    if args.bgzf_out and not (args.sam_out or args.coverage):
+        ap.error("--bgzf-out requires --sam-out or --coverage (it compresses the text those two write)")
+    if args.bgzf_out:
+        from . import bgzf
+        try:
+            bgzf.route()
+            bgzf.block_bytes()
+        except ValueError as e:
+            ap.error(str(e))
     if args.sam_out and (args.save_pkl or args.resume or args.backend == "bowtie"):
         ap.error("--sam-out runs on the device-resident route: not together with -spl / -rr / --backend bowtie")
     if args.trf_clusters:

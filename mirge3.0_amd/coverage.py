@@ -166,9 +166,10 @@ def sq_order(header: Optional[bytes]) -> Optional[List[str]]:
     return [nm for nm, _ in parse_sq(header)]
 
 
-def sample_paths(workDir, name: str, stranded: bool) -> List[Path]:
+def sample_paths(workDir, name: str, stranded: bool, bgzf_out: bool = False) -> List[Path]:
     workDir = Path(workDir)
-    return [workDir / f"{name}.plus.bedgraph", workDir / f"{name}.minus.bedgraph"] if stranded else [workDir / f"{name}.bedgraph"]
+    ext = "bedgraph.gz" if bgzf_out else "bedgraph"
+    return [workDir / f"{name}.plus.{ext}", workDir / f"{name}.minus.{ext}"] if stranded else [workDir / f"{name}.{ext}"]
 
 
 def _reference_name(casc, p: int, r: int) -> str:
@@ -178,14 +179,28 @@ def _reference_name(casc, p: int, r: int) -> str:
 
 
 def write_sample(casc, uniq, res, order: np.ndarray, sample: int, paths: Sequence, stranded: bool, organism: str,
-                 sq_names: Optional[Sequence[str]] = None) -> dict:
+                 sq_names: Optional[Sequence[str]] = None, bgzf_out: bool = False) -> dict:
     """One sample's file (``stranded``: its two files) through ``mirge_coverage_write_device``; -> dict(intervals, weight, lines, bytes).
-    A data error -- a chromosome ``sq_names`` lacks, a row outside [1, 2^31 - 1] -- is a ValueError and leaves no file."""
+    A data error -- a chromosome ``sq_names`` lacks, a row outside [1, 2^31 - 1] -- is a ValueError and leaves no file.
+    ``bgzf_out``: ``paths`` are ``.bedgraph.gz`` files (``--bgzf-out``, bgzf.py), each written with its ``.gzi`` through
+    ``mirge_coverage_write_device_bgzf``; the dict gains ``bgzf`` = one ``bgzf.stats_dict`` per file."""
     paths = [str(p) for p in paths]
     if len(paths) != (2 if stranded else 1):
         raise ValueError("write_sample: one path, or two when stranded")
     classes, arr, _keep = sam_export.pass_tables(casc, organism)
     order = np.ascontiguousarray(order, dtype=np.int64)
+    if bgzf_out:
+        from . import bgzf
+        bgzf.route()
+        block = bgzf.block_bytes()
+    if classes.size == 0 and bgzf_out:  # no library of any class that has rows: empty streams
+        gz, gzi = bgzf.write_host(b"", block)
+        for p in paths:
+            for q, data in ((p, gz), (bgzf.gzi_path(p), gzi)):
+                with open(q, "wb") as fh:
+                    fh.write(data)
+        return dict(intervals=0, weight=0, lines=0, bytes=0,
+                    bgzf=[dict(file_bytes=len(gz), stored=0, fixed=0, dynamic=0, members=0, stream_bytes=0) for _ in paths])
     if classes.size == 0:  # no library of any class that has rows: empty files
         for p in paths:
             open(p, "wb").close()
@@ -196,10 +211,15 @@ def write_sample(casc, uniq, res, order: np.ndarray, sample: int, paths: Sequenc
     nm_off = np.ascontiguousarray(nm.offsets, dtype=np.int64)
     outs = [C.c_int64(0) for _ in range(4)]
     err = np.zeros(4, dtype=np.int64)
-    rc = _ffi.load().mirge_coverage_write_device(
-        casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, flat, off, len(names),
-        nm_data, nm_off, bool(stranded), paths[0].encode(), paths[1].encode() if stranded else None,
-        C.byref(outs[0]), C.byref(outs[1]), C.byref(outs[2]), C.byref(outs[3]), err)
+    common = (casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, flat, off, len(names),
+              nm_data, nm_off, bool(stranded), paths[0].encode(), paths[1].encode() if stranded else None,
+              C.byref(outs[0]), C.byref(outs[1]), C.byref(outs[2]), C.byref(outs[3]), err)
+    if bgzf_out:
+        st = np.zeros(2 * bgzf.N_STATS, dtype=np.int64)
+        rc = _ffi.load().mirge_coverage_write_device_bgzf(*common, bgzf.gzi_path(paths[0]).encode(),
+                                                          bgzf.gzi_path(paths[1]).encode() if stranded else None, block, st)
+    else:
+        rc = _ffi.load().mirge_coverage_write_device(*common)
     if rc != 0 and int(err[0]) == 2:
         read = uniq.unpack().to_list()[int(err[1])]
         raise ValueError(f"--coverage: read {read} on reference {_reference_name(casc, int(err[2]), int(err[3]))} lies outside "
@@ -207,8 +227,11 @@ def write_sample(casc, uniq, res, order: np.ndarray, sample: int, paths: Sequenc
     if rc != 0 and int(err[0]) == 1:
         msg = _ffi.load().mirge_last_error().decode()
         raise ValueError("--coverage: " + msg.split(": ", 1)[-1])
-    _ffi._check(rc, "mirge_coverage_write_device")
-    return dict(intervals=int(outs[0].value), weight=int(outs[1].value), lines=int(outs[2].value), bytes=int(outs[3].value))
+    _ffi._check(rc, "mirge_coverage_write_device_bgzf" if bgzf_out else "mirge_coverage_write_device")
+    out = dict(intervals=int(outs[0].value), weight=int(outs[1].value), lines=int(outs[2].value), bytes=int(outs[3].value))
+    if bgzf_out:
+        out["bgzf"] = [bgzf.stats_dict(st[k * bgzf.N_STATS:(k + 1) * bgzf.N_STATS]) for k in range(len(paths))]
+    return out
 
 
 def run(args, workDir, base_names, casc, uniq, res, order, tm: Optional[dict] = None) -> dict:
@@ -228,11 +251,17 @@ def run(args, workDir, base_names, casc, uniq, res, order, tm: Optional[dict] = 
             if getattr(args, "coverage_bigwig", False):  # first: a data error then leaves no file of this sample
                 from . import bigwig
                 files_bw.update(bigwig.run(args, workDir, base_names, casc, uniq, res, order, tm, sample=s))
-            paths = sample_paths(workDir, str(name), stranded)
-            st = write_sample(casc, uniq, res, order, s, paths, stranded, args.organism_name, sq_names)
+            bgzf_out = bool(getattr(args, "bgzf_out", False))
+            paths = sample_paths(workDir, str(name), stranded, bgzf_out)
+            st = write_sample(casc, uniq, res, order, s, paths, stranded, args.organism_name, sq_names, bgzf_out=bgzf_out)
             files[str(name)] = dict(paths=[str(p) for p in paths], **st)
+            gz = ""
+            if bgzf_out:
+                tot = {k: sum(f[k] for f in st["bgzf"]) for k in ("file_bytes", "members", "stored", "fixed", "dynamic")}
+                gz = (f" in {tot['file_bytes']} compressed bytes, {tot['members']} members: {tot['stored']} stored, {tot['fixed']} fixed, "
+                      f"{tot['dynamic']} dynamic")
             log.write(f"coverage ({'stranded' if stranded else 'unstranded'}, chromosomes in {'@SQ' if sq_names is not None else 'byte'} order) "
-                      f"{name}: {st['intervals']} intervals, summed weight {st['weight']}, {st['lines']} lines, {st['bytes']} bytes\n")
+                      f"{name}: {st['intervals']} intervals, summed weight {st['weight']}, {st['lines']} lines, {st['bytes']} bytes{gz}\n")
     if tm is not None:
         tm["coverage_s"] = time.perf_counter() - t0 - tm.get("coverage_bigwig_s", 0.0)
     for name, v in files_bw.items():

@@ -292,7 +292,8 @@ struct BamHuffWork { uint32_t a[MIRGE_BAM_HUFF_MAX]; uint32_t bl[16]; uint16_t o
 // OWN: k_bam_blocks_tight's copies of what takes pointers into the block's BamDynamic.  While k_bam_blocks_dynamic is the only caller the
 // compiler folds its one LDS block's addresses into these functions before it inlines them; a second caller's other block ends that, and
 // the dynamic kernel then compiles to other code (same registers and LDS, another schedule).  With copies of its own it stays what it was.
-template <bool OWN = false>
+// OWN is a number: 1 is the tight route's set of copies, 2 that of k_bgzf_text (kernels_bgzf.hpp).
+template <int OWN = 0>
 __device__ __forceinline__ void bam_huff_rank(const uint32_t* cnt, uint32_t n, uint8_t* len, BamHuffWork& w, uint32_t tid, uint32_t nth) {
     for (uint32_t s = tid; s < n; s += nth) {
         const uint32_t c = cnt[s];
@@ -303,7 +304,7 @@ __device__ __forceinline__ void bam_huff_rank(const uint32_t* cnt, uint32_t n, u
         w.order[rank] = (uint16_t)s; w.a[rank] = c;
     }
 }
-template <bool OWN = false>
+template <int OWN = 0>
 __device__ __forceinline__ void bam_huff_tree(const uint32_t* cnt, uint32_t n, uint32_t max_bits, uint8_t* len, BamHuffWork& w) {
     uint32_t* A = w.a;
     uint32_t m = 0;
@@ -347,7 +348,7 @@ __device__ __forceinline__ void bam_huff_lengths(const uint32_t* cnt, uint32_t n
     __syncthreads();
 }
 // two codes at once: the second one's tree is thread nth / 2's
-template <bool OWN = false>
+template <int OWN = 0>
 __device__ __forceinline__ void bam_huff_lengths2(const uint32_t* cnt0, uint32_t n0, uint8_t* len0, BamHuffWork& w0, const uint32_t* cnt1, uint32_t n1, uint8_t* len1,
                                                   BamHuffWork& w1, uint32_t max_bits, uint32_t tid, uint32_t nth) {
     bam_huff_rank<OWN>(cnt0, n0, len0, w0, tid, nth);
@@ -387,7 +388,7 @@ struct BamDynamic {
     uint8_t len_ll[MIRGE_BAM_HUFF_MAX], len_d[32], len_cl[2][32];
 };
 // length k of the HLIT + HDIST lengths the header spells, as one sequence
-template <bool OWN = false>
+template <int OWN = 0>
 __device__ __forceinline__ uint32_t bam_dyn_seq(const BamDynamic& y, uint32_t k) { return k < y.hlit ? y.len_ll[k] : y.len_d[k - y.hlit]; }
 
 // the counting walk of deflate == 2: the segment's bits under the fixed code, as BamBits<false> counts them; its symbols into the wave's
@@ -436,7 +437,7 @@ __device__ __forceinline__ void bam_put_match(BamDynBits& w, uint32_t len, uint3
 // thread 0, the lengths of both codes known: HLIT, HDIST, and the sequence of their lengths in the symbols 0 .. 18 twice -- with the
 // run symbols (16: the length in front 3 to 6 times more, 17: 3 to 10 zeros, 18: 11 to 138 zeros; greedy, a run may cross from one code
 // into the other) into tok, and plain, a symbol per length -- and either form's counts
-template <bool OWN = false>
+template <int OWN = 0>
 __device__ __forceinline__ void bam_dyn_header_tokens(BamDynamic& y) {
     uint32_t hlit = MIRGE_BAM_NLL, hdist = MIRGE_BAM_ND, any = 0;
     for (uint32_t x = 0; x < MIRGE_BAM_ND; x++) any |= y.len_d[x];
@@ -464,7 +465,7 @@ __device__ __forceinline__ void bam_dyn_header_tokens(BamDynamic& y) {
     y.n_tok = nt;
 }
 // thread 0, the lengths of the code of either form known: the shorter header (a tie: the one with run symbols), HCLEN, its bits with BFINAL and BTYPE
-template <bool OWN = false>
+template <int OWN = 0>
 __device__ __forceinline__ void bam_dyn_header_choice(BamDynamic& y) {
     uint32_t bits[2], hclen[2];
     for (uint32_t f = 0; f < 2u; f++) {
@@ -478,7 +479,7 @@ __device__ __forceinline__ void bam_dyn_header_choice(BamDynamic& y) {
     y.hclen = y.plain ? hclen[1] : hclen[0];
 }
 // thread 0: the header into the output words
-template <bool OWN = false>
+template <int OWN = 0>
 __device__ __forceinline__ void bam_dyn_put_header(const BamDynamic& y, BamBits<true>& b) {
     b.put(5u, 3);  // BFINAL = 1, BTYPE = 10
     b.put(y.hlit - 257u, 5); b.put(y.hdist - 1u, 5); b.put(y.hclen - 4u, 4);

@@ -50,6 +50,7 @@ __device__ __forceinline__ void load_read(const GroupView<W>& g, uint32_t i, Mir
 #include "kernels_pileup.hpp"
 #include "kernels_sam.hpp"
 #include "kernels_bam.hpp"
+#include "kernels_bgzf.hpp"
 #include "kernels_trf.hpp"
 #include "kernels_umi.hpp"
 #include "kernels_ec.hpp"

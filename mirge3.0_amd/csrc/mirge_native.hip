@@ -50,6 +50,7 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_genome.hpp"
 #include "native_pileup.hpp"
 #include "native_stage.hpp"
+#include "native_bgzf.hpp"
 #include "native_sam.hpp"
 #include "native_bam.hpp"
 #include "native_trf.hpp"

@@ -254,13 +254,16 @@ struct CovInput {
     }
 };
 
-extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
-                                           const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
-                                           const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
-                                           const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
-                                           int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
-                                           int64_t* err_out) {
-    const std::string who = "mirge_coverage_write_device";
+// mirge_coverage_write_device and mirge_coverage_write_device_bgzf: gzi_path == nullptr are the plain files, else `path` / `path_minus`
+// are .gz files, each a stream of its own (BgzfSink): the minus file's block 0 starts at the minus text's byte 0
+static int coverage_write_impl(const std::string& who, mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                               const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                               const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                               const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
+                               int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
+                               int64_t* err_out, const char* gzi_path, const char* gzi_path_minus, int64_t block_bytes, int64_t* stats_out) {
+    const bool bgzf = gzi_path != nullptr;
+    if (bgzf && stranded && !gzi_path_minus) return fail(-1, who + ": bad argument");
     if (!c || !path || (stranded && !path_minus) || !chrom_rank || !chrom_rank_off || n_rank < 0 || n_rank > (1 << 24) || !rank_name_off ||
         (n_rank && !rank_names) || n_pass < 1 || n_pass > MIRGE_MAX_PASSES || !passes)
         return fail(-1, who + ": bad argument");
@@ -278,7 +281,11 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
     CovDev dev;
     uint8_t* d_text[2] = {nullptr, nullptr};
     OutFile out[2] = {{who}, {who}};  // (the strands' files: both or neither, commit_all; uncommitted, a file goes)
+    BgzfStream gz0(who), gz1(who);
+    BgzfStream* const gzs[2] = {&gz0, &gz1};
     PoolScope scope(c);
+    BgzfSink sink(scope, who);
+    if (bgzf) CHECK(sink.configure(block_bytes));  // (a wrong MIRGE_BGZF_* value: before anything is done)
     CHECK(in.build(scope, who, U, res, order, sample, class_pass, n_class, passes, n_pass, chrom_rank, chrom_rank_off, n_rank, err_out, hc));
     CHECK(dev.runs(scope, who, in.intervals(), in.n_rows, (uint32_t)std::max(n_rank, 1), stranded != 0));
     hc.lap("runs");
@@ -286,6 +293,30 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
     hc.lap("measured");
     // ---- the file or files: every error of the data has been raised by now
     const unsigned long long body = dev.body, split = stranded ? dev.split : dev.body;
+    if (bgzf) {
+        const unsigned long long base[2] = {0ull, split};
+        gz0.bytes = split; gz1.bytes = body - split;
+        CHECK(gz0.open(path, gzi_path));
+        if (stranded) CHECK(gz1.open(path_minus, gzi_path_minus));
+        auto fill = [&](int s, unsigned long long at, uint32_t nn, uint8_t* dst, const uint8_t** text) -> int {
+            const size_t tiles = ((size_t)nn + tile - 1) / tile;
+            LaunchScope ls(c, "k_cov_write", (double)nn);
+            hipLaunchKernelGGL(k_cov_write, dim3((unsigned)std::min<size_t>(tiles, (size_t)c->n_cu * 32)), dim3(MIRGE_BLOCK), 0, c->stream, dev.r,
+                               (uint32_t)dev.n_runs, (const uint32_t*)dev.d_name_off, (const uint8_t*)dev.d_name_data,
+                               (const unsigned long long*)dev.d_off, base[s] + at, nn, (uint32_t)tile, dst);
+            *text = dst;
+            return 0;
+        };
+        CHECK(sink.run(gzs, stranded ? 2 : 1, chunk, fill));
+        hc.lap("formatted + deflated + written");
+        CHECK(commit_all({&gz0.gz, &gz0.gzi, &gz1.gz, &gz1.gzi}));
+        if (stats_out) { gz0.stats(stats_out); gz1.stats(stats_out + MIRGE_BGZF_STATS); }
+        if (n_intervals_out) *n_intervals_out = (int64_t)in.n_rows;
+        if (weight_out) *weight_out = (int64_t)dev.weight;
+        if (n_lines_out) *n_lines_out = (int64_t)dev.n_runs;
+        if (n_bytes_out) *n_bytes_out = (int64_t)dev.body;
+        return 0;
+    }
     CHECK(out[0].open(path));
     if (stranded) CHECK(out[1].open(path_minus));
     if (body) {
@@ -323,4 +354,29 @@ extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, c
     if (n_lines_out) *n_lines_out = (int64_t)dev.n_runs;
     if (n_bytes_out) *n_bytes_out = (int64_t)dev.body;
     return 0;
+}
+
+extern "C" int mirge_coverage_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                                           const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                           const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                                           const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
+                                           int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
+                                           int64_t* err_out) {
+    return coverage_write_impl("mirge_coverage_write_device", c, U, res, order, sample, class_pass, n_class, passes, n_pass, chrom_rank, chrom_rank_off,
+                               n_rank, rank_names, rank_name_off, stranded, path, path_minus, n_intervals_out, weight_out, n_lines_out, n_bytes_out,
+                               err_out, nullptr, nullptr, 0, nullptr);
+}
+// `path` / `path_minus` are the .bedgraph.gz files, gzi_path / gzi_path_minus their block indexes; block_bytes <= 0:
+// MIRGE_BGZF_BLOCK_BYTES; stats_out[16]: BgzfStream::stats of either file
+extern "C" int mirge_coverage_write_device_bgzf(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                                                const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                                const int32_t* chrom_rank, const int64_t* chrom_rank_off, int32_t n_rank, const char* rank_names,
+                                                const int64_t* rank_name_off, int32_t stranded, const char* path, const char* path_minus,
+                                                int64_t* n_intervals_out, int64_t* weight_out, int64_t* n_lines_out, int64_t* n_bytes_out,
+                                                int64_t* err_out, const char* gzi_path, const char* gzi_path_minus, int64_t block_bytes,
+                                                int64_t* stats_out) {
+    if (!gzi_path) return fail(-1, "mirge_coverage_write_device_bgzf: bad argument");
+    return coverage_write_impl("mirge_coverage_write_device_bgzf", c, U, res, order, sample, class_pass, n_class, passes, n_pass, chrom_rank,
+                               chrom_rank_off, n_rank, rank_names, rank_name_off, stranded, path, path_minus, n_intervals_out, weight_out, n_lines_out,
+                               n_bytes_out, err_out, gzi_path, gzi_path_minus, block_bytes, stats_out);
 }

@@ -140,13 +140,15 @@ struct SamPrep {
     }
 };
 
-extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
-                                      const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
-                                      const char* path, const char* header, int64_t header_len, int64_t* n_lines_out,
-                                      int64_t* n_bytes_out) {
-    if (!c || !path || (!header && header_len) || header_len < 0) return fail(-1, "mirge_sam_write_device: bad argument");
+// mirge_sam_write_device and mirge_sam_write_device_bgzf: gzi_path == nullptr is the plain file, else `path` is the .gz (BgzfSink)
+static int sam_write_impl(const std::string& who, mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                          const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass, const char* path,
+                          const char* header, int64_t header_len, int64_t* n_lines_out, int64_t* n_bytes_out, const char* gzi_path,
+                          int64_t block_bytes, int64_t* stats_out) {
+    if (!c || !path || (!header && header_len) || header_len < 0) return fail(-1, who + ": bad argument");
     HIPOK(hipSetDevice(c->device)); CHECK(join_pending_now(c));
     HostClock hc("sam_write_device");
+    const bool bgzf = gzi_path != nullptr;
     // ---- sizes of the chunked output
     size_t tile = env_bytes("MIRGE_SAM_TILE_BYTES", 8160);  // 255 probe points of 32 bytes + the one behind the tile's end: one per thread
     tile = std::min<size_t>(MIRGE_SAM_MAX_TILE, std::max<size_t>(64, tile)) & ~size_t(15);
@@ -157,9 +159,13 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     uint8_t* d_text[2] = {nullptr, nullptr};
     uint32_t* d_fixed;
     unsigned long long *d_total, *d_off, *d_nlines, body = 0, lines = 0;
-    OutFile out("mirge_sam_write_device");  // (not committed: it takes its file with it, behind the scope's wait)
+    OutFile out(who);  // (not committed: it takes its file with it, behind the scope's wait)
+    BgzfStream gz(who);
+    BgzfStream* const gzs[1] = {&gz};
     PoolScope scope(c);
-    CHECK(prep.build(scope, "mirge_sam_write_device", U, res, order, sample, class_pass, n_class, passes, n_pass));
+    BgzfSink sink(scope, who);
+    if (bgzf) CHECK(sink.configure(block_bytes));  // (a wrong MIRGE_BGZF_* value: before anything is done)
+    CHECK(prep.build(scope, who, U, res, order, sample, class_pass, n_class, passes, n_pass));
     const SamTables& t = prep.t;
     uint32_t* const d_rows = prep.d_rows;
     const size_t n_rows = prep.n_rows;
@@ -181,6 +187,37 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     HIPOK(hipMemcpyAsync(&lines, d_nlines, 8, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
     hc.lap("measured");
+    if (bgzf) {  // ---- the stream is the header and the body in one; its chunks are whole BGZF blocks
+        const unsigned long long H = (unsigned long long)header_len;
+        uint8_t* d_header = nullptr;
+        if (H) {
+            CHECK(scope.get(&d_header, (size_t)H + 16));
+            HIPOK(hipMemcpyAsync(d_header, header, (size_t)H, hipMemcpyHostToDevice, c->stream));
+        }
+        gz.bytes = H + body;
+        CHECK(gz.open(path, gzi_path));
+        // the header's part of a chunk lies in front of a multiple of 16, where k_sam_write's 16-byte stores start
+        auto fill = [&](int, unsigned long long at, uint32_t nn, uint8_t* dst, const uint8_t** text) -> int {
+            const uint32_t hpart = at < H ? (uint32_t)std::min<unsigned long long>(nn, H - at) : 0u, pad = (16u - (hpart & 15u)) & 15u, bn = nn - hpart;
+            if (hpart) HIPOK(hipMemcpyAsync(dst + pad, d_header + at, hpart, hipMemcpyDeviceToDevice, c->stream));
+            if (bn) {
+                const size_t tiles = ((size_t)bn + tile - 1) / tile;
+                LaunchScope ls(c, "k_sam_write", (double)bn);
+                hipLaunchKernelGGL(k_sam_write, dim3((unsigned)std::min<size_t>(tiles, (size_t)c->n_cu * 32)), dim3(MIRGE_BLOCK), 0, c->stream, t,
+                                   (const uint32_t*)d_rows, (uint32_t)n_rows, (const uint32_t*)d_fixed, (const unsigned long long*)d_off, at + hpart - H, bn,
+                                   (uint32_t)tile, dst + pad + hpart);
+            }
+            *text = dst + pad;
+            return 0;
+        };
+        CHECK(sink.run(gzs, 1, chunk, fill));
+        hc.lap("formatted + deflated + written");
+        CHECK(commit_all({&gz.gz, &gz.gzi}));
+        if (stats_out) gz.stats(stats_out);
+        if (n_lines_out) *n_lines_out = (int64_t)lines;
+        if (n_bytes_out) *n_bytes_out = (int64_t)body;
+        return 0;
+    }
     // ---- the file: header, then the body chunk by chunk
     CHECK(out.open(path));
     if (header_len && out.put(header, (size_t)header_len, 0)) return fail(-8, std::string("cannot write ") + path);
@@ -214,4 +251,21 @@ extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const 
     if (n_lines_out) *n_lines_out = (int64_t)lines;
     if (n_bytes_out) *n_bytes_out = (int64_t)body;
     return 0;
+}
+
+extern "C" int mirge_sam_write_device(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                                      const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                      const char* path, const char* header, int64_t header_len, int64_t* n_lines_out,
+                                      int64_t* n_bytes_out) {
+    return sam_write_impl("mirge_sam_write_device", c, U, res, order, sample, class_pass, n_class, passes, n_pass, path, header, header_len, n_lines_out,
+                          n_bytes_out, nullptr, 0, nullptr);
+}
+// `path` is `<sample>.sam.gz`, gzi_path its block index; block_bytes <= 0: MIRGE_BGZF_BLOCK_BYTES; stats_out[8]: BgzfStream::stats
+extern "C" int mirge_sam_write_device_bgzf(mirge_ctx* c, const mirge_reads* U, const mirge_result* res, const int64_t* order, int32_t sample,
+                                           const int32_t* class_pass, int32_t n_class, const mirge_sam_pass* passes, int32_t n_pass,
+                                           const char* path, const char* header, int64_t header_len, int64_t* n_lines_out,
+                                           int64_t* n_bytes_out, const char* gzi_path, int64_t block_bytes, int64_t* stats_out) {
+    if (!gzi_path) return fail(-1, "mirge_sam_write_device_bgzf: bad argument");
+    return sam_write_impl("mirge_sam_write_device_bgzf", c, U, res, order, sample, class_pass, n_class, passes, n_pass, path, header, header_len,
+                          n_lines_out, n_bytes_out, gzi_path, block_bytes, stats_out);
 }

@@ -335,6 +335,9 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
             if getattr(args, "unmapped_features", False):  # generate_featureFiles / get_precursors (novel_mir.py:424-428)
                 from . import unmapped_features as _unmapped_features
                 out["unmapped_features"] = _unmapped_features.run(args, ctx, workDir, base_names, tm)
+    # --bgzf-out rides on args into both text exporters below: <sample>.sam.gz / <sample>.bedgraph.gz with their .gzi (bgzf.py)
+    if getattr(args, "bgzf_out", False) and not (getattr(args, "sam_out", False) or getattr(args, "coverage", None)):
+        raise RuntimeError("--bgzf-out needs --sam-out or --coverage")
     if getattr(args, "sam_out", False):  # --sam-out: <sample>.sam, one line per raw read (manifoldAlign.py:12-64, bamFmt.py:115-170)
         if ann is not None or res is None:
             raise RuntimeError("--sam-out needs the cascade's result on the device (a single-process run)")

@@ -218,10 +218,29 @@ def pass_tables(casc, organism: str):
     return out
 
 
-def write_sample(casc, uniq, res, order: np.ndarray, sample: int, path, header: bytes, organism: str):
-    """One sample's file through ``mirge_sam_write_device``; -> (lines below the header, their bytes)"""
+def write_sample(casc, uniq, res, order: np.ndarray, sample: int, path, header: bytes, organism: str, bgzf_out: bool = False):
+    """One sample's file through ``mirge_sam_write_device``; -> (lines below the header, their bytes).  ``bgzf_out``: ``path`` is the
+    ``.sam.gz`` file (``--bgzf-out``, bgzf.py), written with its ``.gzi`` through ``mirge_sam_write_device_bgzf``; -> (lines, bytes, the
+    file's numbers as ``bgzf.stats_dict`` gives them)"""
     classes, arr, _keep = pass_tables(casc, organism)
     order = np.ascontiguousarray(order, dtype=np.int64)
+    if bgzf_out:
+        from . import bgzf
+        bgzf.route()
+        block = bgzf.block_bytes()
+        if classes.size == 0:  # no library of any class that writes lines: the header alone
+            gz, gzi = bgzf.write_host(header, block)
+            for p, data in ((str(path), gz), (bgzf.gzi_path(path), gzi)):
+                with open(p, "wb") as fh:
+                    fh.write(data)
+            ms = bgzf.members(gz)
+            return 0, 0, dict(file_bytes=len(gz), stored=sum(m["btype"] == 0 for m in ms), fixed=sum(m["btype"] == 1 for m in ms),
+                              dynamic=sum(m["btype"] == 2 for m in ms), members=len(ms), stream_bytes=len(header))
+        n_lines, n_bytes, st = C.c_int64(0), C.c_int64(0), np.zeros(bgzf.N_STATS, dtype=np.int64)
+        _ffi._check(_ffi.load().mirge_sam_write_device_bgzf(
+            casc.ctx._h, uniq._h, res._h, order if order.size else None, sample, classes, classes.size, arr, casc.n_pass, str(path).encode(),
+            header, len(header), C.byref(n_lines), C.byref(n_bytes), bgzf.gzi_path(path).encode(), block, st), "mirge_sam_write_device_bgzf")
+        return int(n_lines.value), int(n_bytes.value), bgzf.stats_dict(st)
     if classes.size == 0:  # no library of any class that writes lines: the header alone
         with open(path, "wb") as fh:
             fh.write(header)
@@ -251,8 +270,16 @@ def run(args, workDir, base_names, casc, uniq, res, order, tm: Optional[dict] = 
     pass_tables(casc, args.organism_name)
     t_tables = time.perf_counter() - t_tables
     files = {}
+    bgzf_out = bool(getattr(args, "bgzf_out", False))
     for s, name in enumerate(base_names):
-        path = workDir / (str(name) + ".sam")
+        path = workDir / (str(name) + (".sam.gz" if bgzf_out else ".sam"))
+        if bgzf_out:
+            n_lines, n_bytes, st = write_sample(casc, uniq, res, order, s, path, header, args.organism_name, bgzf_out=True)
+            files[str(name)] = dict(path=str(path), lines=n_lines, bytes=n_bytes, bgzf=st)
+            with open(workDir / "run.log", "a+") as log:
+                log.write(f"sam-out (bgzf) {name}: {n_lines} lines, {st['stream_bytes']} bytes of text in {st['file_bytes']} compressed bytes, "
+                          f"{st['members']} members: {st['stored']} stored, {st['fixed']} fixed, {st['dynamic']} dynamic\n")
+            continue
         n_lines, n_bytes = write_sample(casc, uniq, res, order, s, path, header, args.organism_name)
         files[str(name)] = dict(path=str(path), lines=n_lines, bytes=n_bytes)
     if tm is not None:
