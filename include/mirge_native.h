@@ -217,6 +217,25 @@ int mirge_kmer_correct_stats(int64_t* out);
 int mirge_kmer_correct_ratio(mirge_ctx* ctx, const mirge_reads* uniq, int32_t k_start, int32_t k_end, int32_t threshold, int32_t ratio,
                              mirge_reads** out, uint32_t* final_of, uint32_t* rounds_mask);
 int mirge_kmer_correct_ratio_stats(int64_t* out);
+/* -a auto: a sample's 3' adapter from the distinct reads of its head (README, "`-a auto`: the 3' adapter, inferred from the reads").  uniq: a
+ * collapse result with ONE count column (more: an error), made of UNTRIMMED reads.  A read without N of 12 .. 256 letters is eligible;
+ * T = the sum of their counts; for a 12-mer x, C(x) = the sum of the counts over every window start p <= 63 that spells x and M(x) the
+ * mask of those p.  The seed is the 12-mer with the largest C among those with three distinct letters, popcount(M) >= 6 and
+ * C >= max(32, ceil(T / 20)) (equal C: the smallest string); up to 64 steps to the left while a letter in front keeps popcount(M) >= 6
+ * and 10 C >= 9 C(current); then to the right, up to 32 letters, while a letter behind has 2 C >= C(start).  No candidate, or an empty
+ * dictionary: seq is empty, len 0 (T and candidates are still reported).  Codes have the first letter most significant (A C G T =
+ * 0 1 2 3).  probe (n_probe codes, may be NULL with 0): probe_sum[q] / probe_mask[q] = C and M of code probe[q] (a code >= 4^12: zeros). */
+typedef struct mirge_adapter {
+    char seq[40];          /* NUL-terminated; empty: no adapter */
+    int32_t len, left_steps, spread, pad; /* letters; steps of the left walk; popcount(M(start)) */
+    uint64_t support;      /* C(start) */
+    uint64_t eligible;     /* T */
+    uint64_t seed_sum;     /* C(seed) */
+    uint64_t candidates;   /* seed candidates */
+    uint32_t seed, start;  /* codes, first letter most significant */
+} mirge_adapter;
+int mirge_adapter_infer(mirge_ctx* ctx, const mirge_reads* uniq, mirge_adapter* out, const uint32_t* probe, int64_t n_probe, uint64_t* probe_sum,
+                        uint64_t* probe_mask);
 /* Several raw read sets as one, in the order given (the samples of a run, one file each, before the joint collapse
  * that replaces the per-file dicts and their outer join, digest.py:133-163,243).  The parts stay valid. */
 int mirge_reads_concat(mirge_ctx* ctx, const mirge_reads* const* parts, int32_t n_parts, mirge_reads** out);

@@ -51,6 +51,7 @@ int mirge_kmer_correct(mirge_ctx*, const mirge_reads*, int32_t, int32_t, int32_t
 int mirge_kmer_correct_stats(int64_t*);
 int mirge_kmer_correct_ratio(mirge_ctx*, const mirge_reads*, int32_t, int32_t, int32_t, int32_t, mirge_reads**, uint32_t*, uint32_t*);
 int mirge_kmer_correct_ratio_stats(int64_t*);
+int mirge_adapter_infer(mirge_ctx*, const mirge_reads*, mirge_adapter*, const uint32_t*, int64_t, uint64_t*, uint64_t*);
 int mirge_reads_concat(mirge_ctx*, const mirge_reads* const*, int32_t, mirge_reads**);
 void mirge_reads_destroy(mirge_reads*);
 int64_t mirge_reads_count(const mirge_reads*);
@@ -234,8 +235,21 @@ class SamPass(C.Structure):
                 ("cds_hi", C.c_void_p), ("n_chrom", C.c_int64), ("chrom_data", C.c_void_p), ("chrom_off", C.c_void_p)]
 
 
+class MirgeAdapter(C.Structure):
+    """``mirge_adapter`` of include/mirge_native.h: what ``mirge_adapter_infer`` found (``-a auto``)"""
+    _fields_ = [("seq", C.c_char * 40), ("len", C.c_int32), ("left_steps", C.c_int32), ("spread", C.c_int32), ("pad", C.c_int32),
+                ("support", C.c_uint64), ("eligible", C.c_uint64), ("seed_sum", C.c_uint64), ("candidates", C.c_uint64),
+                ("seed", C.c_uint32), ("start", C.c_uint32)]
+
+    FIELDS = ("seq", "len", "left_steps", "spread", "support", "eligible", "seed_sum", "candidates", "seed", "start")
+
+    def as_dict(self) -> dict:
+        return {k: (self.seq.decode() if k == "seq" else int(getattr(self, k))) for k in self.FIELDS}
+
+
 _SCALARS = {"void": None, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
-_STRUCTS = {"mirge_policy": MirgePolicy, "mirge_trim": MirgeTrim, "mirge_umi": MirgeUmi, "mirge_sam_pass": SamPass}
+_STRUCTS = {"mirge_policy": MirgePolicy, "mirge_trim": MirgeTrim, "mirge_umi": MirgeUmi, "mirge_sam_pass": SamPass,
+            "mirge_adapter": MirgeAdapter}
 _ELEMENTS = {"char": "uint8", "void": None, "float": "float32", "double": "float64",
              **{t + "_t": t for t in ("int8", "uint8", "int32", "uint32", "int64", "uint64")}}  # C element type -> dtype (None: any)
 
@@ -790,6 +804,20 @@ class DeviceReads:
         _check(load().mirge_kmer_correct_ratio(self.ctx._h, self._h, k_start, k_end, threshold, ratio, C.byref(h), final_of, mask),
                "mirge_kmer_correct_ratio")
         return DeviceReads(self.ctx, h), final_of[:n], mask[:n]
+
+    def adapter_infer(self, probes=None):
+        """``mirge_adapter_infer`` on a one-column collapse result of UNTRIMMED reads (``-a auto``) -> the fields of ``mirge_adapter`` as a
+        dict (``seq`` empty: no adapter); with ``probes`` (12-mer codes, first letter most significant) -> (that dict, uint64 sums,
+        uint64 masks of the probed codes)"""
+        out = MirgeAdapter()
+        if probes is None:
+            _check(load().mirge_adapter_infer(self.ctx._h, self._h, C.byref(out), None, 0, None, None), "mirge_adapter_infer")
+            return out.as_dict()
+        codes = np.ascontiguousarray(probes, dtype=np.uint32)
+        n = int(codes.shape[0])
+        sums, masks = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        _check(load().mirge_adapter_infer(self.ctx._h, self._h, C.byref(out), codes if n else None, n, sums, masks), "mirge_adapter_infer")
+        return out.as_dict(), sums[:n], masks[:n]
 
     def first_appearance_order(self) -> np.ndarray:
         """Indices of the unique reads in the order their first copy appeared in the raw reads (``mirge_collapse_order``)."""

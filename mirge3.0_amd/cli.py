@@ -3,7 +3,7 @@
   python -m mirge3_amd.cli -s S1.fastq,S2.fastq -lib /path/Libs -on human -db miRBase -o out
 
 Same flag names as the reference (``mirge/libs/parse.py``) for what is implemented -- trimming (-a / -g / -q / -nxt / -NX /
--u), UMIs (-umi / --qiagenumi / -udd), -spk, -tcf, -spl / -rr, -ie, -gff, -ai, --kmer-correct (--kmer-ratio) --; switches of subsystems that are out of
+-u; -a auto infers each sample's 3' adapter), UMIs (-umi / --qiagenumi / -udd), -spk, -tcf, -spl / -rr, -ie, -gff, -ai, --kmer-correct (--kmer-ratio) --; switches of subsystems that are out of
 scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignored.  Writes the reference's files:
 ``run.log``, ``mapped.csv``, ``unmapped.csv``, ``miR.Counts.csv``, ``miR.RPM.csv``, ``annotation.report.csv/html``
 (+ ``isomirs.csv`` / ``isomirs.samples.csv`` with ``-ie``, ``sample_miRge3.gff`` with ``-gff``, the three
@@ -76,7 +76,9 @@ def parse_args(argv=None):
     # -a and -g fill ONE list of (kind, sequence) in command-line order, as mirge/libs/parse.py does: the order decides ties
     # between two adapters, and what 'illumina' stands for (mirge/__main__.py:65-83)
     ap.add_argument("-a", "--adapter", dest="adapters", action="append", default=None, type=lambda x: ("back", x),
-                    help="3' adapter removed from every read (cutadapt's regular 3' adapter; 'illumina' = TGGAATTCTCGGGTGCCAAGGAACTCCAG)")
+                    help="3' adapter removed from every read (cutadapt's regular 3' adapter; 'illumina' = TGGAATTCTCGGGTGCCAAGGAACTCCAG; "
+                         "'auto' = inferred on the device from each sample's first MIRGE_ADAPTER_HEAD_READS records, default 2^18: the only "
+                         "-a of the run, one -g SEQ may follow; writes adapter.auto.csv; README, '-a auto')")
     ap.add_argument("-g", "--front", dest="adapters", action="append", default=None, type=lambda x: ("front", x),
                     help="5' adapter: the adapter and everything in front of it are removed (cutadapt's regular 5' adapter; "
                          "'illumina' = GTTCAGAGTTCTACAGTCCGACGATC); with two adapters the better match is removed from a read")
@@ -236,6 +238,11 @@ def parse_args(argv=None):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             ap.error("--kmer-correct is a single-process option")
         args.kmer_range = (vals["ks"], vals["ke"], vals["kh"])
+    from . import adapter_auto
+    why = adapter_auto.refusal(args)
+    if why:
+        ap.error(why)
+    args.adapter_auto = adapter_auto.wanted(args)
     if args.qiagenumi and not (args.adapters and args.adapters[0][0] == "back"):
         ap.error("--qiagenumi reads the UMI behind the 3' adapter: give it with -a (first)")
     args.bowtieVersion = "True"
@@ -418,6 +425,9 @@ def main(argv=None):
     if unpinned and rank == 0:  # counted with, but not silently: these follow cutadapt's documentation, no real cutadapt has confirmed them
         msg = ("WARNING: trimming option(s) " + "; ".join(unpinned) + " are implemented from cutadapt's documentation and have not been "
                "compared with cutadapt itself (tools/cutadapt_crosscheck.py does that where cutadapt is installed)")
+    if unpinned and args.adapter_auto:
+        args.unpinned_note = msg  # (-a auto: said behind the inferred adapters' lines, fastpath.run)
+    elif unpinned and rank == 0:
         with open(workDir / "run.log", "a+") as fh:
             fh.write(msg + "\n")
         if not args.quiet:

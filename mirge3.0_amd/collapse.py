@@ -575,11 +575,12 @@ ILLUMINA_3P = 'TGGAATTCTCGGGTGCCAAGGAACTCCAG'  # what `-a illumina` stands for (
 ILLUMINA_5P = 'GTTCAGAGTTCTACAGTCCGACGATC'     # what `-g illumina` stands for
 
 
-def adapters_from_args(args):
+def adapters_from_args(args, auto=None):
     """``args.adapters`` as the reference has it after mirge/__main__.py:65-83: a list of (kind, sequence) in command-line
     order, 'illumina' spelled out -- with ONE adapter by its kind, with TWO by its position (the first is taken for the 3'
     adapter, the second for the 5' one, whatever their flags were: the reference's own rule).  Plain strings (3' adapters)
-    and a separate ``front`` list are accepted from callers that build the namespace themselves."""
+    and a separate ``front`` list are accepted from callers that build the namespace themselves.  ``auto``: the sequence that
+    stands for the literal ``auto`` of ``-a auto`` (adapter_auto.py: one per sample); without it the literal stays."""
     adapters = getattr(args, "adapters", None) or []
     if isinstance(adapters, str):
         adapters = [adapters]
@@ -592,6 +593,8 @@ def adapters_from_args(args):
         adapters = [(k, (ILLUMINA_3P, ILLUMINA_5P)[i] if q == "illumina" else q) for i, (k, q) in enumerate(adapters)]
     elif len(adapters) == 1:
         adapters = [(k, {"back": ILLUMINA_3P, "front": ILLUMINA_5P}.get(k, q) if q == "illumina" else q) for k, q in adapters]
+    if auto is not None:
+        adapters = [(k, auto if q == "auto" else q) for k, q in adapters]
     return adapters
 
 
@@ -635,14 +638,17 @@ def parse_adapter_spec(kind: str, spec: str) -> dict:
     return dict(kind=kind, seq=spec, anchored=anchored)
 
 
-def trim_from_args(args):
+def trim_from_args(args, auto=None):
     """The cutadapt modifier chain of ``stipulate`` (digest.py:59-101) as the options of ``mirge_reads_parse_trim``:
     ``-q`` (default "10": quality trimming is ALWAYS in the reference's chain), ``-a`` / ``-g`` (one or two adapters, 3'
     or 5', regular or anchored; with two, a read loses the better match -- AdapterCutter with times = 1 --; or ONE linked
     adapter ``A...B``: ``parse_adapter_spec``), ``-nxt``, ``-NX``, ``-u``,
     ``--overlap``, ``--error-rate``, ``-phr``, ``-n`` (repeat the removal), ``--no-indels``, ``--match-read-wildcards``, ``-N``,
-    ``--action none``.  More than two adapters and ``--action mask`` / ``lowercase`` are refused."""
-    adapters = adapters_from_args(args)
+    ``--action none``.  More than two adapters and ``--action mask`` / ``lowercase`` are refused.  ``auto``: this sample's inferred 3'
+    adapter, in place of the literal of ``-a auto``."""
+    adapters = adapters_from_args(args, auto)
+    if any(q == "auto" for _, q in adapters):
+        raise SystemExit("-a auto: the adapter is inferred per sample on the device-resident route (fastpath.run); this route has no sequence for it")
     if len(adapters) > 2 or any(kind not in ("back", "front") for kind, _ in adapters):
         raise NotImplementedError("up to two adapters are supported (-a / -g, in any combination)")
     specs = [parse_adapter_spec(k, q) for k, q in adapters]

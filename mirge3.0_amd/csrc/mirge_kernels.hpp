@@ -54,5 +54,6 @@ __device__ __forceinline__ void load_read(const GroupView<W>& g, uint32_t i, Mir
 #include "kernels_trf.hpp"
 #include "kernels_umi.hpp"
 #include "kernels_ec.hpp"
+#include "kernels_adapter.hpp"
 #include "kernels_cov.hpp"
 #include "kernels_bw.hpp"

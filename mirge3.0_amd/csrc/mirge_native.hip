@@ -56,5 +56,6 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_trf.hpp"
 #include "native_umi.hpp"
 #include "native_ec.hpp"
+#include "native_adapter.hpp"
 #include "native_cov.hpp"
 #include "native_bw.hpp"

@@ -155,7 +155,21 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
     if tm["libraries_s"] > 0.005:  # this call loaded them: where the time went
         tm["libraries_detail_s"] = {k: round(v, 4) for k, v in casc.timing.items()}
     min_len = int(getattr(args, "minimum_length", 16))
-    trim = trim_from_args(args)
+    if getattr(args, "adapter_auto", False):  # -a auto: every sample's own 3' adapter, all inferred before any sample is parsed
+        from . import adapter_auto
+        t_a = time.perf_counter()
+        try:
+            autos = adapter_auto.infer_all(ctx, files, base_names, workDir, say)
+        except SystemExit as e:
+            outlog.write(str(e) + "\n")
+            outlog.close()
+            raise
+        tm["adapter_auto_s"] = time.perf_counter() - t_a
+        if getattr(args, "unpinned_note", None):
+            say(args.unpinned_note)
+        trims = [trim_from_args(args, auto=a) for a in autos]  # the MirgeTrim per sample
+    else:
+        trims = [trim_from_args(args)] * len(files)
     umi = umi_from_args(args)
     sampleReadCounts, trimmedReadCounts, trimmedReadCountsUnique = {}, {}, {}
     parsed = []
@@ -173,7 +187,7 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
     del _collapse.GZ_LOG[:]
     texts = read_texts(files, stream=True)  # read ahead on worker threads; a .gz is inflated on all cores, or piece by piece beside its parse
     gz_tm: Dict[str, float] = {}
-    for f, name in zip(files, base_names):
+    for f, name, trim in zip(files, base_names, trims):
         t = time.perf_counter()
         text = next(texts)
         t_read += time.perf_counter() - t
