@@ -680,6 +680,28 @@ int mirge_trf_cluster(mirge_ctx* ctx, const mirge_reads* uniq, int64_t n_grp, co
                       const double* rp100k, const int32_t* tlen, int64_t n_gauss, const double* gauss, float* rho, float* delta,
                       int32_t* nneigh, int32_t* order, int32_t* cl, int32_t* halo, int32_t* nclust, int32_t* centre);
 
+/* ---- per-sample read QC (--read-qc; mirge3_amd/readqc.py holds the specification)
+ * mirge_qc            the accumulator of ONE sample: the 64-bit tables of the `raw` and the `trimmed` view in device memory, alive across the
+ *                     pieces of a streamed sample.  Integer sums only: the tables do not depend on how the sample was cut into pieces.
+ * mirge_reads_parse_trim_qc   mirge_reads_parse_trim (trim may be NULL) that also adds the text's records to `qc` (NULL: exactly
+ *                     mirge_reads_parse_trim).  raw = every record's sequence line (a trailing '\r' stripped); trimmed = the read after the
+ *                     LAST modifier, once per record whatever count_per_modifier says, if it has at least min_len letters.  MIRGE_QC_FORM =
+ *                     pos (a lane per position) | read (a lane per read, the default): two forms of the text histogram, the same tables.
+ * mirge_qc_fetch      tables[2][MIRGE_QC_VIEW_WORDS = 92467] (raw, then trimmed), each view: [0..7] the scalars reads, bases, reads_with_N,
+ *                     empty_reads, qual_clamped, qual_length_mismatch, 0, 0; [8 ..] length[65536]; base[257][5] (letters A C G T N; row 256:
+ *                     positions of 256 and more); qual[257][94]; meanq[94]; gc[101]; first[257][5] (row = min(length, 256)).
+ *                     *has_qual = 1 when a FASTQ piece went in (else the quality tables are zero and mean nothing).
+ * mirge_qc_class_profile      out[n_samples][n_pass + 1][257][5][2]: per sample, class (the pass that annotated the read; n_pass: none),
+ *                     min(length, 256) and first letter (an empty read: N) the sum of the unique reads' counts and the number of unique
+ *                     reads with a count > 0. */
+typedef struct mirge_qc mirge_qc;
+int mirge_qc_create(mirge_ctx* ctx, mirge_qc** out);
+void mirge_qc_destroy(mirge_qc* qc);
+int mirge_reads_parse_trim_qc(mirge_ctx* ctx, const char* text, int64_t nbytes, int32_t format, int32_t min_len, const mirge_trim* trim,
+                              mirge_qc* qc, mirge_reads** out, int64_t* n_records);
+int mirge_qc_fetch(mirge_ctx* ctx, const mirge_qc* qc, int64_t* tables, int32_t* has_qual);
+int mirge_qc_class_profile(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, int32_t n_pass, int64_t* out);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

@@ -142,6 +142,11 @@ int mirge_trf_assign(mirge_ctx*, const mirge_reads*, const mirge_result*, int64_
 int mirge_trf_row_counts(mirge_ctx*, const mirge_reads*, const int64_t*, int64_t, uint32_t*);
 int mirge_trf_cluster(mirge_ctx*, const mirge_reads*, int64_t, const int64_t*, const int64_t*, const int32_t*, const double*, const int32_t*, int64_t, const double*,
     float*, float*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*);
+int mirge_qc_create(mirge_ctx*, mirge_qc**);
+void mirge_qc_destroy(mirge_qc*);
+int mirge_reads_parse_trim_qc(mirge_ctx*, const char*, int64_t, int32_t, int32_t, const mirge_trim*, mirge_qc*, mirge_reads**, int64_t*);
+int mirge_qc_fetch(mirge_ctx*, const mirge_qc*, int64_t*, int32_t*);
+int mirge_qc_class_profile(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, int64_t*);
 int mirge_ctx_timer_start(mirge_ctx*);
 int mirge_ctx_timer_stop(mirge_ctx*, double*);
 int mirge_ctx_profile_enable(mirge_ctx*, int32_t);
@@ -325,7 +330,7 @@ def _shutdown():
     then libraries, then contexts (a handle freed after its context is gone would crash at exit)."""
     objs = [r() for r in _live]
     objs = [o for o in objs if o is not None]
-    for kind in (CascadeResult, DeviceReads, DeviceLibrary, DeviceGenome, Context):
+    for kind in (CascadeResult, ReadQc, DeviceReads, DeviceLibrary, DeviceGenome, Context):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -477,7 +482,7 @@ class Context:
             # context's pool, and a handle destroyed after its context (a reference kept by a traceback, a cycle the collector
             # reaches late) would free into released memory
             objs = [o for o in (r() for r in _live) if o is not None and getattr(o, "ctx", None) is self]
-            for kind in (CascadeResult, DeviceReads, DeviceLibrary, DeviceGenome):
+            for kind in (CascadeResult, ReadQc, DeviceReads, DeviceLibrary, DeviceGenome):
                 for o in objs:
                     if isinstance(o, kind):
                         o.close()
@@ -701,6 +706,19 @@ class DeviceReads:
         return DeviceReads(ctx, h), int(nrec.value)
 
     @staticmethod
+    def parse_qc(ctx: Context, text, fmt: int, min_len: int, trim: Optional["MirgeTrim"], qc: Optional["ReadQc"]):
+        """``parse`` that also adds the text's records to ``qc`` (``mirge_reads_parse_trim_qc``, ``--read-qc``); ``qc`` None: exactly ``parse``"""
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(text, dtype=np.uint8)
+        h = C.c_void_p()
+        nrec = C.c_int64()
+        _check(load().mirge_reads_parse_trim_qc(ctx._h, buf if buf.size else None, buf.size, fmt, min_len, trim, None if qc is None else qc._h,
+                                                C.byref(h), C.byref(nrec)), "mirge_reads_parse_trim_qc")
+        if qc is not None:
+            qc.fed += 1
+        return DeviceReads(ctx, h), int(nrec.value)
+
+    @staticmethod
     def parse_umi(ctx: Context, text, fmt: int, min_len: int, trim: Optional["MirgeTrim"], umi: "MirgeUmi"):
         """``parse`` with the reference's UMI handling (``mirge_reads_parse_umi``) -> (raw INSERTS, records seen, the
         distinct UMI-tagged reads with their counts -- a collapse result -- or None without ``-udd``).  With ``-udd``
@@ -902,6 +920,53 @@ def kmer_correct_ratio_stats() -> list:
     if rounds < 0:
         _check(rounds, "mirge_kmer_correct_ratio_stats")
     return [{"above": int(out[2 * r]), "dominated": int(out[2 * r + 1])} for r in range(rounds)]
+
+
+QC_VIEW_WORDS = 92467  # MIRGE_QC_VIEW_WORDS of csrc/kernels_qc.hpp: the 64-bit words of one view's tables (mirge_qc_fetch)
+
+
+class ReadQc:
+    """The ``--read-qc`` accumulator of ONE sample (``mirge_qc``): the tables of the ``raw`` and the ``trimmed`` view on the device, fed by
+    ``DeviceReads.parse_qc`` piece by piece"""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _check(load().mirge_qc_create(ctx._h, C.byref(self._h)), "mirge_qc_create")
+        self.fed = 0  # pieces that went in
+        _track(self)
+
+    def reset(self):
+        """empty tables again (a sample whose text is parsed a second time from its start)"""
+        self.close()
+        _check(load().mirge_qc_create(self.ctx._h, C.byref(self._h)), "mirge_qc_create")
+        self.fed = 0
+
+    def fetch(self):
+        """-> (int64 [2][QC_VIEW_WORDS]: raw, trimmed, in the layout include/mirge_native.h documents; True when a FASTQ piece went in)"""
+        out = np.zeros((2, QC_VIEW_WORDS), dtype=np.int64)
+        has_q = C.c_int32()
+        _check(load().mirge_qc_fetch(self.ctx._h, self._h, out, C.byref(has_q)), "mirge_qc_fetch")
+        return out, bool(has_q.value)
+
+    def close(self):
+        if self._h:
+            load().mirge_qc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def qc_class_profile(ctx: "Context", uniq: "DeviceReads", res: "CascadeResult") -> np.ndarray:
+    """``mirge_qc_class_profile`` -> int64 [S][n_pass + 1][257][5][2]: per sample, class (pass; n_pass: unmapped), min(length, 256), first
+    letter (A C G T N) the raw reads and the unique reads with a count > 0"""
+    out = np.zeros((max(uniq.n_samples, 1), res.n_pass + 1, 257, 5, 2), dtype=np.int64)
+    _check(load().mirge_qc_class_profile(ctx._h, uniq._h, res._h, res.n_pass, out), "mirge_qc_class_profile")
+    return out
 
 
 class CascadeResult:

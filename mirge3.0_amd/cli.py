@@ -146,6 +146,11 @@ def parse_args(argv=None):
                          "<sample>.sam.gz and <sample>.bedgraph.gz (or .plus. / .minus.bedgraph.gz) in place of the plain files, each "
                          "with a block index <name>.gz.gzi; the decompressed bytes are those of the plain file (bigWig and BAM "
                          "outputs are untouched)")
+    ap.add_argument("--read-qc", dest="read_qc", action="store_true",
+                    help="per-sample read QC from the text the parse already holds on the device: <sample>.readqc.tsv (per-position "
+                         "quality and base composition, length, mean quality, GC and first-letter distributions of the raw and the "
+                         "trimmed reads; the length x first-letter profile of every annotation class) and readqc.summary.csv; not with "
+                         "-umi, -spl, -rr, --backend bowtie or a sharded run")
     ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "tight", "host"),
                     help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
                          "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
@@ -243,6 +248,10 @@ def parse_args(argv=None):
     if why:
         ap.error(why)
     args.adapter_auto = adapter_auto.wanted(args)
+    from . import readqc
+    why = readqc.refusal(args)
+    if why:
+        ap.error(why)
     if args.qiagenumi and not (args.adapters and args.adapters[0][0] == "back"):
         ap.error("--qiagenumi reads the UMI behind the 3' adapter: give it with -a (first)")
     args.bowtieVersion = "True"

@@ -900,18 +900,21 @@ def write_tcf(path, raw: "_ffi.DeviceReads", dictionary: "_ffi.DeviceReads" = No
         fo.write(FlatSeqs.join_columns([head, num, seqs], b"_\n\n"))
 
 
-def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None, name=None, timings: Dict[str, float] = None):
+def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None, name=None, timings: Dict[str, float] = None, qc=None):
     """One file's text -> (raw reads as the collapse takes them, records seen): parse, the modifier chain, the length
     filter and -- with ``umi`` -- the reference's UMI handling, all on the GPU (``mirge_reads_parse[_trim|_umi]``).
     With ``-udd`` also writes ``<name>_umiCounts.csv``.  ``text`` may be a ``GzipRecordStream``: its pieces are uploaded and
-    parsed one by one while the next ones inflate, and appended on the device (``mirge_reads_concat``: file order kept)."""
+    parsed one by one while the next ones inflate, and appended on the device (``mirge_reads_concat``: file order kept).
+    ``qc`` (``_ffi.ReadQc``, ``--read-qc``): the sample's accumulator, fed by every piece; not with ``umi``."""
+    if qc is not None and umi is not None:
+        raise RuntimeError("--read-qc: not together with -umi")
     if isinstance(text, (GzipRecordStream, TextRecordStream, ParallelGzipStream)):
         if umi is not None:  # the UMI routes look at the whole sample (a collapse inside): not streamed
             text = text.whole_text()
         else:
-            return _parse_stream(ctx, text, min_len, trim, timings)
+            return _parse_stream(ctx, text, min_len, trim, timings, qc)
     if umi is None:
-        return _ffi.DeviceReads.parse(ctx, text, 0, min_len, trim)
+        return _ffi.DeviceReads.parse_qc(ctx, text, 0, min_len, trim, qc) if qc is not None else _ffi.DeviceReads.parse(ctx, text, 0, min_len, trim)
     raw, n_rec, tagged = _ffi.DeviceReads.parse_umi(ctx, text, 0, min_len, trim, umi)
     if tagged is not None:
         if workDir is not None:
@@ -924,14 +927,17 @@ def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None,
     return raw, n_rec
 
 
-def _parse_stream(ctx: _ffi.Context, stream, min_len: int, trim, timings=None):
+def _parse_stream(ctx: _ffi.Context, stream, min_len: int, trim, timings=None, qc=None):
     try:
-        return _parse_stream_once(ctx, stream, min_len, trim, timings)
+        return _parse_stream_once(ctx, stream, min_len, trim, timings, qc)
     except GzRouteDeclined:  # not a file for the parallel inflater: everything again through zlib (what was parsed ahead is closed)
-        return _parse_stream_once(ctx, GzipRecordStream(stream.path), min_len, trim, timings)
+        if qc is not None:
+            qc.reset()  # (the pieces counted so far are counted again)
+        return _parse_stream_once(ctx, GzipRecordStream(stream.path), min_len, trim, timings, qc)
 
 
-def _parse_stream_once(ctx: _ffi.Context, stream, min_len: int, trim, timings=None):
+def _parse_stream_once(ctx: _ffi.Context, stream, min_len: int, trim, timings=None, qc=None):
+    parse = _ffi.DeviceReads.parse if qc is None else (lambda c, text, fmt, ml, tr: _ffi.DeviceReads.parse_qc(c, text, fmt, ml, tr, qc))
     parts, n_rec = [], 0
     t_wait = t_gpu = 0.0
     t = time.perf_counter()
@@ -941,9 +947,9 @@ def _parse_stream_once(ctx: _ffi.Context, stream, min_len: int, trim, timings=No
             t_wait += t1 - t
             if isinstance(item, tuple):  # not FASTQ: the whole text at once
                 data = unwrap_fasta(item[1]) if item[1][:1] == b">" else item[1]
-                r, n = _ffi.DeviceReads.parse(ctx, data, 0, min_len, trim)
+                r, n = parse(ctx, data, 0, min_len, trim)
             else:
-                r, n = _ffi.DeviceReads.parse(ctx, item, 1, min_len, trim)
+                r, n = parse(ctx, item, 1, min_len, trim)
             parts.append(r)
             n_rec += n
             t = time.perf_counter()

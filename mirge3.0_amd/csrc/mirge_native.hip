@@ -59,3 +59,4 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_adapter.hpp"
 #include "native_cov.hpp"
 #include "native_bw.hpp"
+#include "native_qc.hpp"

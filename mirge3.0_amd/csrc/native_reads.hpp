@@ -351,6 +351,7 @@ struct ParseJob {
     int64_t* s2start = nullptr;
     int32_t* s2len = nullptr;
     bool line_flags_checked = false;
+    bool want_qual = false;  // --read-qc: the quality lines of a FASTQ text are marked even when nothing trims
     ~ParseJob() {
         if (!c) return;
         (void)hipStreamSynchronize(c->stream);
@@ -423,8 +424,8 @@ static int parse_lines(ParseJob& J, const char* text, int64_t nbytes, const Trim
     if (trimming) {
         CHECK(dalloc(c, &J.lstart, (size_t)J.n_raw));
         CHECK(dalloc(c, &J.lend, (size_t)J.n_raw));
-        if (format == 1) { CHECK(dalloc(c, &J.qstart, (size_t)J.n_raw)); CHECK(dalloc(c, &J.qend, (size_t)J.n_raw)); }
     }
+    if (format == 1 && (trimming || J.want_qual)) { CHECK(dalloc(c, &J.qstart, (size_t)J.n_raw)); CHECK(dalloc(c, &J.qend, (size_t)J.n_raw)); }
     hipLaunchKernelGGL(k_nl_mark, dim3(ntile), dim3(MIRGE_BLOCK), 0, c->stream, J.dtext, n, J.tile_off, period, sphase,
                        trimming ? J.lstart : J.dstart, trimming ? J.lend : J.dend, (uint64_t)J.n_raw, (int)format, J.lflags, J.qstart, J.qend);
     if (trimming) {
@@ -578,9 +579,13 @@ extern "C" int mirge_collapse(mirge_ctx* c, const mirge_reads* raw, const int32_
 static int umi_check_layout(const std::string& who, int32_t front, int32_t back);  // native_umi.hpp
 static int umi_cluster_device(mirge_ctx* c, const mirge_reads* T, int32_t front, int32_t back, uint8_t* d_founder, int64_t* n_founders);
 
-extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len,
-                                     const mirge_trim* trim, const mirge_umi* umi, mirge_reads** out, int64_t* n_records,
-                                     mirge_reads** tagged_out) {
+// --read-qc (native_qc.hpp): the accumulator of a sample, fed from the ParseJob between parse_lines and parse_pack
+struct mirge_qc;
+static int qc_accumulate(ParseJob& J, const TrimOpts* topt, int32_t min_len, mirge_qc* q);
+
+// the one implementation behind mirge_reads_parse, _parse_trim, _parse_umi (qc == nullptr) and _parse_trim_qc
+static int reads_parse_impl(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len, const mirge_trim* trim,
+                            const mirge_umi* umi, mirge_reads** out, int64_t* n_records, mirge_reads** tagged_out, mirge_qc* qc) {
     if (!c || !out || nbytes < 0 || (nbytes > 0 && !text) || format < 0 || format > 3)
         return fail(-1, "mirge_reads_parse: bad argument");
     if (tagged_out) *tagged_out = nullptr;
@@ -613,11 +618,12 @@ extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nby
     }
     if (nbytes == 0) { *out = R.release(); return 0; }
     ParseJob J;
-    J.c = c; J.format = format;
+    J.c = c; J.format = format; J.want_qual = qc != nullptr;
     // (the first of the stripped line ends closed the last line with a letter in it; the others closed empty lines)
     int rc = parse_lines(J, text, nbytes, trim ? &topt : nullptr, umi, format == 3 ? 0 : std::max(0, tail_line_ends - 1));
     if (rc) { mirge_reads_destroy(R.release()); return rc; }
     if (n_records) *n_records = J.n_raw;
+    if (qc && (rc = qc_accumulate(J, trim ? &topt : nullptr, min_len, qc))) { mirge_reads_destroy(R.release()); return rc; }
     const int32_t f = umi ? umi->front : 0, b = umi ? umi->back : 0;
     // the worker's own length test (digest.py:348 / :360 / :368): on the read as the modifiers left it, with -umi (no
     // --qiagenumi) on what UMIParser leaves of it, max(0, len - f - b)
@@ -695,13 +701,18 @@ extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nby
     return 0;
 }
 
+extern "C" int mirge_reads_parse_umi(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len,
+                                     const mirge_trim* trim, const mirge_umi* umi, mirge_reads** out, int64_t* n_records,
+                                     mirge_reads** tagged_out) {
+    return reads_parse_impl(c, text, nbytes, format, min_len, trim, umi, out, n_records, tagged_out, nullptr);
+}
 extern "C" int mirge_reads_parse_trim(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len,
                                       const mirge_trim* trim, mirge_reads** out, int64_t* n_records) {
-    return mirge_reads_parse_umi(c, text, nbytes, format, min_len, trim, nullptr, out, n_records, nullptr);
+    return reads_parse_impl(c, text, nbytes, format, min_len, trim, nullptr, out, n_records, nullptr, nullptr);
 }
 extern "C" int mirge_reads_parse(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len,
                                  mirge_reads** out, int64_t* n_records) {
-    return mirge_reads_parse_umi(c, text, nbytes, format, min_len, nullptr, nullptr, out, n_records, nullptr);
+    return reads_parse_impl(c, text, nbytes, format, min_len, nullptr, nullptr, out, n_records, nullptr, nullptr);
 }
 
 

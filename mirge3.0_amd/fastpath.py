@@ -182,6 +182,10 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
         if kmer_ratio:
             say(f"NOTE: --kmer-ratio {kmer_ratio} with -ai / -gff: a true variant one letter from a k-mer at least {kmer_ratio} times as abundant "
                 "(a minor member of a miRNA family below that share of its sibling) is corrected into it")
+    read_qc = bool(getattr(args, "read_qc", False))  # --read-qc: one accumulator per sample, fed by every piece of its text
+    if read_qc and umi is not None:
+        raise RuntimeError("--read-qc: not together with -umi")
+    qc_handles = []
     t_read = t_parse = 0.0
     from . import collapse as _collapse
     del _collapse.GZ_LOG[:]
@@ -192,7 +196,9 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
         text = next(texts)
         t_read += time.perf_counter() - t
         t1 = time.perf_counter()
-        raw, n_rec = parse_sample(ctx, text, min_len, trim, umi, workDir, name, timings=gz_tm)
+        if read_qc:
+            qc_handles.append(_ffi.ReadQc(ctx))
+        raw, n_rec = parse_sample(ctx, text, min_len, trim, umi, workDir, name, timings=gz_tm, qc=qc_handles[-1] if read_qc else None)
         del text
         t_parse += time.perf_counter() - t1
         sampleReadCounts[name], trimmedReadCounts[name] = n_rec, len(raw)
@@ -253,6 +259,11 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
                            list(base_names), sampleReadCounts, trimmedReadCounts, trimmedReadCountsUnique,
                            float(args.crThreshold), bool(args.spikeIn), workDir)
     tm["join_tables_s"] = time.perf_counter() - t
+    if read_qc:  # <sample>.readqc.tsv, readqc.summary.csv, a line per sample: the class profile from the dictionary and the cascade's result
+        from . import readqc
+        t = time.perf_counter()
+        readqc.write_all(ctx, workDir, list(base_names), qc_handles, uniq, res, say)
+        tm["read_qc_s"] = time.perf_counter() - t
     outlog.close()
     out = reports(args, workDir, ref_db, base_names, casc, uniq, res, out, merges, counts, first, tm)
     tm["total_s"] = time.perf_counter() - t0
