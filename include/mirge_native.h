@@ -702,6 +702,28 @@ int mirge_reads_parse_trim_qc(mirge_ctx* ctx, const char* text, int64_t nbytes, 
 int mirge_qc_fetch(mirge_ctx* ctx, const mirge_qc* qc, int64_t* tables, int32_t* has_qual);
 int mirge_qc_class_profile(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, int32_t n_pass, int64_t* out);
 
+/* ---- the trimmed reads of a sample as FASTQ / FASTA / one sequence per line (--trimmed-out; mirge3_amd/trimmed_out.py holds the specification)
+ * mirge_fqout         the writer of ONE sample, alive across the pieces of a streamed sample: `path` (written as `<path>.tmp`), and with
+ *                     gzi_path != NULL `path` is a BGZF file (mirge3_amd/bgzf.py) and gzi_path its block index; block_bytes <= 0:
+ *                     MIRGE_BGZF_BLOCK_BYTES.  A wrong MIRGE_BGZF_BLOCK_BYTES / MIRGE_BGZF_DEFLATE fails the create.
+ * mirge_reads_parse_trim_out  mirge_reads_parse_trim_qc (qc may be NULL) that also appends the piece's part of the stream S to `fq` (NULL:
+ *                     exactly mirge_reads_parse_trim_qc): in file order every record whose read after the LAST modifier has at least min_len
+ *                     letters, as  H \n S \n + \n Q \n  (format 1),  H \n S \n  (2) or  S \n  (3); H the header line and S the read
+ *                     verbatim, Q the same slice of the quality line, a trailing '\r' stripped from each.  A quality line that is not as long
+ *                     as its sequence line fails the call (`--trimmed-out: ...`) before the piece writes anything; a piece writes only after
+ *                     its reads were packed without error.  A failed call leaves no file of the sample, and the writer takes no more pieces.
+ *                     S does not depend on how the sample was cut into pieces, nor on MIRGE_FQ_CHUNK_BYTES (default 32 MiB) or
+ *                     MIRGE_FQ_TILE_BYTES (a multiple of 16, at most 16384).  BGZF: member b holds S[b * B, (b + 1) * B).
+ * mirge_fqout_finish  the last, short member, the EOF block and the .gzi (BGZF); the files are renamed to their names.
+ *                     stats_out[8]: records, written, stream bytes, file bytes, members, members stored, fixed, dynamic.
+ * mirge_fqout_destroy without finish: the .tmp files are removed. */
+typedef struct mirge_fqout mirge_fqout;
+int mirge_fqout_create(mirge_ctx* ctx, const char* path, const char* gzi_path, int64_t block_bytes, mirge_fqout** out);
+int mirge_reads_parse_trim_out(mirge_ctx* ctx, const char* text, int64_t nbytes, int32_t format, int32_t min_len, const mirge_trim* trim,
+                               mirge_qc* qc, mirge_fqout* fq, mirge_reads** out, int64_t* n_records);
+int mirge_fqout_finish(mirge_ctx* ctx, mirge_fqout* fq, int64_t* stats_out);
+void mirge_fqout_destroy(mirge_fqout* fq);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

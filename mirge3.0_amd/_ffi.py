@@ -147,6 +147,10 @@ void mirge_qc_destroy(mirge_qc*);
 int mirge_reads_parse_trim_qc(mirge_ctx*, const char*, int64_t, int32_t, int32_t, const mirge_trim*, mirge_qc*, mirge_reads**, int64_t*);
 int mirge_qc_fetch(mirge_ctx*, const mirge_qc*, int64_t*, int32_t*);
 int mirge_qc_class_profile(mirge_ctx*, const mirge_reads*, const mirge_result*, int32_t, int64_t*);
+int mirge_fqout_create(mirge_ctx*, const char*, const char*, int64_t, mirge_fqout**);
+int mirge_reads_parse_trim_out(mirge_ctx*, const char*, int64_t, int32_t, int32_t, const mirge_trim*, mirge_qc*, mirge_fqout*, mirge_reads**, int64_t*);
+int mirge_fqout_finish(mirge_ctx*, mirge_fqout*, int64_t*);
+void mirge_fqout_destroy(mirge_fqout*);
 int mirge_ctx_timer_start(mirge_ctx*);
 int mirge_ctx_timer_stop(mirge_ctx*, double*);
 int mirge_ctx_profile_enable(mirge_ctx*, int32_t);
@@ -330,7 +334,7 @@ def _shutdown():
     then libraries, then contexts (a handle freed after its context is gone would crash at exit)."""
     objs = [r() for r in _live]
     objs = [o for o in objs if o is not None]
-    for kind in (CascadeResult, ReadQc, DeviceReads, DeviceLibrary, DeviceGenome, Context):
+    for kind in (CascadeResult, ReadQc, TrimmedOut, DeviceReads, DeviceLibrary, DeviceGenome, Context):
         for o in objs:
             if isinstance(o, kind):
                 try:
@@ -482,7 +486,7 @@ class Context:
             # context's pool, and a handle destroyed after its context (a reference kept by a traceback, a cycle the collector
             # reaches late) would free into released memory
             objs = [o for o in (r() for r in _live) if o is not None and getattr(o, "ctx", None) is self]
-            for kind in (CascadeResult, ReadQc, DeviceReads, DeviceLibrary, DeviceGenome):
+            for kind in (CascadeResult, ReadQc, TrimmedOut, DeviceReads, DeviceLibrary, DeviceGenome):
                 for o in objs:
                     if isinstance(o, kind):
                         o.close()
@@ -714,6 +718,23 @@ class DeviceReads:
         nrec = C.c_int64()
         _check(load().mirge_reads_parse_trim_qc(ctx._h, buf if buf.size else None, buf.size, fmt, min_len, trim, None if qc is None else qc._h,
                                                 C.byref(h), C.byref(nrec)), "mirge_reads_parse_trim_qc")
+        if qc is not None:
+            qc.fed += 1
+        return DeviceReads(ctx, h), int(nrec.value)
+
+    @staticmethod
+    def parse_out(ctx: Context, text, fmt: int, min_len: int, trim: Optional["MirgeTrim"], qc: Optional["ReadQc"], out: Optional["TrimmedOut"]):
+        """``parse_qc`` that also appends the text's trimmed records to ``out`` (``mirge_reads_parse_trim_out``, ``--trimmed-out``); ``out`` None:
+        exactly ``parse_qc``.  A call that fails leaves no file of the sample."""
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(text, dtype=np.uint8)
+        h = C.c_void_p()
+        nrec = C.c_int64()
+        fq = None
+        if out is not None:
+            fq = out.handle_for(fmt or (3 if not buf.size else (1 if buf[0] == 64 else (2 if buf[0] == 62 else 3))))
+        _check(load().mirge_reads_parse_trim_out(ctx._h, buf if buf.size else None, buf.size, fmt, min_len, trim, None if qc is None else qc._h, fq,
+                                                 C.byref(h), C.byref(nrec)), "mirge_reads_parse_trim_out")
         if qc is not None:
             qc.fed += 1
         return DeviceReads(ctx, h), int(nrec.value)
@@ -952,6 +973,56 @@ class ReadQc:
     def close(self):
         if self._h:
             load().mirge_qc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TrimmedOut:
+    """The ``--trimmed-out`` writer of ONE sample (``mirge_fqout``), fed by ``DeviceReads.parse_out`` piece by piece.  The file's name depends
+    on the input format (``trimmed_out.file_name``), which the first piece tells: the native writer is created then, in ``directory``.
+    ``mode``: ``plain`` | ``gz`` (BGZF with a ``.gzi``); ``block_bytes`` <= 0: MIRGE_BGZF_BLOCK_BYTES."""
+    STATS = ("records", "written", "stream_bytes", "file_bytes", "members", "stored", "fixed", "dynamic")
+
+    def __init__(self, ctx: Context, directory, sample: str, mode: str = "plain", block_bytes: int = 0):
+        if mode not in ("plain", "gz"):
+            raise ValueError(f"mode={mode!r}: plain or gz")
+        self.ctx, self.directory, self.sample, self.mode, self.block_bytes = ctx, str(directory), str(sample), mode, int(block_bytes)
+        self._h = C.c_void_p()
+        self.fmt = 0
+        self.path = None  # the file's final name, once known
+        _track(self)
+
+    def handle_for(self, fmt: int):
+        """the native writer, created for input format ``fmt`` (1 FASTQ, 2 FASTA, 3 one sequence per line) on first use"""
+        if not self._h:
+            from . import trimmed_out
+            self.fmt = int(fmt)
+            self.path = os.path.join(self.directory, trimmed_out.file_name(self.sample, self.fmt, self.mode))
+            gzi = (self.path + ".gzi").encode() if self.mode == "gz" else None
+            _check(load().mirge_fqout_create(self.ctx._h, self.path.encode(), gzi, self.block_bytes, C.byref(self._h)), "mirge_fqout_create")
+        return self._h
+
+    def reset(self):
+        """nothing written yet again: the files reopened, the offsets 0 (a sample whose text is parsed a second time from its start)"""
+        self.close()
+        self.fmt, self.path = 0, None
+
+    def finish(self) -> dict:
+        """the rest of the stream, the files renamed to their names -> STATS as a dict (plus ``path``); a sample without a piece: an empty file"""
+        out = np.zeros(8, dtype=np.int64)
+        _check(load().mirge_fqout_finish(self.ctx._h, self.handle_for(self.fmt or 3), out), "mirge_fqout_finish")
+        self.close()
+        return {**{k: int(v) for k, v in zip(self.STATS, out)}, "path": self.path}
+
+    def close(self):
+        """without ``finish``: the ``.tmp`` files are removed"""
+        if self._h:
+            load().mirge_fqout_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -151,6 +151,13 @@ def parse_args(argv=None):
                          "quality and base composition, length, mean quality, GC and first-letter distributions of the raw and the "
                          "trimmed reads; the length x first-letter profile of every annotation class) and readqc.summary.csv; not with "
                          "-umi, -spl, -rr, --backend bowtie or a sharded run")
+    ap.add_argument("--trimmed-out", dest="trimmed_out", nargs="?", const="plain", default=None, choices=("plain", "gz"),
+                    help="write every sample's reads as the modifier chain leaves them (-a, -g, -q, -u, --trim-n, -a auto), formatted on the "
+                         "device from the text the parse holds there: in file order every record whose read after the LAST modifier has at "
+                         "least --minimum-length letters, whatever --trim-count says, with its header and the same slice of its qualities: "
+                         "<sample>.trimmed.fastq (.trimmed.fasta / .trimmed.txt for FASTA / one-sequence-per-line input); gz: the same "
+                         "bytes as BGZF, deflated on the device, <name>.gz with a block index <name>.gz.gzi.  With --kmer-correct the file "
+                         "holds the reads BEFORE correction.  Not with -umi, -spl, -rr, --backend bowtie or a sharded run")
     ap.add_argument("--bam-deflate", dest="bam_deflate", default=None, choices=("device", "dynamic", "tight", "host"),
                     help="with --sorted-bam: how the BGZF blocks are deflated, for this run and ahead of MIRGE_BAM_DEFLATE.  device (the "
                          "default): on the device with the fixed Huffman code; dynamic: on the device, per block also a Huffman code of "
@@ -250,6 +257,10 @@ def parse_args(argv=None):
     args.adapter_auto = adapter_auto.wanted(args)
     from . import readqc
     why = readqc.refusal(args)
+    if why:
+        ap.error(why)
+    from . import trimmed_out
+    why = trimmed_out.refusal(args)
     if why:
         ap.error(why)
     if args.qiagenumi and not (args.adapters and args.adapters[0][0] == "back"):

@@ -900,20 +900,25 @@ def write_tcf(path, raw: "_ffi.DeviceReads", dictionary: "_ffi.DeviceReads" = No
         fo.write(FlatSeqs.join_columns([head, num, seqs], b"_\n\n"))
 
 
-def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None, name=None, timings: Dict[str, float] = None, qc=None):
+def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None, name=None, timings: Dict[str, float] = None, qc=None, out=None):
     """One file's text -> (raw reads as the collapse takes them, records seen): parse, the modifier chain, the length
     filter and -- with ``umi`` -- the reference's UMI handling, all on the GPU (``mirge_reads_parse[_trim|_umi]``).
     With ``-udd`` also writes ``<name>_umiCounts.csv``.  ``text`` may be a ``GzipRecordStream``: its pieces are uploaded and
     parsed one by one while the next ones inflate, and appended on the device (``mirge_reads_concat``: file order kept).
-    ``qc`` (``_ffi.ReadQc``, ``--read-qc``): the sample's accumulator, fed by every piece; not with ``umi``."""
+    ``qc`` (``_ffi.ReadQc``, ``--read-qc``): the sample's accumulator, fed by every piece; not with ``umi``.
+    ``out`` (``_ffi.TrimmedOut``, ``--trimmed-out``): the sample's writer, fed by every piece (the caller finishes it); not with ``umi``."""
     if qc is not None and umi is not None:
         raise RuntimeError("--read-qc: not together with -umi")
+    if out is not None and umi is not None:
+        raise RuntimeError("--trimmed-out: not together with -umi")
     if isinstance(text, (GzipRecordStream, TextRecordStream, ParallelGzipStream)):
         if umi is not None:  # the UMI routes look at the whole sample (a collapse inside): not streamed
             text = text.whole_text()
         else:
-            return _parse_stream(ctx, text, min_len, trim, timings, qc)
+            return _parse_stream(ctx, text, min_len, trim, timings, qc, out)
     if umi is None:
+        if out is not None:
+            return _ffi.DeviceReads.parse_out(ctx, text, 0, min_len, trim, qc, out)
         return _ffi.DeviceReads.parse_qc(ctx, text, 0, min_len, trim, qc) if qc is not None else _ffi.DeviceReads.parse(ctx, text, 0, min_len, trim)
     raw, n_rec, tagged = _ffi.DeviceReads.parse_umi(ctx, text, 0, min_len, trim, umi)
     if tagged is not None:
@@ -927,17 +932,22 @@ def parse_sample(ctx: _ffi.Context, text, min_len: int, trim, umi, workDir=None,
     return raw, n_rec
 
 
-def _parse_stream(ctx: _ffi.Context, stream, min_len: int, trim, timings=None, qc=None):
+def _parse_stream(ctx: _ffi.Context, stream, min_len: int, trim, timings=None, qc=None, out=None):
     try:
-        return _parse_stream_once(ctx, stream, min_len, trim, timings, qc)
+        return _parse_stream_once(ctx, stream, min_len, trim, timings, qc, out)
     except GzRouteDeclined:  # not a file for the parallel inflater: everything again through zlib (what was parsed ahead is closed)
         if qc is not None:
             qc.reset()  # (the pieces counted so far are counted again)
-        return _parse_stream_once(ctx, GzipRecordStream(stream.path), min_len, trim, timings, qc)
+        if out is not None:
+            out.reset()  # (the pieces written so far are written again, from offset 0)
+        return _parse_stream_once(ctx, GzipRecordStream(stream.path), min_len, trim, timings, qc, out)
 
 
-def _parse_stream_once(ctx: _ffi.Context, stream, min_len: int, trim, timings=None, qc=None):
-    parse = _ffi.DeviceReads.parse if qc is None else (lambda c, text, fmt, ml, tr: _ffi.DeviceReads.parse_qc(c, text, fmt, ml, tr, qc))
+def _parse_stream_once(ctx: _ffi.Context, stream, min_len: int, trim, timings=None, qc=None, out=None):
+    if out is not None:
+        parse = lambda c, text, fmt, ml, tr: _ffi.DeviceReads.parse_out(c, text, fmt, ml, tr, qc, out)
+    else:
+        parse = _ffi.DeviceReads.parse if qc is None else (lambda c, text, fmt, ml, tr: _ffi.DeviceReads.parse_qc(c, text, fmt, ml, tr, qc))
     parts, n_rec = [], 0
     t_wait = t_gpu = 0.0
     t = time.perf_counter()

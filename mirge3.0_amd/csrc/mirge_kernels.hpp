@@ -58,3 +58,4 @@ __device__ __forceinline__ void load_read(const GroupView<W>& g, uint32_t i, Mir
 #include "kernels_cov.hpp"
 #include "kernels_bw.hpp"
 #include "kernels_qc.hpp"
+#include "kernels_fq.hpp"

@@ -60,3 +60,4 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_cov.hpp"
 #include "native_bw.hpp"
 #include "native_qc.hpp"
+#include "native_fq.hpp"

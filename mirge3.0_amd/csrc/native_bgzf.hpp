@@ -60,8 +60,16 @@ struct BgzfSink {
     // The streams, one behind the other, in chunks of chunk_bytes rounded down to whole blocks (one block at least).
     // fill(s, at, n, dst, &text): queue the production of bytes [at, at + n) of stream s somewhere in dst[0 .. n + 32) (16-aligned) and
     // say where in `text`.  Behind run() every stream's .gz ends with the EOF block and its .gzi is written; nothing is committed.
+    // run = chunks (the members of bytes [0, bytes) of every stream) + close (the EOF blocks and the indexes).  A stream that arrives in parts
+    // (`--trimmed-out`: native_fq.hpp) calls chunks once per part, with `bytes` = the part's length, a multiple of the block size except for the
+    // last part, and `base` = the stream offset of the part's first byte: `at` counts within the part, the index holds stream offsets.
     template <class Fill>
     int run(BgzfStream* const* streams, int n_streams, size_t chunk_bytes, Fill fill) {
+        CHECK(chunks(streams, n_streams, chunk_bytes, 0ull, fill));
+        return close(streams, n_streams);
+    }
+    template <class Fill>
+    int chunks(BgzfStream* const* streams, int n_streams, size_t chunk_bytes, unsigned long long base, Fill fill) {
         mirge_ctx* const c = scope.c;
         struct Chunk { int s; unsigned long long at; uint32_t n; };
         unsigned long long longest = 0;
@@ -146,7 +154,7 @@ struct BgzfSink {
                     total = joined.size(); src = joined.data();
                 }
                 for (size_t b = 0; b < nb; b++) {
-                    if (st.members) { st.index.push_back(st.file_at + at[b]); st.index.push_back(k.at + (unsigned long long)b * block); }
+                    if (st.members) { st.index.push_back(st.file_at + at[b]); st.index.push_back(base + k.at + (unsigned long long)b * block); }
                     st.members++;
                     const uint32_t btype = (src[at[b] + 18] >> 1) & 3u;
                     if (btype < 3u) st.forms[btype]++;
@@ -157,6 +165,9 @@ struct BgzfSink {
             };
             CHECK(pipe.run(plan.size(), queue, take));
         }
+        return 0;
+    }
+    int close(BgzfStream* const* streams, int n_streams) {
         for (int s = 0; s < n_streams; s++) {
             BgzfStream& st = *streams[s];
             CHECK(st.gz.put(kBgzfEofBlock, sizeof(kBgzfEofBlock), st.file_at));

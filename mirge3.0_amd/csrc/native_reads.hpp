@@ -351,7 +351,7 @@ struct ParseJob {
     int64_t* s2start = nullptr;
     int32_t* s2len = nullptr;
     bool line_flags_checked = false;
-    bool want_qual = false;  // --read-qc: the quality lines of a FASTQ text are marked even when nothing trims
+    bool want_qual = false;  // --read-qc, --trimmed-out: the quality lines of a FASTQ text are marked even when nothing trims
     ~ParseJob() {
         if (!c) return;
         (void)hipStreamSynchronize(c->stream);
@@ -583,9 +583,19 @@ static int umi_cluster_device(mirge_ctx* c, const mirge_reads* T, int32_t front,
 struct mirge_qc;
 static int qc_accumulate(ParseJob& J, const TrimOpts* topt, int32_t min_len, mirge_qc* q);
 
-// the one implementation behind mirge_reads_parse, _parse_trim, _parse_umi (qc == nullptr) and _parse_trim_qc
+// --trimmed-out (native_fq.hpp): the writer of a sample; a piece is measured between parse_lines and parse_pack and written behind a
+// parse_pack that succeeded
+struct mirge_fqout;
+struct FqPiece;
+static void fq_piece_free(FqPiece* P);
+static int fq_measure(ParseJob& J, const TrimOpts* topt, int32_t min_len, mirge_fqout* f, FqPiece** piece);
+static int fq_emit(ParseJob& J, mirge_fqout* f, FqPiece* piece);
+
+// the one implementation behind mirge_reads_parse, _parse_trim, _parse_umi (qc == fq == nullptr), _parse_trim_qc (fq == nullptr) and _parse_trim_out
 static int reads_parse_impl(mirge_ctx* c, const char* text, int64_t nbytes, int32_t format, int32_t min_len, const mirge_trim* trim,
-                            const mirge_umi* umi, mirge_reads** out, int64_t* n_records, mirge_reads** tagged_out, mirge_qc* qc) {
+                            const mirge_umi* umi, mirge_reads** out, int64_t* n_records, mirge_reads** tagged_out, mirge_qc* qc,
+                            mirge_fqout* fq = nullptr) {
+    if (fq && umi) return fail(-1, "mirge_reads_parse: --trimmed-out is not written on the UMI routes");
     if (!c || !out || nbytes < 0 || (nbytes > 0 && !text) || format < 0 || format > 3)
         return fail(-1, "mirge_reads_parse: bad argument");
     if (tagged_out) *tagged_out = nullptr;
@@ -618,12 +628,19 @@ static int reads_parse_impl(mirge_ctx* c, const char* text, int64_t nbytes, int3
     }
     if (nbytes == 0) { *out = R.release(); return 0; }
     ParseJob J;
-    J.c = c; J.format = format; J.want_qual = qc != nullptr;
+    J.c = c; J.format = format; J.want_qual = qc != nullptr || fq != nullptr;
+    std::unique_ptr<FqPiece, void (*)(FqPiece*)> piece(nullptr, fq_piece_free);  // (behind J: its blocks go back before J's)
     // (the first of the stripped line ends closed the last line with a letter in it; the others closed empty lines)
     int rc = parse_lines(J, text, nbytes, trim ? &topt : nullptr, umi, format == 3 ? 0 : std::max(0, tail_line_ends - 1));
     if (rc) { mirge_reads_destroy(R.release()); return rc; }
     if (n_records) *n_records = J.n_raw;
     if (qc && (rc = qc_accumulate(J, trim ? &topt : nullptr, min_len, qc))) { mirge_reads_destroy(R.release()); return rc; }
+    if (fq) {
+        FqPiece* p = nullptr;
+        rc = fq_measure(J, trim ? &topt : nullptr, min_len, fq, &p);
+        piece.reset(p);
+        if (rc) { mirge_reads_destroy(R.release()); return rc; }
+    }
     const int32_t f = umi ? umi->front : 0, b = umi ? umi->back : 0;
     // the worker's own length test (digest.py:348 / :360 / :368): on the read as the modifiers left it, with -umi (no
     // --qiagenumi) on what UMIParser leaves of it, max(0, len - f - b)
@@ -632,6 +649,7 @@ static int reads_parse_impl(mirge_ctx* c, const char* text, int64_t nbytes, int3
         // counts add up: slicing every counted read == slicing the keys of the merged dictionary (digest.py:164-181)
         const SliceOpts so{pre, min_len, f, b};
         rc = parse_pack(J, J.dstart, J.dend, J.s2start, J.s2len, J.n_seq, so, R.get(), nullptr);
+        if (rc == 0 && fq) rc = fq_emit(J, fq, piece.get());
         if (rc) { mirge_reads_destroy(R.release()); return rc; }
         *out = R.release();
         return 0;

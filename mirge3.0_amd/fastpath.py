@@ -186,6 +186,9 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
     if read_qc and umi is not None:
         raise RuntimeError("--read-qc: not together with -umi")
     qc_handles = []
+    trimmed_mode = getattr(args, "trimmed_out", None)  # --trimmed-out: one writer per sample, fed by every piece of its text
+    if trimmed_mode and umi is not None:
+        raise RuntimeError("--trimmed-out: not together with -umi")
     t_read = t_parse = 0.0
     from . import collapse as _collapse
     del _collapse.GZ_LOG[:]
@@ -198,9 +201,20 @@ def run(args, files: List[str], base_names: List[str], workDir, ref_db: str, tim
         t1 = time.perf_counter()
         if read_qc:
             qc_handles.append(_ffi.ReadQc(ctx))
-        raw, n_rec = parse_sample(ctx, text, min_len, trim, umi, workDir, name, timings=gz_tm, qc=qc_handles[-1] if read_qc else None)
+        writer = _ffi.TrimmedOut(ctx, workDir, name, trimmed_mode) if trimmed_mode else None
+        try:
+            raw, n_rec = parse_sample(ctx, text, min_len, trim, umi, workDir, name, timings=gz_tm, qc=qc_handles[-1] if read_qc else None, out=writer)
+        except BaseException:
+            if writer is not None:
+                writer.close()  # (a failed parse: no trimmed file of this sample)
+            raise
         del text
         t_parse += time.perf_counter() - t1
+        if writer is not None:  # the parse has ended without error: the last member, the index, the files under their names
+            from . import trimmed_out
+            t_w = time.perf_counter()
+            say(trimmed_out.log_line(name, writer.finish(), trimmed_mode))
+            tm["trimmed_out_s"] = tm.get("trimmed_out_s", 0.0) + time.perf_counter() - t_w
         sampleReadCounts[name], trimmedReadCounts[name] = n_rec, len(raw)
         if kmer is not None:  # the sample's dictionary, corrected on the device, stands for its reads from here on
             outlog.flush()
