@@ -724,6 +724,29 @@ int mirge_reads_parse_trim_out(mirge_ctx* ctx, const char* text, int64_t nbytes,
 int mirge_fqout_finish(mirge_ctx* ctx, mirge_fqout* fq, int64_t* stats_out);
 void mirge_fqout_destroy(mirge_fqout* fq);
 
+/* ---- unannotated reads' nearest hairpin by edit distance (--unmapped-nearest; mirge3_amd/nearest.py holds the specification)
+ * mirge_nearest_scan  queries q[n_q] and targets t[n_t] as ASCII + offsets (n + 1 each).  For EVERY query: D (the smallest unit-cost edit
+ *                     distance to a non-empty substring of a target; -1 for a query shorter than 12 or longer than 64 letters, or when
+ *                     no target has a base), the target of lowest index that reaches it, there the smallest end e and for it the largest
+ *                     start s (0-based, h[s:e]); hairpin = s = e = -1 where D = -1.  No K and no cap.  Letters match iff equal and one
+ *                     of A C G T.  The kernels are the run's.  Limits: 2^24 targets, fewer than 2^32 - 16 target bases in all,
+ *                     fewer than 2^31 - 16 queries.  MIRGE_NEAR_CHUNK_BASES (1 .. 4096, default 4096): bases per workgroup's run of
+ *                     whole targets (a longer target is a run of its own); MIRGE_NEAR_FORCE64=1: every query in the 64-bit instance.
+ *                     Neither changes a result.
+ * mirge_nearest_unmapped  the same over the rows of `uniq` that `res` left at MIRGE_NO_PASS and that are 12 .. 64 nt long; kept are the
+ *                     rows with D <= min(K, length / 8), 1 <= K <= 8.  mirge_nearest_count / _fetch: the kept rows in ascending handle
+ *                     index: row, D, hairpin, s, e.  mirge_nearest_stats: stats_out[5] = unannotated rows, of them too short, too long,
+ *                     considered, kept. */
+typedef struct mirge_nearest mirge_nearest;
+int mirge_nearest_scan(mirge_ctx* ctx, const char* q_text, const int64_t* q_off, int64_t n_q, const char* t_text, const int64_t* t_off,
+                       int64_t n_t, int32_t* dist, int32_t* hairpin, int32_t* start, int32_t* end);
+int mirge_nearest_unmapped(mirge_ctx* ctx, const mirge_reads* uniq, const mirge_result* res, const char* t_text, const int64_t* t_off,
+                           int64_t n_t, int32_t K, mirge_nearest** out);
+int64_t mirge_nearest_count(const mirge_nearest* hits);
+int mirge_nearest_fetch(const mirge_nearest* hits, uint32_t* row, int32_t* dist, int32_t* hairpin, int32_t* start, int32_t* end);
+int mirge_nearest_stats(const mirge_nearest* hits, int64_t* stats_out);
+void mirge_nearest_destroy(mirge_nearest* hits);
+
 /* ---- measurement (bench.py): HIP events on the ctx stream ---- */
 int mirge_ctx_timer_start(mirge_ctx* ctx);
 int mirge_ctx_timer_stop(mirge_ctx* ctx, double* ms_out);

@@ -151,6 +151,12 @@ int mirge_fqout_create(mirge_ctx*, const char*, const char*, int64_t, mirge_fqou
 int mirge_reads_parse_trim_out(mirge_ctx*, const char*, int64_t, int32_t, int32_t, const mirge_trim*, mirge_qc*, mirge_fqout*, mirge_reads**, int64_t*);
 int mirge_fqout_finish(mirge_ctx*, mirge_fqout*, int64_t*);
 void mirge_fqout_destroy(mirge_fqout*);
+int mirge_nearest_scan(mirge_ctx*, const char*, const int64_t*, int64_t, const char*, const int64_t*, int64_t, int32_t*, int32_t*, int32_t*, int32_t*);
+int mirge_nearest_unmapped(mirge_ctx*, const mirge_reads*, const mirge_result*, const char*, const int64_t*, int64_t, int32_t, mirge_nearest**);
+int64_t mirge_nearest_count(const mirge_nearest*);
+int mirge_nearest_fetch(const mirge_nearest*, uint32_t*, int32_t*, int32_t*, int32_t*, int32_t*);
+int mirge_nearest_stats(const mirge_nearest*, int64_t*);
+void mirge_nearest_destroy(mirge_nearest*);
 int mirge_ctx_timer_start(mirge_ctx*);
 int mirge_ctx_timer_stop(mirge_ctx*, double*);
 int mirge_ctx_profile_enable(mirge_ctx*, int32_t);
@@ -1369,6 +1375,45 @@ def trf_row_counts(ctx: Context, uniq: DeviceReads, rows) -> np.ndarray:
     if rows.size:
         _check(load().mirge_trf_row_counts(ctx._h, uniq._h, rows, rows.shape[0], out), "mirge_trf_row_counts")
     return out
+
+
+NEAREST_STATS = ("unmapped", "short", "long", "considered", "reported")
+
+
+def _flat_ascii(seqs) -> Tuple[np.ndarray, np.ndarray, int]:
+    """sequences (``FlatSeqs`` or strings) -> (bytes as uint8, never empty; int64 offsets; their number)"""
+    flat = seqs if isinstance(seqs, FlatSeqs) else FlatSeqs.from_list(list(seqs))
+    data = np.ascontiguousarray(flat.data, dtype=np.uint8)
+    return (data if data.size else np.zeros(1, np.uint8)), np.ascontiguousarray(flat.offsets, dtype=np.int64), len(flat)
+
+
+def nearest_scan(ctx: Context, queries, targets) -> dict:
+    """``mirge_nearest_scan``: for EVERY query (``FlatSeqs`` or strings) against the targets in order -> ``dist``, ``hairpin``, ``start``,
+    ``end`` (int32; all -1 for a query outside 12 .. 64 letters or targets without a base); ``h[start:end]`` is the matched substring."""
+    q, q_off, n = _flat_ascii(queries)
+    t, t_off, n_t = _flat_ascii(targets)
+    out = {k: np.full(max(n, 1), -1, np.int32) for k in ("dist", "hairpin", "start", "end")}
+    _check(load().mirge_nearest_scan(ctx._h, q, q_off, n, t, t_off, n_t, out["dist"], out["hairpin"], out["start"], out["end"]), "mirge_nearest_scan")
+    return {k: a[:n] for k, a in out.items()}
+
+
+def nearest_unmapped(ctx: Context, uniq: DeviceReads, res: CascadeResult, targets, K: int) -> Tuple[dict, dict]:
+    """``mirge_nearest_unmapped``: the rows of ``uniq`` that ``res`` left unannotated, 12 .. 64 nt long, with D <= min(K, length // 8) ->
+    ({``row`` (uint32 handle index, ascending), ``dist``, ``hairpin``, ``start``, ``end`` (int32)}, {name of ``NEAREST_STATS``: int})"""
+    lib = load()
+    t, t_off, n_t = _flat_ascii(targets)
+    h = C.c_void_p()
+    _check(lib.mirge_nearest_unmapped(ctx._h, uniq._h, res._h, t, t_off, n_t, int(K), C.byref(h)), "mirge_nearest_unmapped")
+    try:
+        m = lib.mirge_nearest_count(h)
+        out = dict(row=np.zeros(m, np.uint32), **{k: np.zeros(m, np.int32) for k in ("dist", "hairpin", "start", "end")})
+        if m:
+            _check(lib.mirge_nearest_fetch(h, *(out[k] for k in ("row", "dist", "hairpin", "start", "end"))), "mirge_nearest_fetch")
+        st = np.zeros(len(NEAREST_STATS), np.int64)
+        _check(lib.mirge_nearest_stats(h, st), "mirge_nearest_stats")
+    finally:
+        lib.mirge_nearest_destroy(h)
+    return out, dict(zip(NEAREST_STATS, (int(x) for x in st)))
 
 
 def bam_huffman_probe(ctx: Context, counts, max_bits: int) -> np.ndarray:

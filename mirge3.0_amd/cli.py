@@ -13,7 +13,8 @@ scope (novel miRNA, BAM, tRF, DESeq2, miREC) are rejected instead of being ignor
 cluster SAMs and the selected / sorted tables of the reads aligned to their cluster sequences) and ``--unmapped-features``
 (``<sample>_features.tsv``, ``_cluster.txt``, ``_precursor.fa``), the tRNA fragment reports with ``--trf-report`` and the two
 clustering files per sample behind them with ``--trf-clusters``, ``<sample>.bedgraph`` or ``<sample>.plus.bedgraph`` /
-``<sample>.minus.bedgraph`` with this project's ``--coverage``).
+``<sample>.minus.bedgraph`` with this project's ``--coverage``, ``unmapped.nearest.csv`` and ``nearest.summary.csv`` with this
+project's ``--unmapped-nearest``).
 
 One process: all samples on one GPU, byte-compatible outputs.  Under ``torch.distributed.run`` with N
 ranks: samples are sharded one per GPU (multigpu.py); rank 0 gathers each sample's count columns and its
@@ -137,6 +138,13 @@ def parse_args(argv=None):
                          "<sample>.bedgraph (unstranded, the default) or <sample>.plus.bedgraph and <sample>.minus.bedgraph (stranded); "
                          "a row counts with its read count; chromosomes in the @SQ order of --sam-header FILE, else in byte order; "
                          "independent of --sam-out and --sorted-bam")
+    ap.add_argument("--unmapped-nearest", dest="unmapped_nearest", nargs="?", const="3", default=None, metavar="K",
+                    help="for every row of unmapped.csv of 12 to 64 nt, the hairpin of <org>_hairpin_<db> nearest to it by unit-cost edit "
+                         "distance (substitutions, insertions, deletions; forward strand), computed on the device by brute force against "
+                         "every base of the library: unmapped.nearest.csv (the rows with distance <= min(K, length // 8): hairpin, "
+                         "distance, 1-based start and end, the matched stretch, the mature miRNAs it overlaps, the counts), "
+                         "nearest.summary.csv and one run.log line per sample; K in 1 .. 8, a bare flag means 3; needs no genome; not "
+                         "with -spl, -rr, --backend bowtie or a sharded run")
     ap.add_argument("--coverage-bigwig", dest="coverage_bigwig", action="store_true",
                     help="with --coverage: also write the same runs as bigWig, sections, zoom levels and their deflate computed on the "
                          "device: <sample>.bw, or <sample>.plus.bw and <sample>.minus.bw when stranded; needs --sam-header FILE whose "
@@ -261,6 +269,10 @@ def parse_args(argv=None):
         ap.error(why)
     from . import trimmed_out
     why = trimmed_out.refusal(args)
+    if why:
+        ap.error(why)
+    from . import nearest
+    why = nearest.refusal(args)
     if why:
         ap.error(why)
     if args.qiagenumi and not (args.adapters and args.adapters[0][0] == "back"):

@@ -59,3 +59,4 @@ __device__ __forceinline__ void load_read(const GroupView<W>& g, uint32_t i, Mir
 #include "kernels_bw.hpp"
 #include "kernels_qc.hpp"
 #include "kernels_fq.hpp"
+#include "kernels_nearest.hpp"

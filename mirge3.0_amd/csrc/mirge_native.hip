@@ -61,3 +61,4 @@ static_assert(MIRGE_MAX_PASSES == MIRGE_MAX_PASSES_K, "pass cap");
 #include "native_bw.hpp"
 #include "native_qc.hpp"
 #include "native_fq.hpp"
+#include "native_nearest.hpp"

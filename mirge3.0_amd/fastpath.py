@@ -374,6 +374,11 @@ def reports(args, workDir, ref_db: str, base_names, casc, uniq, res, out, merges
             if getattr(args, "unmapped_features", False):  # generate_featureFiles / get_precursors (novel_mir.py:424-428)
                 from . import unmapped_features as _unmapped_features
                 out["unmapped_features"] = _unmapped_features.run(args, ctx, workDir, base_names, tm)
+    if getattr(args, "unmapped_nearest", None):  # --unmapped-nearest: the rows of unmapped.csv against the hairpins by edit distance
+        if ann is not None or res is None:
+            raise RuntimeError("--unmapped-nearest needs the cascade's result on the device (a single-process run)")
+        from . import nearest as _nearest
+        out["unmapped_nearest"] = _nearest.run(args, workDir, base_names, casc, uniq, res, order, tm, ref_db=ref_db)
     # --bgzf-out rides on args into both text exporters below: <sample>.sam.gz / <sample>.bedgraph.gz with their .gzi (bgzf.py)
     if getattr(args, "bgzf_out", False) and not (getattr(args, "sam_out", False) or getattr(args, "coverage", None)):
         raise RuntimeError("--bgzf-out needs --sam-out or --coverage")
